@@ -10,6 +10,12 @@ per-GPU batch is fixed, the global batch grows with N.
 
 Prints one JSON line on rank 0.  The matrix is resident in HBM before the timed
 region; nothing under /root/reference is read.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line; the CPU
+baselines (seconds to minutes of host work) run only with `--full`.  `--dump-outputs DIR`
+writes the result of the last timed step as DIR/<name>.npy (float64), for
+comparing two builds output for output: the seeds of every step are fixed by the
+arguments.
 """
 import argparse
 import json
@@ -49,19 +55,26 @@ WORKLOADS = {
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 
 
+def dump_outputs(path, **arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 (every field here is an integer below 2^53, so exact)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def load_matrix(name):
     from plo_testlib import DATA, read_sms, to_csr_mod
     fname, p, batch, desc = WORKLOADS[name]
     if fname.endswith(".slp"):
-        # data/32x32x32_15096_L.sms is absent upstream; rebuild it from the stored SLP with bin/SLPchecker
-        import fcntl
+        # data/32x32x32_15096_L.sms is absent upstream; rebuild it from the stored SLP with bin/SLPchecker.
+        # The tool comes from __graft_entry__.build(): the benchmark builds nothing and writes nothing into the tree,
+        # which may be read-only to the user who runs it.
         import subprocess
-        host = os.path.join(ROOT, "plinopt_amd", "csrc", "host")
-        with open(os.path.join(host, ".build.lock"), "w") as lk:      # ranks of one node share the tree: build once
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.check_call(["make", "-s", "-C", host])
-            fcntl.flock(lk, fcntl.LOCK_UN)
-        out = subprocess.run([os.path.join(ROOT, "bin", "SLPchecker"), "-q", str(p), os.path.join(DATA, fname)],
+        slpchecker = os.path.join(ROOT, "bin", "SLPchecker")
+        if not os.path.exists(slpchecker):
+            raise FileNotFoundError("%s not built: run __graft_entry__.build() first" % slpchecker)
+        out = subprocess.run([slpchecker, "-q", str(p), os.path.join(DATA, fname)],
                              capture_output=True, text=True, check=True).stdout.splitlines()
         m, n = int(out[0].split()[0]), int(out[0].split()[1])
         rows = [[] for _ in range(m)]
@@ -267,6 +280,8 @@ def bench_cob(args):
     dt = max_over_ranks(time.perf_counter() - t0)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, best=list(res))          # (zeros_v, zeros_w, index, found) of the last step's enumeration
     per = kms / steps
     algo = st["algo_bytes"]
     out = {"metric": "CoB candidate rows/sec", "value": total * world * steps / dt, "unit": "candidates/s", "n_gpus": world, "steps": steps, "warmup": warm,
@@ -282,7 +297,7 @@ def bench_cob(args):
     ir = issue_roofline("cob", "plo::cob_tab_kernel", per)
     if ir:
         out["roofline_hbm"] = out["roofline"]; out["roofline"] = ir       # the issue view is the meaningful one; the HBM figure stays beside it
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # BASELINE configs[2] AS WRITTEN (`bin/sparsifier -c 4 data/4x4x4_49_156_L.sms`, over Q): 4^4 = 256 candidate rows per enumeration, a few
         # dozen enumerations per run -- wall clock of the whole command on the GPU (two 31-bit primes per enumeration + check over Q) and on the host
         import re as _re
@@ -374,6 +389,8 @@ def bench_tril(args):
     per_rank_ms = gather_per_rank(dev, world, kms, wall[0], wall[1])
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, best=[fl[0], fl[1], seed, variant])      # (ADD, SCA, seed, variant) of the last step's winner
     st = G.last_stats
     per = kms / steps
     algo = st["algo_bytes"] * batch
@@ -392,7 +409,7 @@ def bench_tril(args):
     ir = issue_roofline("tril", "plo::tril_kernel", per)
     if ir:
         out["roofline_hbm"] = out["roofline"]; out["roofline"] = ir
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         n = 2000
         t0 = time.perf_counter()
         ob = O.search(0, n)
@@ -444,6 +461,8 @@ def bench_kmethod(args):
     per_rank_ms = gather_per_rank(dev, world, kms, wall[0], wall[1])
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, best=[word[0], word[1], seed])          # (adds + muls, adds, seed) of the last step's winner
     per = kms / steps
     out = {"metric": "kernel-method restarts/sec", "value": gb * steps / dt, "unit": "restarts/s", "n_gpus": world, "steps": steps, "warmup": warm,
            "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
@@ -454,7 +473,7 @@ def bench_kmethod(args):
            "per_rank_ms": {"columns": PER_RANK_COLUMNS, "rows": per_rank_ms, "steps": steps},
            "roofline": issue_roofline("kmethod", "plo::kmethod_kernel", per) or {"bound": "issue", "achieved": 0.0, "peak": 1.0, "unit": "scalar wave-instructions/clk/CU", "frac": 0.0, "traffic": None},
            "kernel": {"lds_bytes": st["lds_bytes"], "waves_per_wg": st["waves_per_wg"], "grid": st["grid"], "launches_per_step": st["launches"]}}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         M = OracleMatrix(m, n, rp, c, v, p)
         nref = 300
         t0 = time.perf_counter()
@@ -474,7 +493,11 @@ def main():
     ap.add_argument("--workload", default="32x32x32", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="candidates per GPU per step (default: per workload)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure the CPU baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's result as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.workload == "cob":
         return bench_cob(args)
@@ -522,12 +545,13 @@ def main():
     kernel_ms = 0.0
     launches = 0
     best_word = None
+    last = None                                    # (adds + muls, adds, seed) of the latest step's winner
     stats = None
     search_s = 0.0                                 # wall time of this rank's searches (library call) and of the all-reduces, timed steps only
     reduce_s = 0.0
 
     def step(k, timed):
-        nonlocal kernel_ms, launches, best_word, stats, search_s, reduce_s
+        nonlocal kernel_ms, launches, best_word, last, stats, search_s, reduce_s
         s0 = seed_base + k * global_batch          # this step's global seed range
         my0 = s0 + rank * batch                    # this rank's shard (independent candidates, no exchange)
         t_a = time.perf_counter()
@@ -541,6 +565,7 @@ def main():
         if timed:
             search_s += t_b - t_a
             reduce_s += time.perf_counter() - t_b
+        last = (fl[0], fl[1], seed)
         if best_word is None or (fl, seed) < (best_word[2], best_word[1]):
             best_word = (word, seed, fl)
         return seed
@@ -563,6 +588,8 @@ def main():
     # where a loss of scaling would come from: every rank's kernel time, search wall time and time inside the all-reduce
     per_rank_ms = gather_per_rank(dev, world, kernel_ms, search_s, reduce_s)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, best=list(last))
         # dominant kernel: cse_wave_kernel; algorithmic bytes per candidate B_cand
         per_launch_ms = kernel_ms / max(launches, 1)
         algo_bytes = stats["algo_bytes"]
@@ -635,7 +662,7 @@ def main():
             ir = issue_roofline(args.workload, "plo::cse_wave_kernel", search_ms)
             if ir:      # LDS-resident candidates: the HBM figure says nothing, report instruction issue (committed PMC counters of this workload)
                 out["roofline_hbm"] = out["roofline"]; out["roofline"] = ir
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = (cpu_baseline_host_engine(m, n, rp, c, v, p) if args.workload == "32x32x32"
                                    else cpu_baseline(m, n, rp, c, v, p))
         print(json.dumps(out))

@@ -1,4 +1,4 @@
-"""bench.py prints ONE JSON line with the driver's contract keys plus `roofline` and `cpu_baseline`; checked on the
+"""bench.py prints ONE JSON line with the driver's contract keys plus `roofline` (and `cpu_baseline` with --full); checked on the
 quick workloads (the default, config 5, takes a minute and is run by the driver itself), and under
 torch.distributed.run with one rank (the launch line the driver uses for N > 1)."""
 import json
@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from plo_testlib import ROOT
@@ -26,7 +27,7 @@ def one_line(cmd, env=None):
 
 @pytest.mark.parametrize("workload", ["winograd", "tril"])
 def test_bench_line_has_the_contract_keys(hip, workload):
-    d = one_line([sys.executable, "bench.py", "--workload", workload, "--steps", "2", "--warmup", "1"])
+    d = one_line([sys.executable, "bench.py", "--workload", workload, "--steps", "2", "--warmup", "1", "--full"])
     assert KEYS <= set(d) and ROOF <= set(d["roofline"]) and CPUB <= set(d["cpu_baseline"])
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True and d["vs_baseline"] is None
     assert d["value"] > 0 and d["roofline"]["frac"] == pytest.approx(d["roofline"]["achieved"] / d["roofline"]["peak"])
@@ -56,3 +57,15 @@ def test_lds_resident_cse_workload_reports_issue_roofline(hip):
     d = one_line([sys.executable, "bench.py", "--workload", "4x4x4_L", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
     assert d["roofline"]["bound"] == "issue" and d["roofline"]["frac"] == pytest.approx(d["roofline"]["achieved"] / d["roofline"]["peak"])
     assert d["roofline_hbm"]["bound"] == "hbm" and d["value"] > 1e7
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one(hip, tmp_path):
+    """without --full no CPU baseline is walked; --dump-outputs writes the last timed step's winner, the same one the line reports
+    when there is one step and no warmup (the line's `best` covers the warmup too), and the same from run to run"""
+    cmd = [sys.executable, "bench.py", "--workload", "4x4x4_L", "--steps", "1", "--warmup", "0", "--dump-outputs"]
+    d = one_line(cmd + [str(tmp_path / "a")])
+    assert KEYS <= set(d) and "cpu_baseline" not in d and d["steps"] == 1 and d["ms_per_step"] > 0
+    a = np.load(tmp_path / "a" / "best.npy")
+    assert a.dtype == np.float64 and a.tolist() == [d["best"]["adds_plus_muls"], d["best"]["adds"], d["best"]["seed"]]
+    one_line(cmd + [str(tmp_path / "b")])
+    assert np.array_equal(np.load(tmp_path / "b" / "best.npy"), a)
