@@ -258,6 +258,30 @@ int  plo_tril_search(plo_tril_plan_t *plan, uint64_t seed0, uint64_t nseeds, plo
 int  plo_tril_search_multi(const plo_qcsr_t *A, const plo_qcsr_t *B, const plo_qcsr_t *T, int expanded, uint64_t seed0, uint64_t nseeds,
                            int ndev, const int *devices, plo_tril_best_t *best, plo_stats_t *stats);
 
+/* ---- In-place linear search: replaces the body of the restart loop of SearchLinearAlgorithm
+ * (include/plinopt_inplace.inl:621-669; driver src/inplacer.cpp:38-80).  A (m x n) as rational CSR (plo_qcsr_t above, columns
+ * sorted per row; empty rows allowed: the barrier Atom(' ', l, ' ', 0) of :474-476).  One candidate (seed) = a row permutation
+ * drawn from the seed's stream (no sign flips), then variant 0 = the unoriented program (:636) and variant 1 = the oriented
+ * program APPENDED to variant 0's simplified one (:654: the reference does not clear lProgram), simplified and counted as one
+ * program (ROWS = 2m); cost = (ADD, SCA) lexicographic as :637-641, ties to the smaller (seed, variant).  seed ==
+ * PLO_LIN_BASE_SEED is the unpermuted oriented program of :613 (the incumbent; both halves of ops6 hold it).  Entries +-1 run
+ * the unit kernel, others are residues modulo the 31-bit prime 2147483629 (as plo_tril_plan_create_q); the host replays and
+ * checks the winner over Q.  PLO_E_UNSUPPORTED: a row of more than 64 entries, or an entry that vanishes modulo the prime;
+ * PLO_E_CAPACITY: more than 16382 rows or columns, or a program that does not fit LDS.  Without a device every entry returns
+ * PLO_E_HIP. */
+#define PLO_LIN_BASE_SEED 0xFFFFFFFFFFFFFFFFull
+typedef struct { uint32_t add, sca, rows; uint32_t variant; uint64_t seed; } plo_lin_best_t;
+typedef struct plo_lin_plan plo_lin_plan_t;
+int  plo_lin_plan_create_q(const plo_qcsr_t *A, plo_lin_plan_t **plan);
+void plo_lin_plan_destroy(plo_lin_plan_t *plan);
+/* ops6[6k..6k+5] = ADD,SCA,ROWS of variant 0 then of variant 1 for candidate k (seeds[k], or seed0+k when seeds==NULL) */
+int  plo_lin_cost_many(plo_lin_plan_t *plan, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats);
+int  plo_lin_search(plo_lin_plan_t *plan, uint64_t seed0, uint64_t nseeds, plo_lin_best_t *best, plo_stats_t *stats);
+/* The restart loop over `ndev` devices from one process: contiguous shards of the seed range, one host thread, one device and
+ * one plan each, the minimum under (ADD, SCA), then (seed, variant), by the two MIN all-reduces of plo_cse_search_multi.  Same
+ * conventions for devices, stats and PLO_MULTI_REDUCE. */
+int  plo_lin_search_multi(const plo_qcsr_t *A, uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_lin_best_t *best, plo_stats_t *stats);
+
 /* Pack / unpack the (cost, seed) word used by the grid reduction and by the
  * single 8-byte MIN all-reduce across ranks (the `#pragma omp critical`
  * best-so-far of include/plinopt_optimize.inl:1214-1237).  seed_off is the

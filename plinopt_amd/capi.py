@@ -24,6 +24,7 @@ EXPORTS = [
     "plo_cse_enum_cost_many_plan", "plo_cse_enum_search_plan",
     "plo_cob_search", "plo_cob_search_range", "plo_cob_search_batch",
     "plo_tril_plan_create", "plo_tril_plan_create_x", "plo_tril_plan_create_q", "plo_tril_plan_destroy", "plo_tril_cost_many", "plo_tril_search",
+    "plo_lin_plan_create_q", "plo_lin_plan_destroy", "plo_lin_cost_many", "plo_lin_search", "plo_lin_search_multi",
     "plo_pack_cost",
 ]
 
@@ -72,6 +73,10 @@ class QCSR(ctypes.Structure):
 
 class TrilBest(ctypes.Structure):
     _fields_ = [("add", ctypes.c_uint32), ("sca", ctypes.c_uint32), ("mul", ctypes.c_uint32), ("variant", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
+
+
+class LinBest(ctypes.Structure):
+    _fields_ = [("add", ctypes.c_uint32), ("sca", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("variant", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
 
 
 class PloError(RuntimeError):
@@ -147,6 +152,13 @@ def lib():
                                               ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(Best), ctypes.POINTER(Stats)]
         L.plo_tril_search_multi.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                             ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(TrilBest), ctypes.POINTER(Stats)]
+        L.plo_lin_plan_create_q.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(ctypes.c_void_p)]
+        L.plo_lin_plan_destroy.argtypes = [ctypes.c_void_p]
+        L.plo_lin_plan_destroy.restype = None
+        L.plo_lin_cost_many.argtypes = [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_uint64, u32p, ctypes.POINTER(Stats)]
+        L.plo_lin_search.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(LinBest), ctypes.POINTER(Stats)]
+        L.plo_lin_search_multi.argtypes = [ctypes.POINTER(QCSR), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                           ctypes.POINTER(LinBest), ctypes.POINTER(Stats)]
         L.plo_multi_comm_inits.restype = ctypes.c_uint64
         L.plo_pack_cost.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32]
         L.plo_pack_cost.restype = ctypes.c_uint64

@@ -306,6 +306,12 @@ template <class F> class SlpEval {
         auto it = vars.find(t);
         if (it != vars.end()) return it->second;
         if (t[0] == 'i' && t.size() > 1 && isdigit((unsigned char)t[1])) { Lin v; v.emplace_back(std::stol(t.substr(1)), f.one()); return v; }
+        // any other unassigned word is an input of matrixBuilder (plinopt_programs.inl:1517-1524), numbered by first appearance:
+        // an unassigned <letter><index> is input column <index> (the reference's numbering for the in-order prologue of
+        // input2Temps, e.g. `inplacer -t`: z0:=t0; z1:=t1; ...)
+        if (isalpha((unsigned char)t[0]) && t.size() > 1 && std::all_of(t.begin() + 1, t.end(), [](char ch) { return isdigit((unsigned char)ch) != 0; })) {
+            Lin v; v.emplace_back(std::stol(t.substr(1)), f.one()); return v;
+        }
         throw std::runtime_error("SLP: undefined variable " + t);
     }
 public:

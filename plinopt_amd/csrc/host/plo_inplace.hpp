@@ -1,6 +1,7 @@
 // ==========================================================================
-// plo_inplace.hpp -- host side of the in-place trilinear search (bin/trilplacer):
-// builds, simplifies and prints the program of one candidate over the rationals.
+// plo_inplace.hpp -- host side of the in-place trilinear search (bin/trilplacer) and of the
+// in-place linear search (bin/inplacer): builds, simplifies and prints the program of one
+// candidate over the rationals.
 // The GPU (plo_tril_search) only counts; the winning (seed, variant) is replayed
 // here to obtain the text.  Inputs the device path refuses (entries other than
 // +-1, empty rows) are searched here with OpenMP.
@@ -9,7 +10,8 @@
 // :133-144, orientindex/nextindex :179-236, simplify :243-311, pushvariables
 // :322-393, LinearAlgorithm :400-502, TransposedDoubleAlgorithm :507-598 (-e),
 // DoubleExpand :676-716, TriLinearProgram :732-806,
-// SearchTriLinearAlgorithm :812-929; output syntax plinopt_inplace.h:101-112.
+// SearchTriLinearAlgorithm :812-929; output syntax plinopt_inplace.h:101-112;
+// SearchLinearAlgorithm :604-673, Pprint :163-175.
 // Random choices: the per-candidate stream of include/plinopt_hip.h.
 // ==========================================================================
 #pragma once
@@ -258,6 +260,42 @@ inline TrilCandidate tril_candidate(const QMat &A, const QMat &B, const QMat &T,
         }
     }
     return C;
+}
+
+// ---------------------------------------------------------------------------------------------------------- bin/inplacer
+// One loop of SearchLinearAlgorithm (:621-669): a row permutation (:626-633, no sign flips), variant 0 = the unoriented program
+// (:636), variant 1 = the oriented program appended to variant 0's simplified one (:654: lProgram is not cleared; in_linear
+// appends, and its noop removal and simplify fixpoint run over the whole concatenation).  The stream is the trilinear
+// candidate's without the sign draws (plo_lin.hip); seed ~0 is the unpermuted oriented program of :613 (both variants hold it).
+struct LinCandidate { std::vector<uint32_t> perm; Tricount ops[2]; InplaceProgram prog[2]; };
+
+inline LinCandidate lin_candidate(const QMat &A, uint64_t seed) {
+    const size_t m = A.rowdim();
+    LinCandidate C; C.perm.resize(m);
+    for (size_t i = 0; i < m; ++i) C.perm[i] = (uint32_t)i;
+    const std::vector<int8_t> plus(m, 1);
+    const InRows R{&A, &C.perm, &plus};
+    CandRng rng(seed);
+    if (seed == ~0ull) { C.ops[0] = in_linear(C.prog[0], R, 'z', false, true, rng); C.ops[1] = C.ops[0]; C.prog[1] = C.prog[0]; return C; }
+    for (size_t i = m; i > 1; --i) std::swap(C.perm[i - 1], C.perm[rng.next() % (uint32_t)i]);
+    C.ops[0] = in_linear(C.prog[0], R, 'z', false, false, rng);
+    C.prog[1] = C.prog[0];
+    C.ops[1] = in_linear(C.prog[1], R, 'z', false, true, rng);
+    return C;
+}
+
+// input2Temps (plinopt_library.inl:307-317) then Pprint (:163-175) of one variant: barrier k is output perm[k].  Variant 1 holds
+// 2m barriers and the reference reads perm[k] past its end for the second half; here barrier k >= m is output perm[k - m], the
+// same row computed again: the output is assigned the same value twice and the program stays correct.
+inline std::string lin_text(const LinCandidate &C, int variant, size_t ntemps, char inchar) {
+    std::ostringstream os;
+    for (size_t i = 0; i < ntemps; ++i) os << 'z' << i << ":=" << inchar << i << ";\n";
+    size_t numop = 0;
+    for (const auto &a : C.prog[variant].at) {
+        if (a.ope == ' ') os << 'o' << C.perm[numop++ % C.perm.size()] << ":=";
+        in_print_atom(os, a);
+    }
+    return os.str();
 }
 
 } // namespace plo

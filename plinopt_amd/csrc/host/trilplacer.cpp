@@ -10,9 +10,8 @@
 // -e: the expanded variant (TransposedDoubleAlgorithm on DoubleExpand(P^T)), on the device too.
 // ==========================================================================
 #include "plo_inplace.hpp"
+#include "plo_dl.hpp"
 #include "../../../include/plinopt_hip.h"
-#include <dlfcn.h>
-#include <libgen.h>
 #include <unistd.h>
 #include <chrono>
 #include <fstream>
@@ -28,13 +27,8 @@ struct HipTril {
     decltype(&plo_tril_plan_create_q) create = nullptr; decltype(&plo_tril_plan_destroy) destroy = nullptr; decltype(&plo_tril_search) search = nullptr;
     decltype(&plo_tril_search_multi) search_multi = nullptr;
     bool load() {
-        std::vector<std::string> cand;
-        for (const char *v : {"PLO_HIP_LIB", "PLINOPT_HIP_LIB"}) if (const char *e = getenv(v)) cand.emplace_back(e);   // (one name for the tools and plinopt_amd/capi.py; the older one still works)
-        char buf[4096]; ssize_t k = readlink("/proc/self/exe", buf, sizeof buf - 1);
-        if (k > 0) { buf[k] = 0; std::string d = dirname(buf); cand.push_back(d + "/../plinopt_amd/libplinopt_hip.so"); cand.push_back(d + "/libplinopt_hip.so"); }
-        cand.emplace_back("libplinopt_hip.so");
-        for (auto &c : cand) { h = dlopen(c.c_str(), RTLD_NOW | RTLD_GLOBAL); if (h) break; }
-        if (!h) { std::cerr << "# \033[1;31mERROR: cannot load libplinopt_hip.so: " << dlerror() << "\033[0m\n"; return false; }
+        h = open_hip_lib();
+        if (!h) return false;
         init = (decltype(init))dlsym(h, "plo_init"); last_error = (decltype(last_error))dlsym(h, "plo_last_error");
         create = (decltype(create))dlsym(h, "plo_tril_plan_create_q"); destroy = (decltype(destroy))dlsym(h, "plo_tril_plan_destroy");
         search = (decltype(search))dlsym(h, "plo_tril_search"); search_multi = (decltype(search_multi))dlsym(h, "plo_tril_search_multi");

@@ -13,6 +13,7 @@
 #include "plo_cse_big.hip"
 #include "plo_cob.hip"
 #include "plo_tril.hip"
+#include "plo_lin.hip"
 #include "../../include/plinopt_hip.h"
 
 #include <algorithm>
@@ -2007,6 +2008,195 @@ int plo_tril_search_multi(const plo_qcsr_t *A, const plo_qcsr_t *B, const plo_qc
             done += piece;
         }
         plo_tril_plan_destroy(plan);
+        return r_;
+    });
+    if (rc != PLO_OK) return rc;
+    plo_stats_t agg{}; int win = -1;
+    rc = multi_min(sh, ndev, devices, agg, win);
+    if (rc != PLO_OK) return rc;
+    if (win < 0) return fail(PLO_E_INTERNAL, "no candidate reported");
+    *best = bests[(size_t)win];
+    agg.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = agg;
+    return PLO_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------- inplacer
+struct plo_lin_plan {
+    plo::LinPlan P{};
+    void *d_img = nullptr; uint32_t *d_err = nullptr; unsigned long long *d_best = nullptr;
+    uint32_t waves_per_wg = 4, lds_bytes = 0, blocks_per_cu = 1;
+    uint64_t algo_bytes = 0;
+    bool rational = false;           // coefficients other than +-1: residues modulo PLO_TRIL_PRIME, lin_kernel<true>
+};
+
+namespace {
+int lin_launch(plo_lin_plan *pl, plo::TrilJob J, plo_stats_t *st) {
+    HIPCHK(hipMemsetAsync(pl->d_err, 0, sizeof(uint32_t), g_stream));
+    J.err = pl->d_err;
+    const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * pl->blocks_per_cu, need));
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, g_stream));
+    if (pl->rational) hipLaunchKernelGGL((plo::lin_kernel<true>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+    else hipLaunchKernelGGL((plo::lin_kernel<false>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, g_stream)); HIPCHK(hipEventSynchronize(e1));
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    uint32_t err = 0;
+    HIPCHK(hipMemcpy(&err, pl->d_err, sizeof err, hipMemcpyDeviceToHost));
+    if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = pl->lds_bytes; st->waves_per_wg = pl->waves_per_wg; st->algo_bytes = pl->algo_bytes; st->candidates += J.ncand; }
+    if (err) return fail(err == plo::TERR_CAP ? PLO_E_INTERNAL : PLO_E_UNSUPPORTED, "device (inplacer): error " + std::to_string(err));
+    return PLO_OK;
+}
+} // namespace
+
+extern "C" {
+
+int plo_lin_plan_create_q(const plo_qcsr_t *A, plo_lin_plan_t **plan)
+{
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!A || !plan) return fail(PLO_E_ARG, "null argument");
+    if (!A->rowptr || !A->col || !A->num || A->m == 0 || A->n == 0) return fail(PLO_E_ARG, "bad matrix");
+    if (A->m > 16382u || A->n > 16382u) return fail(PLO_E_CAPACITY, "more than 16382 rows or columns (an atom holds 14-bit variables)");
+    const uint32_t m = A->m, nnz = A->rowptr[m];
+    bool unit = true;
+    for (uint32_t i = 0; i < m; ++i) {
+        const uint32_t len = A->rowptr[i + 1] - A->rowptr[i];
+        if (len > 64) return fail(PLO_E_UNSUPPORTED, "row with more than 64 entries: host path only");
+        for (uint32_t e = A->rowptr[i]; e < A->rowptr[i + 1]; ++e) {
+            const int64_t nu = A->num[e], de = A->den ? A->den[e] : 1;
+            if (nu == 0 || de == 0) return fail(PLO_E_ARG, "zero entry or zero denominator");
+            if (!(de == 1 && (nu == 1 || nu == -1))) unit = false;
+            if (de % (int64_t)PLO_TRIL_PRIME == 0 || nu % (int64_t)PLO_TRIL_PRIME == 0) return fail(PLO_E_UNSUPPORTED, "entry not a unit modulo the device's prime: host path only");
+            if (A->col[e] >= A->n || (e > A->rowptr[i] && A->col[e] <= A->col[e - 1])) return fail(PLO_E_ARG, "columns must be sorted and in range");
+        }
+    }
+    // the concatenation of variant 1: the simplified program of variant 0 (at most 2 nnz + m atoms) and the oriented one,
+    // checked row by row against 2 len + 2 more atoms (t_linear)
+    // (nnz <= 64 m <= 64 * 16382 here: no overflow)
+    const uint32_t cap = round_up(4u * nnz + 3u * m + 2u, 64);
+    if (cap > 65535u) return fail(PLO_E_CAPACITY, "program does not fit LDS (and counts of 16 bits in the packed key)");
+    const size_t bytes = round_up((m + 1) * 2, 16) + round_up(nnz * 2, 16) + round_up(nnz, 16) + round_up(nnz * 4, 16) + 16;
+    plo_lin_plan *pl = new plo_lin_plan();
+    pl->rational = !unit;
+    std::vector<uint8_t> img(bytes, 0);
+    if (hipMalloc(&pl->d_img, bytes) != hipSuccess) { delete pl; return fail(PLO_E_HIP, "hipMalloc"); }
+    size_t off = 0;
+    plo::TrilMat &D = pl->P.M;
+    D.m = m; D.n = A->n; D.nnz = nnz;
+    uint16_t *rp = (uint16_t *)(img.data() + off); D.rp = (const uint16_t *)((uint8_t *)pl->d_img + off); off += round_up((m + 1) * 2, 16);
+    uint16_t *cl = (uint16_t *)(img.data() + off); D.col = (const uint16_t *)((uint8_t *)pl->d_img + off); off += round_up(nnz * 2, 16);
+    int8_t *vl = (int8_t *)(img.data() + off); D.val = (const int8_t *)((uint8_t *)pl->d_img + off); off += round_up(nnz, 16);
+    uint32_t *vp = (uint32_t *)(img.data() + off); D.valp = (const uint32_t *)((uint8_t *)pl->d_img + off);
+    for (uint32_t i = 0; i <= m; ++i) rp[i] = (uint16_t)A->rowptr[i];
+    for (uint32_t e = 0; e < nnz; ++e) {
+        cl[e] = (uint16_t)A->col[e];
+        const int64_t nu = A->num[e], de = A->den ? A->den[e] : 1;
+        vl[e] = unit ? (int8_t)nu : 0;
+        int64_t a = nu % (int64_t)PLO_TRIL_PRIME, d = de % (int64_t)PLO_TRIL_PRIME; if (a < 0) a += PLO_TRIL_PRIME; if (d < 0) d += PLO_TRIL_PRIME;
+        vp[e] = (uint32_t)((uint64_t)a * inv_mod((uint32_t)d, PLO_TRIL_PRIME) % PLO_TRIL_PRIME);
+    }
+    pl->P.cap = cap; pl->P.p = unit ? 0u : PLO_TRIL_PRIME;
+    pl->P.lds_per_wave = round_up(8u * cap + 2u * ((m + 1u) & ~1u), 16);      // atoms, permutation
+    pl->algo_bytes = 8 + 2ull * (m + 1) + 3ull * nnz;                           // the CSR image, once per candidate
+    // four waves (256 threads) per workgroup, as many workgroups per CU as the 160 KiB of LDS and the 32 waves per CU admit
+    pl->waves_per_wg = 4;
+    pl->lds_bytes = pl->P.lds_per_wave * pl->waves_per_wg;
+    if (pl->lds_bytes > 64u * 1024u) { pl->waves_per_wg = 1; pl->lds_bytes = pl->P.lds_per_wave; }
+    if (pl->lds_bytes > g_lds_max) { (void)hipFree(pl->d_img); delete pl; return fail(PLO_E_CAPACITY, "program does not fit LDS"); }
+    pl->blocks_per_cu = std::max<uint32_t>(1, std::min<uint32_t>(32u / pl->waves_per_wg, (uint32_t)(g_lds_max / pl->lds_bytes)));
+    const void *fn = pl->rational ? (const void *)plo::lin_kernel<true> : (const void *)plo::lin_kernel<false>;
+    if (hipMemcpy(pl->d_img, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess || hipMalloc((void **)&pl->d_err, 4) != hipSuccess ||
+        hipMalloc((void **)&pl->d_best, 8) != hipSuccess || hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes) != hipSuccess) {
+        plo_lin_plan_destroy(pl); return fail(PLO_E_HIP, "device setup of the inplacer plan failed");
+    }
+    *plan = pl;
+    return PLO_OK;
+}
+
+void plo_lin_plan_destroy(plo_lin_plan_t *pl)
+{
+    if (!pl) return;
+    if (pl->d_img) (void)hipFree(pl->d_img);
+    if (pl->d_err) (void)hipFree(pl->d_err);
+    if (pl->d_best) (void)hipFree(pl->d_best);
+    delete pl;
+}
+
+int plo_lin_cost_many(plo_lin_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats)
+{
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!pl || !ops6) return fail(PLO_E_ARG, "null argument");
+    if (n >= (1ull << 31)) return fail(PLO_E_ARG, "at most 2^31-1 candidates per call");
+    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0) return PLO_OK;
+    uint32_t *d_ops = nullptr; uint64_t *d_seeds = nullptr;
+    HIPCHK(hipMalloc((void **)&d_ops, n * 6 * sizeof(uint32_t)));
+    if (seeds && (hipMalloc((void **)&d_seeds, n * 8) != hipSuccess || hipMemcpy(d_seeds, seeds, n * 8, hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipFree(d_ops); if (d_seeds) (void)hipFree(d_seeds); return fail(PLO_E_HIP, "seed upload");
+    }
+    plo::TrilJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.ops = d_ops; J.best = nullptr;
+    int rc = lin_launch(pl, J, st);
+    if (rc == PLO_OK && hipMemcpy(ops6, d_ops, n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back");
+    (void)hipFree(d_ops); if (d_seeds) (void)hipFree(d_seeds);
+    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int plo_lin_search(plo_lin_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_lin_best_t *best, plo_stats_t *stats)
+{
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!pl || !best) return fail(PLO_E_ARG, "null argument");
+    if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
+    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
+    const auto t0 = std::chrono::steady_clock::now();
+    const unsigned long long init = ~0ull;
+    HIPCHK(hipMemcpy(pl->d_best, &init, 8, hipMemcpyHostToDevice));
+    plo::TrilJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.ops = nullptr; J.best = pl->d_best;
+    int rc = lin_launch(pl, J, st);
+    if (rc != PLO_OK) return rc;
+    unsigned long long w = 0;
+    HIPCHK(hipMemcpy(&w, pl->d_best, 8, hipMemcpyDeviceToHost));
+    if (w == init) return fail(PLO_E_INTERNAL, "no candidate reported");
+    best->add = (uint32_t)(w >> 48); best->sca = (uint32_t)(w >> 32) & 0xFFFFu;
+    best->variant = (uint32_t)(w & 1ull); best->rows = pl->P.M.m * (best->variant + 1u);       // one barrier per row, twice in variant 1
+    best->seed = seed0 + ((w & 0xFFFFFFFFull) >> 1);
+    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return PLO_OK;
+}
+
+int plo_lin_search_multi(const plo_qcsr_t *A, uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_lin_best_t *best, plo_stats_t *stats)
+{
+    if (!A || !best) return fail(PLO_E_ARG, "null argument");
+    if (ndev < 1 || ndev > 64) return fail(PLO_E_ARG, "device count outside [1,64]");
+    if (nseeds == 0 || nseeds >= (1ull << 62)) return fail(PLO_E_ARG, "1 .. 2^62-1 candidates per call");
+    DeviceGuard guard;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<MultiShard> sh; std::vector<plo_lin_best_t> bests((size_t)ndev);
+    int rc = multi_run(ndev, devices, seed0, nseeds, sh, [&](MultiShard &S, int) {
+        plo_lin_best_t &b = bests[(size_t)(&S - sh.data())];
+        plo_lin_plan_t *plan = nullptr;
+        int r_ = plo_lin_plan_create_q(A, &plan);
+        if (r_ != PLO_OK) return r_;
+        // (a launch takes at most 2^31-1 candidates: longer shards go in pieces, minimum under the same order)
+        bool have = false;
+        for (uint64_t done = 0; r_ == PLO_OK && done < S.cnt;) {
+            const uint64_t piece = std::min<uint64_t>(S.cnt - done, (1ull << 31) - 1ull);
+            plo_lin_best_t pb{}; plo_stats_t ps{};
+            r_ = plo_lin_search(plan, S.s0 + done, piece, &pb, &ps);
+            if (r_ != PLO_OK) break;
+            S.st.candidates += ps.candidates; S.st.launches += ps.launches; S.st.kernel_ms += ps.kernel_ms; S.st.grid = ps.grid; S.st.lds_bytes = ps.lds_bytes; S.st.waves_per_wg = ps.waves_per_wg; S.st.algo_bytes = ps.algo_bytes;
+            const unsigned long long hi = ((unsigned long long)pb.add << 32) | pb.sca, lo = ((pb.seed - seed0) << 1) | (pb.variant & 1u);      // (ADD, SCA) of :637-641, then (seed, variant)
+            if (!have || hi < S.hi || (hi == S.hi && lo < S.lo)) { S.hi = hi; S.lo = lo; b = pb; have = true; }
+            done += piece;
+        }
+        plo_lin_plan_destroy(plan);
         return r_;
     });
     if (rc != PLO_OK) return rc;

@@ -330,19 +330,35 @@ template <bool RAT> __device__ void t_pushvariables_ref(TrilProg &P, uint32_t nu
     }
 }
 
+// What bin/inplacer (plo_lin.hip) adds to t_linear, each behind a bit of its template parameter X (X = 0: the trilinear search's code):
+//   TL_APPEND    the atoms go after the program in P (the reference's Program is not cleared: :654) -- no P.n = 0;
+//   TL_EMPTYBAR  an empty row l is the barrier Atom(' ', l, ' ', 0) of :474-476 (src = l, no variable) instead of an error;
+//   TL_NOSIGN    no sign array: the rows are taken as they are (sgn may be null).
+enum : uint32_t { TL_APPEND = 1u, TL_EMPTYBAR = 2u, TL_NOSIGN = 4u };
+
 // :400-502 for matrices without empty rows; perm/sign describe the candidate's rows.  RAT = false: entries +-1 (small signed values,
 // no scaling atom in the transposed program); RAT = true: entries are residues of rationals modulo `prime`.
-template <bool RAT> __device__ void t_linear(TrilProg &P, const TrilMat &M, const uint16_t *perm, const uint8_t *sgn, uint32_t sbit, bool transposed,
+template <bool RAT, uint32_t X = 0u> __device__ void t_linear(TrilProg &P, const TrilMat &M, const uint16_t *perm, const uint8_t *sgn, uint32_t sbit, bool transposed,
                          bool oriented, uint32_t &rng, uint32_t lane, uint32_t ops[3], uint32_t cap, uint32_t *errw, uint32_t *bm, uint32_t prime) {
-    P.n = 0;
+    if constexpr (!(X & TL_APPEND)) P.n = 0;
     const unsigned long long tb0 = clock64(); (void)tb0;
     uint32_t preci = M.n;
     const int ONE = 1, MONE = RAT ? (int)(prime - 1u) : -1;
     for (uint32_t l = 0; l < M.m; ++l) {
         const uint32_t r = perm[l], b = M.rp[r], len = (uint32_t)M.rp[r + 1u] - b;
+        if constexpr ((X & TL_EMPTYBAR) != 0u) {
+            if (len == 0) {                                                                            // :474-476
+                if (P.n + 1u > cap) { if (lane == 0) atomicMax(errw, (uint32_t)TERR_CAP); return; }
+                if (lane == 0) P.at[P.n] = ta_make<RAT>(l, -1, 0u, T_BAR);
+                P.n += 1u;
+                TW_SYNC();
+                continue;
+            }
+        }
         if (len == 0 || len > 64u) { if (lane == 0) atomicMax(errw, (uint32_t)TERR_ROW); return; }
         if (P.n + 2u * len + 2u > cap) { if (lane == 0) atomicMax(errw, (uint32_t)TERR_CAP); return; }
-        const bool neg = (sgn[l] >> sbit) & 1u;
+        bool neg = false;
+        if constexpr (!(X & TL_NOSIGN)) neg = (sgn[l] >> sbit) & 1u;
         int c = -1, v = 0;
         if (lane < len) {
             c = M.col[b + lane];

@@ -310,3 +310,69 @@ class TrilPlan:
         capi.check(capi.lib().plo_tril_search(self._h, seed0, nseeds, ctypes.byref(b), ctypes.byref(st)))
         self.last_stats = st.as_dict()
         return (b.add, b.sca, b.mul), b.seed, b.variant
+
+
+LIN_BASE_SEED = (1 << 64) - 1
+
+
+def _qcsr(m, n, rowptr, col, num, den):
+    den = [1] * len(num) if den is None else den
+    a = ((ctypes.c_uint32 * len(rowptr))(*rowptr), (ctypes.c_uint32 * max(len(col), 1))(*col), (ctypes.c_int64 * max(len(num), 1))(*[int(x) for x in num]),
+         (ctypes.c_int64 * max(len(den), 1))(*[int(x) for x in den]))
+    return capi.QCSR(m, n, a[0], a[1], a[2], a[3]), a
+
+
+class LinPlan:
+    """Mirror of the restart loop of `SearchLinearAlgorithm` (reference include/plinopt_inplace.inl:604-673, bin/inplacer):
+    A (m x n) as a rational CSR (rowptr, col, num[, den]); empty rows allowed.  `cost_many` returns, per seed,
+    ((ADD,SCA,ROWS) of variant 0 = unoriented, (ADD,SCA,ROWS) of variant 1 = oriented appended to variant 0);
+    `search` the best ((ADD, SCA, ROWS), seed, variant) under the reference's order (:637-641), ties to the smaller
+    (seed, variant).  LIN_BASE_SEED is the unpermuted oriented program of :613."""
+
+    def __init__(self, m, n, rowptr, col, num, den=None, device=None):
+        L = capi.lib()
+        if device is not None:
+            capi.check(L.plo_init(device))
+        self._h = None
+        self._csr, self._keep = _qcsr(m, n, rowptr, col, num, den)
+        h = ctypes.c_void_p()
+        capi.check(L.plo_lin_plan_create_q(ctypes.byref(self._csr), ctypes.byref(h)))
+        self._h = h
+        self.last_stats = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                capi.lib().plo_lin_plan_destroy(self._h); self._h = None
+        except Exception:
+            pass
+
+    def cost_many(self, seeds=None, seed0=0, n=0):
+        L = capi.lib()
+        if seeds is not None:
+            n = len(seeds); sp = (ctypes.c_uint64 * max(n, 1))(*seeds)
+        else:
+            sp = None
+        ops = (ctypes.c_uint32 * (6 * max(n, 1)))()
+        st = capi.Stats()
+        capi.check(L.plo_lin_cost_many(self._h, sp, seed0, n, ops, ctypes.byref(st)))
+        self.last_stats = st.as_dict()
+        return [(tuple(ops[6 * k:6 * k + 3]), tuple(ops[6 * k + 3:6 * k + 6])) for k in range(n)]
+
+    def search(self, seed0, nseeds):
+        b, st = capi.LinBest(), capi.Stats()
+        capi.check(capi.lib().plo_lin_search(self._h, seed0, nseeds, ctypes.byref(b), ctypes.byref(st)))
+        self.last_stats = st.as_dict()
+        return (b.add, b.sca, b.rows), b.seed, b.variant
+
+
+def lin_search_multi(m, n, rowptr, col, num, den, seed0, nseeds, devices):
+    """`plo_lin_search_multi`: the restart loop of SearchLinearAlgorithm over the listed devices from this process.
+    Returns (((ADD, SCA, ROWS), seed, variant), stats)."""
+    L = capi.lib()
+    csr, keep = _qcsr(m, n, rowptr, col, num, den)
+    dv = (ctypes.c_int * len(devices))(*devices)
+    b, st = capi.LinBest(), capi.Stats()
+    capi.check(L.plo_lin_search_multi(ctypes.byref(csr), seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
+    del keep
+    return ((b.add, b.sca, b.rows), b.seed, b.variant), st.as_dict()
