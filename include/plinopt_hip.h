@@ -282,6 +282,41 @@ int  plo_lin_search(plo_lin_plan_t *plan, uint64_t seed0, uint64_t nseeds, plo_l
  * conventions for devices, stats and PLO_MULTI_REDUCE. */
 int  plo_lin_search_multi(const plo_qcsr_t *A, uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_lin_best_t *best, plo_stats_t *stats);
 
+/* ---- De Groote orbit search: replaces the body of the restart loop of src/orbiter.cpp:272-324.  (L, R, P) is a row-major
+ * triple of an m x k x n product (L: r x mk, columns a k + b; R: r x kn, columns b n + c; P: mn x r, rows a n + c) as
+ * rational CSR; m, k, n come from the shapes by an exact integer square root.  A candidate (U, V, W) transforms it into
+ * L.(U^-1 (x) V), R.(V^-T (x) W), (U (x) W^-1).P and is scored by three counts: nnz (non-zero entries), nno (those that are
+ * not +-1) and cost = nnz (PLO_ORBIT_DENSITY, `-s`, and every run modulo a number) or L.m + R.m + P.n minus the rows of
+ * L.J and R.G and columns of H.P with exactly one non-zero (PLO_ORBIT_CANONICAL, `-c`).
+ * Stream of candidate `seed` (the reference's zoiRandomMatrix, :58-139, default branch :125-136, made reproducible): the
+ * CandRng of the seed (splitmix64, then x <- 950706376 x mod 2^31-1); U (m x m), then V (k x k), then W (n x n), each of size
+ * s drawn as: P by Fisher-Yates (for i = s down to 2, swap P[i-1] and P[next() % i]), Q the same way, D[i] = next() & 1 for
+ * i = 0..s-1, then row-major for i < j: M[P[i]][Q[j]] = next() % 3 - 1; the diagonal M[P[i]][Q[i]] = D[i] ? 1 : -1.
+ * seed == PLO_ORBIT_BASE_SEED is U = V = W = identity: the input itself.
+ * Order: the lexicographic minimum of (cost, nnz, nno, seed); the tool's winner improves on the input iff its (cost, nnz, nno)
+ * is smaller than the input's.
+ * modulus 0 is Q: the rows of L and R and the columns of P are scaled to integers on the host, and the counts are exact.
+ * PLO_E_UNSUPPORTED: a modulus of 2^31 or more, a denominator that is no unit modulo the modulus, or a Q input whose
+ * transformed entries are not provably below 2^62 (row L1 norm times 2^(s-2)).  PLO_E_CAPACITY: m, k or n above 16, more
+ * than 4096 rows, more than 2^20 transformed entries, or an input that does not fit LDS.  PLO_E_ARG: shapes that are not
+ * m k, k n, m n. */
+#define PLO_ORBIT_BASE_SEED 0xFFFFFFFFFFFFFFFFull     /* U = V = W = identity: the input itself */
+#define PLO_ORBIT_DENSITY   0                          /* -s */
+#define PLO_ORBIT_CANONICAL 2                          /* -c */
+typedef struct { uint32_t cost, nnz, nno, reserved; uint64_t seed; } plo_orbit_best_t;
+typedef struct plo_orbit_plan plo_orbit_plan_t;
+int  plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P,
+                             uint64_t modulus /* 0 = Q */, int measure, plo_orbit_plan_t **plan);
+void plo_orbit_plan_destroy(plo_orbit_plan_t *plan);
+/* out3[3k..3k+2] = cost, nnz, nno of candidate k (seeds[k], or seed0+k when seeds==NULL) */
+int  plo_orbit_cost_many(plo_orbit_plan_t *plan, const uint64_t *seeds, uint64_t seed0, uint64_t n,
+                         uint32_t *out3 /* cost, nnz, nno per seed */, plo_stats_t *stats);
+int  plo_orbit_search(plo_orbit_plan_t *plan, uint64_t seed0, uint64_t nseeds, plo_orbit_best_t *best, plo_stats_t *stats);
+/* The restart loop over `ndev` devices from one process, as plo_lin_search_multi: contiguous shards, one host thread, device
+ * and plan each, the minimum under (cost, nnz, nno, seed).  Same conventions for devices, stats and PLO_MULTI_REDUCE. */
+int  plo_orbit_search_multi(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure,
+                            uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats);
+
 /* Pack / unpack the (cost, seed) word used by the grid reduction and by the
  * single 8-byte MIN all-reduce across ranks (the `#pragma omp critical`
  * best-so-far of include/plinopt_optimize.inl:1214-1237).  seed_off is the

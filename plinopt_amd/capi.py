@@ -25,6 +25,7 @@ EXPORTS = [
     "plo_cob_search", "plo_cob_search_range", "plo_cob_search_batch",
     "plo_tril_plan_create", "plo_tril_plan_create_x", "plo_tril_plan_create_q", "plo_tril_plan_destroy", "plo_tril_cost_many", "plo_tril_search",
     "plo_lin_plan_create_q", "plo_lin_plan_destroy", "plo_lin_cost_many", "plo_lin_search", "plo_lin_search_multi",
+    "plo_orbit_plan_create_q", "plo_orbit_plan_destroy", "plo_orbit_cost_many", "plo_orbit_search", "plo_orbit_search_multi",
     "plo_pack_cost",
 ]
 
@@ -77,6 +78,10 @@ class TrilBest(ctypes.Structure):
 
 class LinBest(ctypes.Structure):
     _fields_ = [("add", ctypes.c_uint32), ("sca", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("variant", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
+
+
+class OrbitBest(ctypes.Structure):
+    _fields_ = [("cost", ctypes.c_uint32), ("nnz", ctypes.c_uint32), ("nno", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
 
 
 class PloError(RuntimeError):
@@ -159,6 +164,13 @@ def lib():
         L.plo_lin_search.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(LinBest), ctypes.POINTER(Stats)]
         L.plo_lin_search_multi.argtypes = [ctypes.POINTER(QCSR), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                            ctypes.POINTER(LinBest), ctypes.POINTER(Stats)]
+        L.plo_orbit_plan_create_q.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+        L.plo_orbit_plan_destroy.argtypes = [ctypes.c_void_p]
+        L.plo_orbit_plan_destroy.restype = None
+        L.plo_orbit_cost_many.argtypes = [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_uint64, u32p, ctypes.POINTER(Stats)]
+        L.plo_orbit_search.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(OrbitBest), ctypes.POINTER(Stats)]
+        L.plo_orbit_search_multi.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                             ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(OrbitBest), ctypes.POINTER(Stats)]
         L.plo_multi_comm_inits.restype = ctypes.c_uint64
         L.plo_pack_cost.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32]
         L.plo_pack_cost.restype = ctypes.c_uint64

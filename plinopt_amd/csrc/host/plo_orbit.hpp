@@ -1,0 +1,136 @@
+// ==========================================================================
+// plo_orbit.hpp -- one candidate of the De Groote orbit search (bin/orbiter; reference src/orbiter.cpp:272-324) on the host.
+// A candidate is (U, V, W), drawn from the seed's stream (include/plinopt_hip.h, PLO_ORBIT_*), and transforms the
+// row-major triple (L, R, P) of an m x k x n product into L.(U^-1 (x) V), R.(V^-T (x) W), (U (x) W^-1).P.  Read as
+// matrices, row i of L (m x k) becomes U^-T X V, row i of R (k x n) becomes V^-1 Y W and column j of P (m x n) becomes
+// U Z W^-T: the "sandwich" form, without the Kronecker products.  U = Pi_P T Pi_Q^T with T upper triangular, +-1 on
+// its diagonal and {-1, 0, 1} above, so U^-1 = Pi_Q T^-1 Pi_P^T is integral (back-substitution, entries of size at most
+// 2^(s-2)).  The same function scores a candidate in the host loop and replays the winner.
+// ==========================================================================
+#pragma once
+#include "plo_host.hpp"
+
+namespace plo {
+
+enum { ORBIT_DENSITY = 0, ORBIT_CANONICAL = 2 };
+constexpr uint64_t ORBIT_BASE = ~0ull;
+
+// M (s x s, row-major) and its inverse, integers
+struct Zoi { size_t s = 0; std::vector<int64_t> M, Mi; };
+
+// the stream's matrix: Fisher-Yates P, then Q, then the s sign bits, then the strict upper part row-major
+inline Zoi zoi_matrix(CandRng &rng, size_t s) {
+    std::vector<size_t> P(s), Q(s);
+    std::iota(P.begin(), P.end(), 0); std::iota(Q.begin(), Q.end(), 0);
+    for (auto *perm : {&P, &Q})
+        for (size_t i = s; i > 1; --i) std::swap((*perm)[i - 1], (*perm)[rng.next() % i]);
+    std::vector<int64_t> T(s * s, 0), Ti(s * s, 0);
+    for (size_t i = 0; i < s; ++i) T[i * s + i] = (rng.next() & 1u) ? 1 : -1;
+    for (size_t i = 0; i < s; ++i) for (size_t j = i + 1; j < s; ++j) T[i * s + j] = (int64_t)(rng.next() % 3u) - 1;
+    // T^-1 by back-substitution, column by column (1/d = d for d = +-1)
+    for (size_t j = 0; j < s; ++j)
+        for (size_t i = j + 1; i-- > 0;) {
+            int64_t acc = i == j ? 1 : 0;
+            for (size_t l = i + 1; l <= j; ++l) acc -= T[i * s + l] * Ti[l * s + j];
+            Ti[i * s + j] = T[i * s + i] * acc;
+        }
+    Zoi z; z.s = s; z.M.assign(s * s, 0); z.Mi.assign(s * s, 0);
+    for (size_t i = 0; i < s; ++i) for (size_t j = i; j < s; ++j) { z.M[P[i] * s + Q[j]] = T[i * s + j]; z.Mi[Q[i] * s + P[j]] = Ti[i * s + j]; }
+    return z;
+}
+inline Zoi zoi_identity(size_t s) { Zoi z; z.s = s; z.M.assign(s * s, 0); for (size_t i = 0; i < s; ++i) z.M[i * s + i] = 1; z.Mi = z.M; return z; }
+
+struct OrbitUVW { Zoi U, V, W; };
+inline OrbitUVW orbit_uvw(size_t m, size_t k, size_t n, uint64_t seed) {
+    if (seed == ORBIT_BASE) return {zoi_identity(m), zoi_identity(k), zoi_identity(n)};
+    CandRng rng(seed);
+    OrbitUVW c;
+    c.U = zoi_matrix(rng, m); c.V = zoi_matrix(rng, k); c.W = zoi_matrix(rng, n);
+    return c;
+}
+
+// m, k, n of a triple with L r x mk, R r x kn, P mn x r (exact integer square root of kn.mn/mk), false otherwise
+inline bool orbit_shape(size_t lm, size_t ln, size_t rm, size_t rn, size_t pm, size_t pn, size_t &m, size_t &k, size_t &n) {
+    if (lm != rm || lm != pn || ln == 0 || rn == 0 || pm == 0) return false;
+    const unsigned __int128 num = (unsigned __int128)rn * pm;
+    if (num % ln) return false;
+    const uint64_t q = (uint64_t)(num / ln);
+    uint64_t s = 0;
+    for (uint64_t b = 1ull << 31; b; b >>= 1) if ((unsigned __int128)(s | b) * (s | b) <= q) s |= b;
+    if (s == 0 || s * s != q || pm % s || rn % s) return false;
+    n = (size_t)s; m = pm / n; k = rn / n;
+    return m * k == ln && k * n == rn && m * n == pm;
+}
+
+struct OrbitCount { size_t cost = 0, nnz = 0, nno = 0; };
+inline bool operator<(const OrbitCount &a, const OrbitCount &b) { return std::tie(a.cost, a.nnz, a.nno) < std::tie(b.cost, b.nnz, b.nno); }
+inline bool operator==(const OrbitCount &a, const OrbitCount &b) { return std::tie(a.cost, a.nnz, a.nno) == std::tie(b.cost, b.nnz, b.nno); }
+
+// The triple over F, P kept as its transpose (the columns of P are what the sandwich transforms)
+template <class F> struct OrbitTriple { SparseMat<typename F::Elt> L, R, PT; size_t m = 0, k = 0, n = 0; };
+
+// one part of the sandwich: out_i(p, q) = sum over the entries (a, b, x) of row i of A[a][p] x B[b][q], for the rows of X
+// (columns a * cb + b; output pr x qc); A is sa x sa, B is sb x sb (row-major); Out gets the rows when asked
+template <class F> void orbit_part(const F &f, const SparseMat<typename F::Elt> &X, size_t cb, const std::vector<int64_t> &A, size_t sa,
+                                   const std::vector<int64_t> &B, size_t sb, OrbitCount &c, size_t &canon, SparseMat<typename F::Elt> *Out) {
+    using E = typename F::Elt;
+    std::vector<E> acc(sa * sb);
+    std::vector<E> Af(A.size()), Bf(B.size());
+    for (size_t t = 0; t < A.size(); ++t) Af[t] = f.fromInt(A[t]);
+    for (size_t t = 0; t < B.size(); ++t) Bf[t] = f.fromInt(B[t]);
+    if (Out) *Out = SparseMat<E>(X.rowdim(), sa * sb);
+    for (size_t i = 0; i < X.rowdim(); ++i) {
+        std::fill(acc.begin(), acc.end(), f.zero());
+        for (const auto &e : X.rows[i]) {
+            const size_t a = e.first / cb, b = e.first % cb;
+            for (size_t p = 0; p < sa; ++p) {
+                if (A[a * sa + p] == 0) continue;
+                const E ax = f.mul(Af[a * sa + p], e.second);
+                for (size_t q = 0; q < sb; ++q) if (B[b * sb + q] != 0) acc[p * sb + q] = f.add(acc[p * sb + q], f.mul(ax, Bf[b * sb + q]));
+            }
+        }
+        size_t nz = 0;
+        for (size_t t = 0; t < acc.size(); ++t) {
+            if (f.isZero(acc[t])) continue;
+            ++nz; if (!absOne(f, acc[t])) ++c.nno;
+            if (Out) Out->rows[i].emplace_back(t, acc[t]);
+        }
+        c.nnz += nz; canon += nz == 1;
+    }
+}
+
+// counts of candidate `seed` (cost = nnz, or L.m + R.m + P.n - the rows with one non-zero for ORBIT_CANONICAL); the three
+// transformed matrices (P transposed back) when out is given
+template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &T, uint64_t seed, int measure, OrbitTriple<F> *out = nullptr) {
+    const OrbitUVW c = orbit_uvw(T.m, T.k, T.n, seed);
+    const size_t m = T.m, k = T.k, n = T.n;
+    auto tr = [](const std::vector<int64_t> &M, size_t s) { std::vector<int64_t> R(s * s); for (size_t i = 0; i < s; ++i) for (size_t j = 0; j < s; ++j) R[j * s + i] = M[i * s + j]; return R; };
+    OrbitCount r; size_t canon = 0;
+    orbit_part(f, T.L, k, c.U.Mi, m, c.V.M, k, r, canon, out ? &out->L : nullptr);                  // U^-T X V: A[a][p] = U^-1[a][p]
+    orbit_part(f, T.R, n, tr(c.V.Mi, k), k, c.W.M, n, r, canon, out ? &out->R : nullptr);           // V^-1 Y W: A[b][p] = V^-1[p][b]
+    orbit_part(f, T.PT, n, tr(c.U.M, m), m, tr(c.W.Mi, n), n, r, canon, out ? &out->PT : nullptr);  // U Z W^-T: A[a][p] = U[p][a], B[c][q] = W^-1[q][c]
+    r.cost = measure == ORBIT_CANONICAL ? T.L.rowdim() + T.R.rowdim() + T.PT.rowdim() - canon : r.nnz;
+    if (out) { out->m = m; out->k = k; out->n = n; }
+    return r;
+}
+
+// The Brent equations of the triple over F, exactly: sum_t L[t][a k + b] R[t][b' n + c] P[a' n + c'][t] = [a = a'][b = b'][c = c'].
+// Over Q an overflow throws; the caller reports it as a failed check.
+template <class F> bool orbit_mm_check(const F &f, const OrbitTriple<F> &T) {
+    using E = typename F::Elt;
+    const size_t m = T.m, k = T.k, n = T.n, mk = m * k, kn = k * n, mn = m * n;
+    std::vector<E> S(mk * kn * mn, f.zero());
+    for (size_t t = 0; t < T.L.rowdim(); ++t)
+        for (const auto &l : T.L.rows[t]) for (const auto &r : T.R.rows[t]) {
+            const E lr = f.mul(l.second, r.second);
+            for (const auto &p : T.PT.rows[t]) { E &s = S[(l.first * kn + r.first) * mn + p.first]; s = f.add(s, f.mul(lr, p.second)); }
+        }
+    for (size_t a = 0; a < m; ++a) for (size_t b = 0; b < k; ++b) for (size_t b2 = 0; b2 < k; ++b2) for (size_t c = 0; c < n; ++c)
+        for (size_t a2 = 0; a2 < m; ++a2) for (size_t c2 = 0; c2 < n; ++c2) {
+            const E &s = S[((a * k + b) * kn + b2 * n + c) * mn + a2 * n + c2];
+            if (!(a == a2 && b == b2 && c == c2) ? !f.isZero(s) : !f.isOne(s)) return false;
+        }
+    return true;
+}
+
+} // namespace plo

@@ -14,6 +14,7 @@
 #include "plo_cob.hip"
 #include "plo_tril.hip"
 #include "plo_lin.hip"
+#include "plo_orbit.hip"
 #include "../../include/plinopt_hip.h"
 
 #include <algorithm>
@@ -2197,6 +2198,244 @@ int plo_lin_search_multi(const plo_qcsr_t *A, uint64_t seed0, uint64_t nseeds, i
             done += piece;
         }
         plo_lin_plan_destroy(plan);
+        return r_;
+    });
+    if (rc != PLO_OK) return rc;
+    plo_stats_t agg{}; int win = -1;
+    rc = multi_min(sh, ndev, devices, agg, win);
+    if (rc != PLO_OK) return rc;
+    if (win < 0) return fail(PLO_E_INTERNAL, "no candidate reported");
+    *best = bests[(size_t)win];
+    agg.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = agg;
+    return PLO_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------- orbiter
+struct plo_orbit_plan {
+    plo::OrbitPlan P{};
+    void *d_img = nullptr; uint64_t *d_best = nullptr;
+    uint32_t waves_per_wg = 4, lds_bytes = 0, blocks_per_cu = 1, grid_max = 1;
+    uint64_t algo_bytes = 0;
+};
+
+namespace {
+// m, k, n from L (r x mk), R (r x kn), P (mn x r): n = sqrt(kn mn / mk) exactly
+bool orbit_shape(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint32_t &m, uint32_t &k, uint32_t &n) {
+    if (L->m != R->m || L->m != P->n || L->n == 0 || R->n == 0 || P->m == 0) return false;
+    const uint64_t num = (uint64_t)R->n * P->m;
+    if (num % L->n) return false;
+    const uint64_t q = num / L->n;
+    uint64_t s = 0;
+    for (uint64_t b = 1ull << 31; b; b >>= 1) if ((s | b) * (s | b) <= q) s |= b;
+    if (s == 0 || s * s != q || P->m % s || R->n % s) return false;
+    n = (uint32_t)s; m = P->m / n; k = R->n / n;
+    return (uint64_t)m * k == L->n && (uint64_t)k * n == R->n && (uint64_t)m * n == P->m;
+}
+const char *qcsr_defect(const plo_qcsr_t *A) {
+    if (!A->rowptr || (A->rowptr[A->m] && (!A->col || !A->num))) return "null arrays";
+    for (uint32_t i = 0; i < A->m; ++i) {
+        if (A->rowptr[i + 1] < A->rowptr[i]) return "row pointers decrease";
+        for (uint32_t e = A->rowptr[i]; e < A->rowptr[i + 1]; ++e) {
+            if (A->num[e] == 0 || (A->den && A->den[e] <= 0)) return "zero entry or non-positive denominator";
+            if (A->col[e] >= A->n || (e > A->rowptr[i] && A->col[e] <= A->col[e - 1])) return "columns must be sorted and in range";
+        }
+    }
+    return nullptr;
+}
+int64_t gcd64(int64_t a, int64_t b) { if (a < 0) a = -a; if (b < 0) b = -b; while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
+
+int orbit_launch(plo_orbit_plan *pl, plo::OrbitJob J, plo_stats_t *st) {
+    const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(pl->grid_max, need));
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, g_stream));
+    if (pl->P.p) hipLaunchKernelGGL((plo::orbit_kernel<true>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+    else hipLaunchKernelGGL((plo::orbit_kernel<false>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, g_stream)); HIPCHK(hipEventSynchronize(e1));
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = pl->lds_bytes; st->waves_per_wg = pl->waves_per_wg; st->algo_bytes = pl->algo_bytes; st->candidates += J.ncand; }
+    return PLO_OK;
+}
+} // namespace
+
+extern "C" {
+
+int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, plo_orbit_plan_t **plan)
+{
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
+    if (measure != PLO_ORBIT_DENSITY && measure != PLO_ORBIT_CANONICAL) return fail(PLO_E_ARG, "measure must be PLO_ORBIT_DENSITY or PLO_ORBIT_CANONICAL");
+    if (modulus == 1) return fail(PLO_E_ARG, "modulus 1");
+    uint32_t m = 0, k = 0, n = 0;
+    if (!orbit_shape(L, R, P, m, k, n)) return fail(PLO_E_ARG, "shapes are not r x mk, r x kn, mn x r");
+    for (const plo_qcsr_t *A : {L, R, P}) if (const char *d = qcsr_defect(A)) return fail(PLO_E_ARG, d);
+    if (modulus >= (1ull << 31)) return fail(PLO_E_UNSUPPORTED, "modulus of 2^31 or more: host path only");
+    if (m > 16 || k > 16 || n > 16) return fail(PLO_E_CAPACITY, "m, k or n above 16");
+    const uint32_t r = L->m;
+    if (r > 4096) return fail(PLO_E_CAPACITY, "more than 4096 rows");
+    if ((uint64_t)r * (m * k + k * n + m * n) >= (1ull << 21)) return fail(PLO_E_CAPACITY, "2^21 transformed entries or more (21-bit counts in the key)");
+    // the rows of L, of R and of P^T, each as (position, value) lists
+    std::vector<std::vector<std::pair<uint16_t, std::pair<int64_t, int64_t>>>> rows(3u * r);
+    for (uint32_t i = 0; i < r; ++i) {
+        for (uint32_t e = L->rowptr[i]; e < L->rowptr[i + 1]; ++e) rows[i].push_back({(uint16_t)((L->col[e] / k) << 8 | (L->col[e] % k)), {L->num[e], L->den ? L->den[e] : 1}});
+        for (uint32_t e = R->rowptr[i]; e < R->rowptr[i + 1]; ++e) rows[r + i].push_back({(uint16_t)((R->col[e] / n) << 8 | (R->col[e] % n)), {R->num[e], R->den ? R->den[e] : 1}});
+    }
+    for (uint32_t i = 0; i < P->m; ++i)
+        for (uint32_t e = P->rowptr[i]; e < P->rowptr[i + 1]; ++e) rows[2u * r + P->col[e]].push_back({(uint16_t)((i / n) << 8 | (i % n)), {P->num[e], P->den ? P->den[e] : 1}});
+    std::vector<int64_t> val, scale(3u * r, 1);
+    std::vector<uint16_t> pos;
+    std::vector<uint32_t> rp{0};
+    const uint32_t inv_size[3] = {m, k, n};            // the factor of each part with an inverse: U^-1, V^-1, W^-T
+    for (uint32_t g = 0; g < 3u * r; ++g) {
+        if (modulus) {
+            for (auto &e : rows[g]) {
+                const int64_t mo = (int64_t)modulus;
+                int64_t a = e.second.first % mo, d = e.second.second % mo; if (a < 0) a += mo;
+                if (gcd64(d, mo) != 1) return fail(PLO_E_UNSUPPORTED, "a denominator is not invertible modulo the modulus");
+                const uint64_t v = (uint64_t)a * inv_mod((uint32_t)d, (uint32_t)modulus) % modulus;
+                if (v) { pos.push_back(e.first); val.push_back((int64_t)v); }
+            }
+        } else {
+            // scale the row to integers by the lcm of its denominators; |sums| <= L1 * 2^(s-2) < 2^62
+            __int128 l = 1;
+            for (auto &e : rows[g]) { const int64_t d = e.second.second; l = l / gcd64((int64_t)(l % d), d) * d; if (l > ((__int128)1 << 62)) return fail(PLO_E_UNSUPPORTED, "row scale above 2^62 (int64 bound): host path only"); }
+            __int128 l1 = 0;
+            for (auto &e : rows[g]) {
+                const __int128 v = (__int128)e.second.first * (l / e.second.second);
+                l1 += v < 0 ? -v : v;
+                if (l1 > ((__int128)1 << 62)) return fail(PLO_E_UNSUPPORTED, "row L1 norm above 2^62 (int64 bound): host path only");
+                pos.push_back(e.first); val.push_back((int64_t)v);
+            }
+            const uint32_t s = inv_size[g / r];
+            if ((l1 << (s >= 2 ? s - 2 : 0)) >= ((__int128)1 << 62)) return fail(PLO_E_UNSUPPORTED, "row L1 norm times 2^(s-2) reaches 2^62 (int64 bound): host path only");
+            scale[g] = (int64_t)l;
+        }
+        rp.push_back((uint32_t)val.size());
+    }
+    const uint32_t nnz = (uint32_t)val.size(), nrows = 3u * r, smax = std::max(m, std::max(k, n));
+    plo_orbit_plan *pl = new plo_orbit_plan();
+    plo::OrbitPlan &Q = pl->P;
+    Q.m = m; Q.k = k; Q.n = n; Q.r = r; Q.nnz = nnz; Q.measure = (uint32_t)measure; Q.p = modulus;
+    // shared LDS: values, scales, row pointers, positions
+    Q.off_scale = round_up(8u * nnz, 16); Q.off_rp = Q.off_scale + round_up(8u * nrows, 16); Q.off_pos = Q.off_rp + round_up(4u * (nrows + 1u), 16);
+    Q.shared_bytes = Q.off_pos + round_up(2u * nnz, 16);
+    // a wave: A_L (m x m), B_L (k x k), A_R (k x k), B_R (n x n), A_P (m x m), B_P (n x n), T^-1, T, P and Q, row counters
+    const uint32_t sz[6] = {m, k, k, n, m, n};
+    uint32_t off = 0;
+    for (int f = 0; f < 6; ++f) { Q.off_fac[f] = off; off += round_up(8u * sz[f] * sz[f], 16); }
+    Q.off_ti = off; off += round_up(8u * smax * smax, 16);
+    Q.off_t = off; off += round_up(smax * smax, 16);
+    Q.off_perm = off; off += 32;
+    Q.off_cnt = off; off += round_up(2u * nrows + 2u, 16);
+    Q.lds_per_wave = off;
+    pl->algo_bytes = 10ull * nnz + 12ull * nrows;
+    pl->lds_bytes = 0;
+    for (uint32_t w : {4u, 2u, 1u}) { const uint32_t b = Q.shared_bytes + w * Q.lds_per_wave; if (b <= g_lds_max && b <= 64u * 1024u) { pl->waves_per_wg = w; pl->lds_bytes = b; break; } }
+    if (!pl->lds_bytes) { delete pl; return fail(PLO_E_CAPACITY, "input does not fit LDS"); }
+    pl->blocks_per_cu = std::max<uint32_t>(1, std::min<uint32_t>(32u / pl->waves_per_wg, (uint32_t)(g_lds_max / pl->lds_bytes)));
+    pl->grid_max = (uint32_t)g_cus * pl->blocks_per_cu;
+    // the device image: values, scales, row pointers, positions
+    const size_t bytes = (size_t)Q.shared_bytes;
+    std::vector<uint8_t> img(bytes, 0);
+    memcpy(img.data(), val.data(), 8u * nnz); memcpy(img.data() + Q.off_scale, scale.data(), 8u * nrows);
+    memcpy(img.data() + Q.off_rp, rp.data(), 4u * (nrows + 1u)); memcpy(img.data() + Q.off_pos, pos.data(), 2u * nnz);
+    const void *fn = modulus ? (const void *)plo::orbit_kernel<true> : (const void *)plo::orbit_kernel<false>;
+    if (hipMalloc(&pl->d_img, bytes) != hipSuccess || hipMemcpy(pl->d_img, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc((void **)&pl->d_best, 16ull * pl->grid_max * pl->waves_per_wg) != hipSuccess ||
+        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes) != hipSuccess) {
+        plo_orbit_plan_destroy(pl); return fail(PLO_E_HIP, "device setup of the orbiter plan failed");
+    }
+    uint8_t *d = (uint8_t *)pl->d_img;
+    Q.val = (const int64_t *)d; Q.scale = (const int64_t *)(d + Q.off_scale); Q.rp = (const uint32_t *)(d + Q.off_rp); Q.pos = (const uint16_t *)(d + Q.off_pos);
+    *plan = pl;
+    return PLO_OK;
+}
+
+void plo_orbit_plan_destroy(plo_orbit_plan_t *pl)
+{
+    if (!pl) return;
+    if (pl->d_img) (void)hipFree(pl->d_img);
+    if (pl->d_best) (void)hipFree(pl->d_best);
+    delete pl;
+}
+
+int plo_orbit_cost_many(plo_orbit_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *out3, plo_stats_t *stats)
+{
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!pl || !out3) return fail(PLO_E_ARG, "null argument");
+    if (n >= (1ull << 31)) return fail(PLO_E_ARG, "at most 2^31-1 candidates per call");
+    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0) return PLO_OK;
+    uint32_t *d_out = nullptr; uint64_t *d_seeds = nullptr;
+    HIPCHK(hipMalloc((void **)&d_out, n * 3 * sizeof(uint32_t)));
+    if (seeds && (hipMalloc((void **)&d_seeds, n * 8) != hipSuccess || hipMemcpy(d_seeds, seeds, n * 8, hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipFree(d_out); if (d_seeds) (void)hipFree(d_seeds); return fail(PLO_E_HIP, "seed upload");
+    }
+    plo::OrbitJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.out3 = d_out; J.best = nullptr;
+    int rc = orbit_launch(pl, J, st);
+    if (rc == PLO_OK && hipMemcpy(out3, d_out, n * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back");
+    (void)hipFree(d_out); if (d_seeds) (void)hipFree(d_seeds);
+    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int plo_orbit_search(plo_orbit_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_orbit_best_t *best, plo_stats_t *stats)
+{
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!pl || !best) return fail(PLO_E_ARG, "null argument");
+    if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
+    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t slots = (uint64_t)pl->grid_max * pl->waves_per_wg;
+    HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, 16 * slots, g_stream));
+    plo::OrbitJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.out3 = nullptr; J.best = pl->d_best;
+    int rc = orbit_launch(pl, J, st);
+    if (rc != PLO_OK) return rc;
+    std::vector<uint64_t> w(2 * slots);
+    HIPCHK(hipMemcpy(w.data(), pl->d_best, 16 * slots, hipMemcpyDeviceToHost));
+    uint64_t bk = ~0ull, bi = ~0ull;
+    for (uint64_t s = 0; s < slots; ++s) if (w[2 * s + 1] != ~0ull && (w[2 * s] < bk || (w[2 * s] == bk && w[2 * s + 1] < bi))) { bk = w[2 * s]; bi = w[2 * s + 1]; }
+    if (bi == ~0ull) return fail(PLO_E_INTERNAL, "no candidate reported");
+    best->cost = (uint32_t)(bk >> 42); best->nnz = (uint32_t)(bk >> 21) & 0x1FFFFFu; best->nno = (uint32_t)bk & 0x1FFFFFu; best->reserved = 0;
+    best->seed = seed0 + bi;
+    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return PLO_OK;
+}
+
+int plo_orbit_search_multi(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure,
+                           uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats)
+{
+    if (!L || !R || !P || !best) return fail(PLO_E_ARG, "null argument");
+    if (ndev < 1 || ndev > 64) return fail(PLO_E_ARG, "device count outside [1,64]");
+    if (nseeds == 0 || nseeds >= (1ull << 62)) return fail(PLO_E_ARG, "1 .. 2^62-1 candidates per call");
+    DeviceGuard guard;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<MultiShard> sh; std::vector<plo_orbit_best_t> bests((size_t)ndev);
+    int rc = multi_run(ndev, devices, seed0, nseeds, sh, [&](MultiShard &S, int) {
+        plo_orbit_best_t &b = bests[(size_t)(&S - sh.data())];
+        plo_orbit_plan_t *plan = nullptr;
+        int r_ = plo_orbit_plan_create_q(L, R, P, modulus, measure, &plan);
+        if (r_ != PLO_OK) return r_;
+        // (a launch takes at most 2^31-1 candidates: longer shards go in pieces, minimum under the same order)
+        bool have = false;
+        for (uint64_t done = 0; r_ == PLO_OK && done < S.cnt;) {
+            const uint64_t piece = std::min<uint64_t>(S.cnt - done, (1ull << 31) - 1ull);
+            plo_orbit_best_t pb{}; plo_stats_t ps{};
+            r_ = plo_orbit_search(plan, S.s0 + done, piece, &pb, &ps);
+            if (r_ != PLO_OK) break;
+            S.st.candidates += ps.candidates; S.st.launches += ps.launches; S.st.kernel_ms += ps.kernel_ms; S.st.grid = ps.grid; S.st.lds_bytes = ps.lds_bytes; S.st.waves_per_wg = ps.waves_per_wg; S.st.algo_bytes = ps.algo_bytes;
+            const unsigned long long hi = ((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, lo = pb.seed - seed0;   // (cost, nnz, nno), then seed
+            if (!have || hi < S.hi || (hi == S.hi && lo < S.lo)) { S.hi = hi; S.lo = lo; b = pb; have = true; }
+            done += piece;
+        }
+        plo_orbit_plan_destroy(plan);
         return r_;
     });
     if (rc != PLO_OK) return rc;

@@ -376,3 +376,62 @@ def lin_search_multi(m, n, rowptr, col, num, den, seed0, nseeds, devices):
     capi.check(L.plo_lin_search_multi(ctypes.byref(csr), seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
     del keep
     return ((b.add, b.sca, b.rows), b.seed, b.variant), st.as_dict()
+
+
+ORBIT_BASE_SEED = (1 << 64) - 1
+ORBIT_DENSITY, ORBIT_CANONICAL = 0, 2
+
+
+class OrbitPlan:
+    """Mirror of the restart loop of the reference's orbiter (src/orbiter.cpp:272-324, bin/orbiter): the triple L (r x mk),
+    R (r x kn), P (mn x r), each as a rational CSR (m, n, rowptr, col, num[, den]), over Q (modulus 0) or Z_modulus
+    (< 2^31), scored by `measure` (ORBIT_DENSITY or ORBIT_CANONICAL).  `cost_many` returns (cost, nnz, nno) per seed;
+    `search` the best ((cost, nnz, nno), seed), ties to the smaller seed.  ORBIT_BASE_SEED is the input itself."""
+
+    def __init__(self, L, R, P, modulus=0, measure=ORBIT_DENSITY, device=None):
+        lib = capi.lib()
+        if device is not None:
+            capi.check(lib.plo_init(device))
+        self._h = None
+        self._csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
+        h = ctypes.c_void_p()
+        capi.check(lib.plo_orbit_plan_create_q(*[ctypes.byref(c) for c, _ in self._csr], modulus, measure, ctypes.byref(h)))
+        self._h = h
+        self.last_stats = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                capi.lib().plo_orbit_plan_destroy(self._h); self._h = None
+        except Exception:
+            pass
+
+    def cost_many(self, seeds=None, seed0=0, n=0):
+        lib = capi.lib()
+        if seeds is not None:
+            n = len(seeds); sp = (ctypes.c_uint64 * max(n, 1))(*seeds)
+        else:
+            sp = None
+        out = (ctypes.c_uint32 * (3 * max(n, 1)))()
+        st = capi.Stats()
+        capi.check(lib.plo_orbit_cost_many(self._h, sp, seed0, n, out, ctypes.byref(st)))
+        self.last_stats = st.as_dict()
+        return [tuple(out[3 * k:3 * k + 3]) for k in range(n)]
+
+    def search(self, seed0, nseeds):
+        b, st = capi.OrbitBest(), capi.Stats()
+        capi.check(capi.lib().plo_orbit_search(self._h, seed0, nseeds, ctypes.byref(b), ctypes.byref(st)))
+        self.last_stats = st.as_dict()
+        return (b.cost, b.nnz, b.nno), b.seed
+
+
+def orbit_search_multi(L, R, P, modulus, measure, seed0, nseeds, devices):
+    """`plo_orbit_search_multi`: the orbit search over the listed devices from this process (L, R, P as for OrbitPlan).
+    Returns (((cost, nnz, nno), seed), stats)."""
+    lib = capi.lib()
+    csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
+    dv = (ctypes.c_int * len(devices))(*devices)
+    b, st = capi.OrbitBest(), capi.Stats()
+    capi.check(lib.plo_orbit_search_multi(*[ctypes.byref(c) for c, _ in csr], modulus, measure, seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
+    del csr
+    return ((b.cost, b.nnz, b.nno), b.seed), st.as_dict()
