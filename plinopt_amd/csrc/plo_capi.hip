@@ -412,12 +412,8 @@ int build_big_plan(plo_plan *pl)
         std::vector<uint16_t> rt(PLO_RSTRIDE * PLO_RSTRIDE, 0), iv(rv.size());     // identifiers at [i * 32 + j]
         for (uint32_t i = 0; i < nv; ++i) for (uint32_t j = 0; j < nv; ++j) rt[i * PLO_RSTRIDE + j] = (uint16_t)(std::lower_bound(rv.begin(), rv.end(), rat[i * nv + j]) - rv.begin());
         for (size_t k = 0; k < rv.size(); ++k) iv[k] = (uint16_t)(std::lower_bound(rv.begin(), rv.end(), inv_mod(rv[k], p)) - rv.begin());   // the inverse of v_i/v_j is v_j/v_i: in the set
-        std::vector<uint8_t> ng(PLO_RSTRIDE, 0xFF);                                 // value index of -v
-        for (uint32_t i = 0; i < nv; ++i) { const auto it = std::lower_bound(dv.begin(), dv.end(), p - dv[i]); if (it != dv.end() && *it == p - dv[i]) ng[i] = (uint8_t)(it - dv.begin()); }
-        if ((rc = upload(pl, rv, &B.rval)) || (rc = upload(pl, rt, &B.rtid)) || (rc = upload(pl, iv, &B.invid)) || (rc = upload(pl, ng, &B.negidx))) return rc;
+        if ((rc = upload(pl, rv, &B.rval)) || (rc = upload(pl, rt, &B.rtid)) || (rc = upload(pl, iv, &B.invid))) return rc;
         B.nr = (uint32_t)rv.size(); B.mode = 2u;
-        B.id_one = (uint32_t)(std::lower_bound(rv.begin(), rv.end(), 1u) - rv.begin());
-        { const auto it = std::lower_bound(rv.begin(), rv.end(), p - 1u); B.id_mone = (it != rv.end() && *it == p - 1u) ? (uint32_t)(it - rv.begin()) : 0xFFFFu; }
     }
     B.invtab = nullptr;
     if (p <= (1u << 20)) {                                   // 1/x for every residue (the flush needs v_a/v_c from v_c/v_a): i^-1 = -(p/i) (p mod i)^-1
@@ -453,24 +449,10 @@ int build_big_plan(plo_plan *pl)
       if (bb + 2u * rb + cb <= 64u && !getenv("PLO_BIG_NODUAL")) { B.agg_dual = 1u; B.agg_cb = 64u - bb - 2u * rb; if (B.agg_cb > 16u) B.agg_cb = 16u; }
       else { B.agg_dual = 0u; B.agg_cb = 16u; } }
     // dynamic LDS, in words: histogram, tables of the mode, then max(ProgramGen scratch, aggregation table: 2^aggbits entries of 8 bytes, 6 in mode 2)
-    // Mode 2 with deferred updates (the flat sweep): beside the hashed aggregation table the scratch region holds a DIRECT count table
-    // indexed by column for the entries whose ratio is +-1 (84 % of config 5's), and the waves' queues of the other entries
-    // (plo_cse_big.hip, "direct counts"); the hashed table then has 2^12 slots at most.
-#ifdef PLO_BIG_DIRECT
-    const bool direct = B.mode == 2u && B.defer && !getenv("PLO_BIG_NODIRECT");
-#else
-    const bool direct = false;                               // (an experiment of round 4, kept behind -DPLO_BIG_DIRECT: DESIGN.md 2.2)
-#endif
-    if (direct && B.aggbits > 12u && !getenv("PLO_BIG_AGGBITS")) B.aggbits = 12u;
     const uint32_t agg_words = B.mode == 2u ? (1u << B.aggbits) + (1u << B.aggbits) / 2u : 2u << B.aggbits;
     uint32_t scr_words = std::max<uint32_t>((PLO_BIG_THREADS / 64) * maxlen, agg_words);
-    uint32_t tab_words = B.mode == 1u ? 2u * ((B.nv + 1u) & ~1u) : B.mode == 2u ? ((B.nr + 1u) & ~1u) + PLO_RSTRIDE * PLO_RSTRIDE / 2u + (B.nr + 3u) / 4u * 2u + PLO_RSTRIDE / 4u + (B.defer ? 0u : (1u << B.aggbits) / 2u) : 0u;   // mode 2: ratio values, ratio ids, inverse ids, negated value indices, slot list of the aggregation table (eager flush only)
+    uint32_t tab_words = B.mode == 1u ? 2u * ((B.nv + 1u) & ~1u) : B.mode == 2u ? ((B.nr + 1u) & ~1u) + PLO_RSTRIDE * PLO_RSTRIDE / 2u + (B.nr + 3u) / 4u * 2u + (B.defer ? 0u : (1u << B.aggbits) / 2u) : 0u;   // mode 2: ratio values, ratio ids, inverse ids, slot list of the aggregation table (eager flush only)
     if (B.defer) { tab_words += PLO_DBLOOM_WORDS; scr_words = std::max<uint32_t>(scr_words, PLO_DMREG_WORDS - PLO_DBLOOM_WORDS); }   // Bloom filter, and 64 KB in all for the merge
-    B.dcols = 0u;
-    if (direct && scr_words >= agg_words + PLO_BIG_QUEUE_WORDS + 1024u) {
-        B.dcols = std::min<uint32_t>(scr_words - agg_words - PLO_BIG_QUEUE_WORDS, 32768u);
-        if (const char *e = getenv("PLO_BIG_DCOLS")) B.dcols = (uint32_t)std::min<long>(B.dcols, std::max<long>(1, strtol(e, nullptr, 10)));   // test knob: columns beyond go through the queue
-    }
     pl->big_lds = (((B.maxf0 + 2u) & ~1u) + tab_words + scr_words) * 4u;
     if (pl->big_lds + sizeof(plo::BigShared) + 64 > g_lds_max) return fail(PLO_E_CAPACITY, "frequency histogram does not fit LDS");
     HIPCHK(hipFuncSetAttribute(big_kernel_fn(B), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->big_lds));
@@ -481,6 +463,20 @@ int build_big_plan(plo_plan *pl)
     B.selcap = PLO_BIG_SELCAP;
     if (const char *e = getenv("PLO_BIG_SELCAP")) B.selcap = (uint32_t)std::min<long>(PLO_BIG_SELCAP, std::max<long>(1, strtol(e, nullptr, 10)));   // test knob: forces the bisection tie pick
     pl->big = true; pl->waves_per_wg = PLO_BIG_THREADS / 64; pl->lds_bytes = pl->big_lds + (uint32_t)sizeof(plo::BigShared);
+    return PLO_OK;
+}
+
+// The event pair around one launch on g_stream: launch() enqueues the kernel, *ms gets its time
+template <class Launch> int timed(float *ms, Launch launch)
+{
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, g_stream));
+    launch();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, g_stream)); HIPCHK(hipEventSynchronize(e1));
+    HIPCHK(hipEventElapsedTime(ms, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return PLO_OK;
 }
 
@@ -508,10 +504,8 @@ int launch_big(plo_plan *pl, plo::BigJob J, plo_stats_t *st)
     HIPCHK(hipMemsetAsync(pl->d_next, 0, sizeof(unsigned long long), g_stream));
     HIPCHK(hipMemsetAsync(pl->d_stats, 0, 64 * sizeof(uint32_t), g_stream));
     J.err = pl->d_err; J.next = pl->d_next; J.stats = pl->d_stats;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, g_stream));
-    {
+    float ms = 0;
+    const int trc = timed(&ms, [&] {
         const plo::BigPlan &B = pl->B;
         if (B.defer) {
             if (B.idk) hipLaunchKernelGGL((plo::cse_big_kernel<2, true, true>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
@@ -524,12 +518,8 @@ int launch_big(plo_plan *pl, plo::BigJob J, plo_stats_t *st)
             else if (B.mode == 1u) hipLaunchKernelGGL((plo::cse_big_kernel<1, false>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
             else hipLaunchKernelGGL((plo::cse_big_kernel<0, false>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
         }
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, g_stream));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    });
+    if (trc != PLO_OK) return trc;
     uint32_t err = 0;
     HIPCHK(hipMemcpy(&err, pl->d_err, sizeof err, hipMemcpyDeviceToHost));
     if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = pl->lds_bytes; st->waves_per_wg = pl->waves_per_wg; st->algo_bytes = pl->algo_bytes; }
@@ -600,16 +590,12 @@ int launch(plo_plan *pl, plo::WaveJob J, plo_stats_t *st, float *ms_out)
     if (grid == 0) grid = 1;
     HIPCHK(hipMemsetAsync(pl->d_err, 0, sizeof(uint32_t), g_stream));
     J.err = pl->d_err;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, g_stream));
-    if (pl->P.unit) hipLaunchKernelGGL(plo::cse_wave_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), pl->lds_bytes, g_stream, pl->P, J);
-    else hipLaunchKernelGGL(plo::cse_wave_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), pl->lds_bytes, g_stream, pl->P, J);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, g_stream));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    float ms = 0;
+    const int trc = timed(&ms, [&] {
+        if (pl->P.unit) hipLaunchKernelGGL(plo::cse_wave_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), pl->lds_bytes, g_stream, pl->P, J);
+        else hipLaunchKernelGGL(plo::cse_wave_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), pl->lds_bytes, g_stream, pl->P, J);
+    });
+    if (trc != PLO_OK) return trc;
     uint32_t err = 0;
     HIPCHK(hipMemcpy(&err, pl->d_err, sizeof err, hipMemcpyDeviceToHost));
     if (ms_out) *ms_out = ms;
@@ -690,15 +676,9 @@ int run_chain(plo_chain *ch, plo::WaveJob J, plo_stats_t *st)
         const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * ch->blocks_per_cu, need));
         HIPCHK(hipMemsetAsync(p0->d_err, 0, sizeof(uint32_t), g_stream));
         J.err = p0->d_err;
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, g_stream));
-        hipLaunchKernelGGL(plo::cse_chain_kernel, dim3((uint32_t)grid), dim3(ch->W * 64), ch->lds, g_stream, ch->st[0]->P, ch->st[1]->P, J);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e1, g_stream));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        float ms = 0;
+        const int trc = timed(&ms, [&] { hipLaunchKernelGGL(plo::cse_chain_kernel, dim3((uint32_t)grid), dim3(ch->W * 64), ch->lds, g_stream, ch->st[0]->P, ch->st[1]->P, J); });
+        if (trc != PLO_OK) return trc;
         uint32_t err = 0;
         HIPCHK(hipMemcpy(&err, p0->d_err, sizeof err, hipMemcpyDeviceToHost));
         if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = ch->lds; st->waves_per_wg = ch->W;
@@ -1166,6 +1146,48 @@ int multi_min(const std::vector<MultiShard> &sh, int ndev, const int *devices, p
             agg.reduce = 0; break;
         }
     } else if (mode) return fail(PLO_E_HIP, std::string("PLO_MULTI_REDUCE=rccl: ") + why);
+    return PLO_OK;
+}
+
+// A restart search sharded over devices, for the searches that prepare a plan: every shard creates its plan, searches its block of
+// seeds and destroys the plan; the winner is the minimum of the shards' bests under key(best), the search's own total order as a
+// (hi, lo) word pair.  (A launch takes at most 2^31-1 candidates: longer shards go in pieces, minimum under the same order.)
+template <class Plan, class Best, class Create, class Key>
+int sharded_search(uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, Best *best, plo_stats_t *stats, Create create,
+                   int (*search)(Plan *, uint64_t, uint64_t, Best *, plo_stats_t *), void (*destroy)(Plan *), Key key)
+{
+    if (ndev < 1 || ndev > 64) return fail(PLO_E_ARG, "device count outside [1,64]");
+    if (nseeds == 0 || nseeds >= (1ull << 62)) return fail(PLO_E_ARG, "1 .. 2^62-1 candidates per call");
+    DeviceGuard guard;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<MultiShard> sh; std::vector<Best> bests((size_t)ndev);
+    int rc = multi_run(ndev, devices, seed0, nseeds, sh, [&](MultiShard &S, int) {
+        Best &b = bests[(size_t)(&S - sh.data())];
+        Plan *plan = nullptr;
+        int r_ = create(&plan);
+        if (r_ != PLO_OK) return r_;
+        bool have = false;
+        for (uint64_t done = 0; r_ == PLO_OK && done < S.cnt;) {
+            const uint64_t piece = std::min<uint64_t>(S.cnt - done, (1ull << 31) - 1ull);
+            Best pb{}; plo_stats_t ps{};
+            r_ = search(plan, S.s0 + done, piece, &pb, &ps);
+            if (r_ != PLO_OK) break;
+            S.st.candidates += ps.candidates; S.st.launches += ps.launches; S.st.kernel_ms += ps.kernel_ms; S.st.grid = ps.grid; S.st.lds_bytes = ps.lds_bytes; S.st.waves_per_wg = ps.waves_per_wg; S.st.algo_bytes = ps.algo_bytes;
+            const unsigned long long hi = key(pb).first, lo = key(pb).second;
+            if (!have || hi < S.hi || (hi == S.hi && lo < S.lo)) { S.hi = hi; S.lo = lo; b = pb; have = true; }
+            done += piece;
+        }
+        destroy(plan);
+        return r_;
+    });
+    if (rc != PLO_OK) return rc;
+    plo_stats_t agg{}; int win = -1;
+    rc = multi_min(sh, ndev, devices, agg, win);
+    if (rc != PLO_OK) return rc;
+    if (win < 0) return fail(PLO_E_INTERNAL, "no candidate reported");
+    *best = bests[(size_t)win];
+    agg.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = agg;
     return PLO_OK;
 }
 } // namespace
@@ -1789,28 +1811,56 @@ struct plo_tril_plan {
 };
 
 namespace {
-int tril_launch(plo_tril_plan *pl, plo::TrilJob J, plo_stats_t *st) {
+// One timed launch of a search kernel (trilplacer, inplacer, orbiter) and its statistics
+template <class Plan, class Launch> int timed_launch(Plan *pl, uint64_t grid, uint64_t ncand, plo_stats_t *st, Launch launch) {
+    float ms = 0;
+    const int rc = timed(&ms, launch);
+    if (rc != PLO_OK) return rc;
+    if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = pl->lds_bytes; st->waves_per_wg = pl->waves_per_wg; st->algo_bytes = pl->algo_bytes; st->candidates += ncand; }
+    return PLO_OK;
+}
+
+// Launch of a trilplacer or inplacer job (one wavefront per candidate, plo::TrilJob): `kernel` is the plan's instantiation, `tool` names it in the error text
+template <class Plan, class Kernel> int atoms_launch(Plan *pl, Kernel kernel, const char *tool, plo::TrilJob J, plo_stats_t *st) {
     HIPCHK(hipMemsetAsync(pl->d_err, 0, sizeof(uint32_t), g_stream));
     J.err = pl->d_err;
     const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
     const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * pl->blocks_per_cu, need));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, g_stream));
-    if (pl->rational) hipLaunchKernelGGL((plo::tril_kernel<true>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
-    else hipLaunchKernelGGL((plo::tril_kernel<false>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, g_stream)); HIPCHK(hipEventSynchronize(e1));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    const int rc = timed_launch(pl, grid, J.ncand, st, [&] { hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J); });
+    if (rc != PLO_OK) return rc;
     uint32_t err = 0;
     HIPCHK(hipMemcpy(&err, pl->d_err, sizeof err, hipMemcpyDeviceToHost));
-    if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = pl->lds_bytes; st->waves_per_wg = pl->waves_per_wg; st->algo_bytes = pl->algo_bytes; st->candidates += J.ncand; }
+    if (err) return fail(err == plo::TERR_CAP ? PLO_E_INTERNAL : PLO_E_UNSUPPORTED, std::string("device (") + tool + "): error " + std::to_string(err));
+    return PLO_OK;
+}
+
+// Body of a plo_*_cost_many entry of these searches: `width` words per candidate come back in `out`; launch(d_out, d_seeds, st) fills in
+// the job and launches it
+template <class Launch> int cost_many_run(const void *pl, const uint64_t *seeds, uint64_t n, uint32_t width, uint32_t *out, plo_stats_t *stats, Launch launch) {
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!pl || !out) return fail(PLO_E_ARG, "null argument");
+    if (n >= (1ull << 31)) return fail(PLO_E_ARG, "at most 2^31-1 candidates per call");
+    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0) return PLO_OK;
+    uint32_t *d_out = nullptr; uint64_t *d_seeds = nullptr;
+    HIPCHK(hipMalloc((void **)&d_out, n * width * sizeof(uint32_t)));
+    if (seeds && (hipMalloc((void **)&d_seeds, n * 8) != hipSuccess || hipMemcpy(d_seeds, seeds, n * 8, hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipFree(d_out); if (d_seeds) (void)hipFree(d_seeds); return fail(PLO_E_HIP, "seed upload");
+    }
+    int rc = launch(d_out, d_seeds, st);
+    if (rc == PLO_OK && hipMemcpy(out, d_out, n * width * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back");
+    (void)hipFree(d_out); if (d_seeds) (void)hipFree(d_seeds);
+    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int tril_launch(plo_tril_plan *pl, plo::TrilJob J, plo_stats_t *st) {
+    const int rc = atoms_launch(pl, pl->rational ? plo::tril_kernel<true> : plo::tril_kernel<false>, "trilplacer", J, st);
 #ifdef PLO_TRIL_PROFILE
     { unsigned long long gp[8] = {0}; if (hipMemcpyFromSymbol(gp, HIP_SYMBOL(plo::g_tprof), sizeof gp) == hipSuccess && gp[5]) fprintf(stderr, "# tril profile (wave 0 of every workgroup, %llu candidates): cycles per candidate: perm %.0f build %.0f pushvariables %.0f simplify %.0f; fixpoint trips %.1f\n", gp[5], (double)gp[0] / gp[5], (double)gp[1] / gp[5], (double)gp[2] / gp[5], (double)gp[3] / gp[5], (double)gp[4] / gp[5]); }
 #endif
-    if (err) return fail(err == plo::TERR_CAP ? PLO_E_INTERNAL : PLO_E_UNSUPPORTED, "device (trilplacer): error " + std::to_string(err));
-    return PLO_OK;
+    return rc;
 }
 } // namespace
 
@@ -1917,20 +1967,10 @@ void plo_tril_plan_destroy(plo_tril_plan_t *pl)
 
 int plo_tril_cost_many(plo_tril_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats)
 {
-    if (!pl || !ops6) return fail(PLO_E_ARG, "null argument");
-    if (n >= (1ull << 31)) return fail(PLO_E_ARG, "at most 2^31-1 candidates per call");
-    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
-    if (n == 0) return PLO_OK;
-    uint32_t *d_ops = nullptr; uint64_t *d_seeds = nullptr;
-    HIPCHK(hipMalloc((void **)&d_ops, n * 6 * sizeof(uint32_t)));
-    if (seeds) { HIPCHK(hipMalloc((void **)&d_seeds, n * 8)); HIPCHK(hipMemcpy(d_seeds, seeds, n * 8, hipMemcpyHostToDevice)); }
-    plo::TrilJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.ops = d_ops; J.best = nullptr;
-    int rc = tril_launch(pl, J, st);
-    if (rc == PLO_OK && hipMemcpy(ops6, d_ops, n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back");
-    (void)hipFree(d_ops); if (d_seeds) (void)hipFree(d_seeds);
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    return cost_many_run(pl, seeds, n, 6, ops6, stats, [&](uint32_t *d_ops, const uint64_t *d_seeds, plo_stats_t *st) {
+        plo::TrilJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.ops = d_ops; J.best = nullptr;
+        return tril_launch(pl, J, st);
+    });
 }
 
 int plo_tril_search(plo_tril_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_tril_best_t *best, plo_stats_t *stats)
@@ -1986,40 +2026,9 @@ int plo_tril_search_multi(const plo_qcsr_t *A, const plo_qcsr_t *B, const plo_qc
                           int ndev, const int *devices, plo_tril_best_t *best, plo_stats_t *stats)
 {
     if (!A || !B || !T || !best) return fail(PLO_E_ARG, "null argument");
-    if (ndev < 1 || ndev > 64) return fail(PLO_E_ARG, "device count outside [1,64]");
-    if (nseeds == 0 || nseeds >= (1ull << 62)) return fail(PLO_E_ARG, "1 .. 2^62-1 candidates per call");
-    DeviceGuard guard;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<MultiShard> sh; std::vector<plo_tril_best_t> bests((size_t)ndev);
-    int rc = multi_run(ndev, devices, seed0, nseeds, sh, [&](MultiShard &S, int) {
-        plo_tril_best_t &b = bests[(size_t)(&S - sh.data())];
-        plo_tril_plan_t *plan = nullptr;
-        int r_ = plo_tril_plan_create_q(A, B, T, expanded, &plan);
-        if (r_ != PLO_OK) return r_;
-        // (a launch takes at most 2^31-1 candidates: longer shards go in pieces, minimum under the same order)
-        bool have = false;
-        for (uint64_t done = 0; r_ == PLO_OK && done < S.cnt;) {
-            const uint64_t piece = std::min<uint64_t>(S.cnt - done, (1ull << 31) - 1ull);
-            plo_tril_best_t pb{}; plo_stats_t ps{};
-            r_ = plo_tril_search(plan, S.s0 + done, piece, &pb, &ps);
-            if (r_ != PLO_OK) break;
-            S.st.candidates += ps.candidates; S.st.launches += ps.launches; S.st.kernel_ms += ps.kernel_ms; S.st.grid = ps.grid; S.st.lds_bytes = ps.lds_bytes; S.st.waves_per_wg = ps.waves_per_wg; S.st.algo_bytes = ps.algo_bytes;
-            const unsigned long long hi = ((unsigned long long)pb.add << 32) | pb.sca, lo = ((pb.seed - seed0) << 1) | (pb.variant & 1u);      // the order of include/plinopt_inplace.inl:893-897, then (seed, variant)
-            if (!have || hi < S.hi || (hi == S.hi && lo < S.lo)) { S.hi = hi; S.lo = lo; b = pb; have = true; }
-            done += piece;
-        }
-        plo_tril_plan_destroy(plan);
-        return r_;
-    });
-    if (rc != PLO_OK) return rc;
-    plo_stats_t agg{}; int win = -1;
-    rc = multi_min(sh, ndev, devices, agg, win);
-    if (rc != PLO_OK) return rc;
-    if (win < 0) return fail(PLO_E_INTERNAL, "no candidate reported");
-    *best = bests[(size_t)win];
-    agg.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (stats) *stats = agg;
-    return PLO_OK;
+    return sharded_search(seed0, nseeds, ndev, devices, best, stats,
+        [&](plo_tril_plan_t **plan) { return plo_tril_plan_create_q(A, B, T, expanded, plan); }, plo_tril_search, plo_tril_plan_destroy,
+        [&](const plo_tril_best_t &pb) { return std::make_pair(((unsigned long long)pb.add << 32) | pb.sca, ((pb.seed - seed0) << 1) | (pb.variant & 1u)); });      // the order of include/plinopt_inplace.inl:893-897, then (seed, variant)
 }
 
 } // extern "C"
@@ -2035,24 +2044,7 @@ struct plo_lin_plan {
 
 namespace {
 int lin_launch(plo_lin_plan *pl, plo::TrilJob J, plo_stats_t *st) {
-    HIPCHK(hipMemsetAsync(pl->d_err, 0, sizeof(uint32_t), g_stream));
-    J.err = pl->d_err;
-    const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
-    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * pl->blocks_per_cu, need));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, g_stream));
-    if (pl->rational) hipLaunchKernelGGL((plo::lin_kernel<true>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
-    else hipLaunchKernelGGL((plo::lin_kernel<false>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, g_stream)); HIPCHK(hipEventSynchronize(e1));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    uint32_t err = 0;
-    HIPCHK(hipMemcpy(&err, pl->d_err, sizeof err, hipMemcpyDeviceToHost));
-    if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = pl->lds_bytes; st->waves_per_wg = pl->waves_per_wg; st->algo_bytes = pl->algo_bytes; st->candidates += J.ncand; }
-    if (err) return fail(err == plo::TERR_CAP ? PLO_E_INTERNAL : PLO_E_UNSUPPORTED, "device (inplacer): error " + std::to_string(err));
-    return PLO_OK;
+    return atoms_launch(pl, pl->rational ? plo::lin_kernel<true> : plo::lin_kernel<false>, "inplacer", J, st);
 }
 } // namespace
 
@@ -2131,23 +2123,10 @@ void plo_lin_plan_destroy(plo_lin_plan_t *pl)
 
 int plo_lin_cost_many(plo_lin_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats)
 {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
-    if (!pl || !ops6) return fail(PLO_E_ARG, "null argument");
-    if (n >= (1ull << 31)) return fail(PLO_E_ARG, "at most 2^31-1 candidates per call");
-    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
-    if (n == 0) return PLO_OK;
-    uint32_t *d_ops = nullptr; uint64_t *d_seeds = nullptr;
-    HIPCHK(hipMalloc((void **)&d_ops, n * 6 * sizeof(uint32_t)));
-    if (seeds && (hipMalloc((void **)&d_seeds, n * 8) != hipSuccess || hipMemcpy(d_seeds, seeds, n * 8, hipMemcpyHostToDevice) != hipSuccess)) {
-        (void)hipFree(d_ops); if (d_seeds) (void)hipFree(d_seeds); return fail(PLO_E_HIP, "seed upload");
-    }
-    plo::TrilJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.ops = d_ops; J.best = nullptr;
-    int rc = lin_launch(pl, J, st);
-    if (rc == PLO_OK && hipMemcpy(ops6, d_ops, n * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back");
-    (void)hipFree(d_ops); if (d_seeds) (void)hipFree(d_seeds);
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    return cost_many_run(pl, seeds, n, 6, ops6, stats, [&](uint32_t *d_ops, const uint64_t *d_seeds, plo_stats_t *st) {
+        plo::TrilJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.ops = d_ops; J.best = nullptr;
+        return lin_launch(pl, J, st);
+    });
 }
 
 int plo_lin_search(plo_lin_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_lin_best_t *best, plo_stats_t *stats)
@@ -2175,40 +2154,9 @@ int plo_lin_search(plo_lin_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_lin_
 int plo_lin_search_multi(const plo_qcsr_t *A, uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_lin_best_t *best, plo_stats_t *stats)
 {
     if (!A || !best) return fail(PLO_E_ARG, "null argument");
-    if (ndev < 1 || ndev > 64) return fail(PLO_E_ARG, "device count outside [1,64]");
-    if (nseeds == 0 || nseeds >= (1ull << 62)) return fail(PLO_E_ARG, "1 .. 2^62-1 candidates per call");
-    DeviceGuard guard;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<MultiShard> sh; std::vector<plo_lin_best_t> bests((size_t)ndev);
-    int rc = multi_run(ndev, devices, seed0, nseeds, sh, [&](MultiShard &S, int) {
-        plo_lin_best_t &b = bests[(size_t)(&S - sh.data())];
-        plo_lin_plan_t *plan = nullptr;
-        int r_ = plo_lin_plan_create_q(A, &plan);
-        if (r_ != PLO_OK) return r_;
-        // (a launch takes at most 2^31-1 candidates: longer shards go in pieces, minimum under the same order)
-        bool have = false;
-        for (uint64_t done = 0; r_ == PLO_OK && done < S.cnt;) {
-            const uint64_t piece = std::min<uint64_t>(S.cnt - done, (1ull << 31) - 1ull);
-            plo_lin_best_t pb{}; plo_stats_t ps{};
-            r_ = plo_lin_search(plan, S.s0 + done, piece, &pb, &ps);
-            if (r_ != PLO_OK) break;
-            S.st.candidates += ps.candidates; S.st.launches += ps.launches; S.st.kernel_ms += ps.kernel_ms; S.st.grid = ps.grid; S.st.lds_bytes = ps.lds_bytes; S.st.waves_per_wg = ps.waves_per_wg; S.st.algo_bytes = ps.algo_bytes;
-            const unsigned long long hi = ((unsigned long long)pb.add << 32) | pb.sca, lo = ((pb.seed - seed0) << 1) | (pb.variant & 1u);      // (ADD, SCA) of :637-641, then (seed, variant)
-            if (!have || hi < S.hi || (hi == S.hi && lo < S.lo)) { S.hi = hi; S.lo = lo; b = pb; have = true; }
-            done += piece;
-        }
-        plo_lin_plan_destroy(plan);
-        return r_;
-    });
-    if (rc != PLO_OK) return rc;
-    plo_stats_t agg{}; int win = -1;
-    rc = multi_min(sh, ndev, devices, agg, win);
-    if (rc != PLO_OK) return rc;
-    if (win < 0) return fail(PLO_E_INTERNAL, "no candidate reported");
-    *best = bests[(size_t)win];
-    agg.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (stats) *stats = agg;
-    return PLO_OK;
+    return sharded_search(seed0, nseeds, ndev, devices, best, stats,
+        [&](plo_lin_plan_t **plan) { return plo_lin_plan_create_q(A, plan); }, plo_lin_search, plo_lin_plan_destroy,
+        [&](const plo_lin_best_t &pb) { return std::make_pair(((unsigned long long)pb.add << 32) | pb.sca, ((pb.seed - seed0) << 1) | (pb.variant & 1u)); });      // (ADD, SCA) of :637-641, then (seed, variant)
 }
 
 } // extern "C"
@@ -2250,17 +2198,10 @@ int64_t gcd64(int64_t a, int64_t b) { if (a < 0) a = -a; if (b < 0) b = -b; whil
 int orbit_launch(plo_orbit_plan *pl, plo::OrbitJob J, plo_stats_t *st) {
     const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
     const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(pl->grid_max, need));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, g_stream));
-    if (pl->P.p) hipLaunchKernelGGL((plo::orbit_kernel<true>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
-    else hipLaunchKernelGGL((plo::orbit_kernel<false>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, g_stream)); HIPCHK(hipEventSynchronize(e1));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = pl->lds_bytes; st->waves_per_wg = pl->waves_per_wg; st->algo_bytes = pl->algo_bytes; st->candidates += J.ncand; }
-    return PLO_OK;
+    return timed_launch(pl, grid, J.ncand, st, [&] {
+        if (pl->P.p) hipLaunchKernelGGL((plo::orbit_kernel<true>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+        else hipLaunchKernelGGL((plo::orbit_kernel<false>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+    });
 }
 } // namespace
 
@@ -2367,23 +2308,10 @@ void plo_orbit_plan_destroy(plo_orbit_plan_t *pl)
 
 int plo_orbit_cost_many(plo_orbit_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *out3, plo_stats_t *stats)
 {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
-    if (!pl || !out3) return fail(PLO_E_ARG, "null argument");
-    if (n >= (1ull << 31)) return fail(PLO_E_ARG, "at most 2^31-1 candidates per call");
-    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
-    if (n == 0) return PLO_OK;
-    uint32_t *d_out = nullptr; uint64_t *d_seeds = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, n * 3 * sizeof(uint32_t)));
-    if (seeds && (hipMalloc((void **)&d_seeds, n * 8) != hipSuccess || hipMemcpy(d_seeds, seeds, n * 8, hipMemcpyHostToDevice) != hipSuccess)) {
-        (void)hipFree(d_out); if (d_seeds) (void)hipFree(d_seeds); return fail(PLO_E_HIP, "seed upload");
-    }
-    plo::OrbitJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.out3 = d_out; J.best = nullptr;
-    int rc = orbit_launch(pl, J, st);
-    if (rc == PLO_OK && hipMemcpy(out3, d_out, n * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back");
-    (void)hipFree(d_out); if (d_seeds) (void)hipFree(d_seeds);
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    return cost_many_run(pl, seeds, n, 3, out3, stats, [&](uint32_t *d_out, const uint64_t *d_seeds, plo_stats_t *st) {
+        plo::OrbitJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.out3 = d_out; J.best = nullptr;
+        return orbit_launch(pl, J, st);
+    });
 }
 
 int plo_orbit_search(plo_orbit_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_orbit_best_t *best, plo_stats_t *stats)
@@ -2413,40 +2341,9 @@ int plo_orbit_search_multi(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_q
                            uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats)
 {
     if (!L || !R || !P || !best) return fail(PLO_E_ARG, "null argument");
-    if (ndev < 1 || ndev > 64) return fail(PLO_E_ARG, "device count outside [1,64]");
-    if (nseeds == 0 || nseeds >= (1ull << 62)) return fail(PLO_E_ARG, "1 .. 2^62-1 candidates per call");
-    DeviceGuard guard;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<MultiShard> sh; std::vector<plo_orbit_best_t> bests((size_t)ndev);
-    int rc = multi_run(ndev, devices, seed0, nseeds, sh, [&](MultiShard &S, int) {
-        plo_orbit_best_t &b = bests[(size_t)(&S - sh.data())];
-        plo_orbit_plan_t *plan = nullptr;
-        int r_ = plo_orbit_plan_create_q(L, R, P, modulus, measure, &plan);
-        if (r_ != PLO_OK) return r_;
-        // (a launch takes at most 2^31-1 candidates: longer shards go in pieces, minimum under the same order)
-        bool have = false;
-        for (uint64_t done = 0; r_ == PLO_OK && done < S.cnt;) {
-            const uint64_t piece = std::min<uint64_t>(S.cnt - done, (1ull << 31) - 1ull);
-            plo_orbit_best_t pb{}; plo_stats_t ps{};
-            r_ = plo_orbit_search(plan, S.s0 + done, piece, &pb, &ps);
-            if (r_ != PLO_OK) break;
-            S.st.candidates += ps.candidates; S.st.launches += ps.launches; S.st.kernel_ms += ps.kernel_ms; S.st.grid = ps.grid; S.st.lds_bytes = ps.lds_bytes; S.st.waves_per_wg = ps.waves_per_wg; S.st.algo_bytes = ps.algo_bytes;
-            const unsigned long long hi = ((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, lo = pb.seed - seed0;   // (cost, nnz, nno), then seed
-            if (!have || hi < S.hi || (hi == S.hi && lo < S.lo)) { S.hi = hi; S.lo = lo; b = pb; have = true; }
-            done += piece;
-        }
-        plo_orbit_plan_destroy(plan);
-        return r_;
-    });
-    if (rc != PLO_OK) return rc;
-    plo_stats_t agg{}; int win = -1;
-    rc = multi_min(sh, ndev, devices, agg, win);
-    if (rc != PLO_OK) return rc;
-    if (win < 0) return fail(PLO_E_INTERNAL, "no candidate reported");
-    *best = bests[(size_t)win];
-    agg.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (stats) *stats = agg;
-    return PLO_OK;
+    return sharded_search(seed0, nseeds, ndev, devices, best, stats,
+        [&](plo_orbit_plan_t **plan) { return plo_orbit_plan_create_q(L, R, P, modulus, measure, plan); }, plo_orbit_search, plo_orbit_plan_destroy,
+        [&](const plo_orbit_best_t &pb) { return std::make_pair(((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, pb.seed - seed0); });   // (cost, nnz, nno), then seed
 }
 
 } // extern "C"

@@ -91,10 +91,6 @@ struct BigPlan {
     const uint64_t *st0; const uint32_t *pcount0;     // store image: 2^pbits partitions of capp entries (key48<<16 | count16), entries per partition
     uint64_t o_store, o_pcount, o_ptail, o_log, o_plog, o_hot;
     uint32_t kb, idk;                     // idk: the ratio field of a pair key holds the ratio's identifier (kb bits), not the residue (cse_big_kernel<2, ., true>)
-    // -DPLO_BIG_DIRECT (an experiment of round 4) -- mode 2 with deferred updates: columns of the DIRECT count table of the flat
-    // sweep (0: none), identifiers of the ratios 1 and -1 (0xFFFF: -1 is no ratio of the matrix), value index of -v for every value index (0xFF: none)
-    uint32_t dcols, id_one, id_mone;
-    const uint8_t *negidx;
 };
 
 struct BigJob {
@@ -110,13 +106,8 @@ enum { BERR_TABLE = 11, BERR_FREQ = 12, BERR_COLS = 13, BERR_DM = 14, BERR_HL = 
 // gfx950 agent-scope atomics and sc1 loads are performed at the memory side of the fabric (the 8 XCDs' L2s are not
 // coherent with each other) -- measured: 1.8e7 DRAM atomics per candidate before this change -- while workgroup scope
 // lets the XCD's L2 do them.  Only the work counter, the error word and the best word are shared between workgroups.
-#ifdef PLO_BIG_AGENT_SCOPE
-#define PLO_BIG_SCOPE __HIP_MEMORY_SCOPE_AGENT
-#define PLO_BIG_FENCE() __threadfence()
-#else
 #define PLO_BIG_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
 #define PLO_BIG_FENCE() __threadfence_block()
-#endif
 template <class T> __device__ __forceinline__ T wg_add(T *p, T v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, PLO_BIG_SCOPE); }
 template <class T> __device__ __forceinline__ T wg_sub(T *p, T v) { return __hip_atomic_fetch_add(p, (T)(0 - v), __ATOMIC_RELAXED, PLO_BIG_SCOPE); }
 template <class T> __device__ __forceinline__ T wg_or(T *p, T v) { return __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, PLO_BIG_SCOPE); }
@@ -370,23 +361,9 @@ __device__ __forceinline__ bool agg_add(uint64_t *agg, uint32_t aggbits, uint32_
 // Mode 2 (at most 32 distinct values, hence at most 1024 distinct ratios v_i/v_j): an aggregation entry is
 // (column << 10 | ratio identifier) in a u32 key array and a u16 count array -- 6 bytes per entry instead of 8, 32-bit
 // LDS operations, and no modular product in the sweep (the identifier comes from a 2-byte table lookup).
-#ifdef PLO_BIG_DIRECT
-#define PLO_DIRECT_ONLY(x_) x_
-#else
-#define PLO_DIRECT_ONLY(x_)
-#endif
-#define PLO_BIG_QUEUE 128u                  // entries of a wave's queue of the flat sweep ("direct counts")
-#define PLO_BIG_QUEUE_WORDS (PLO_BIG_QUEUE * (PLO_BIG_THREADS / 64u))
-#ifndef PLO_BIG_DIRECT_MIN
-#define PLO_BIG_DIRECT_MIN 128u            // steps of fewer rows use the hashed table only (their flush does not scan the direct table)
-#endif
 #define PLO_RIDB 10u
 #define PLO_RSTRIDE 32u                    // row stride of the ratio-identifier table (at most 32 values): an index is a shift and an or
-#ifdef PLO_BIG_DIRECT
-struct BigTabs { const uint2 *vts; const uint16_t *rtid; const uint32_t *rval; const uint16_t *invid; uint16_t *list; uint32_t *bloom; const uint8_t *negidx; };
-#else
 struct BigTabs { const uint2 *vts; const uint16_t *rtid; const uint32_t *rval; const uint16_t *invid; uint16_t *list; uint32_t *bloom; };
-#endif   // bloom: DEFER, followed by the scratch region   // list: mode 2, one u16 per aggregation slot
 __device__ __forceinline__ bool agg_add_rid(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, uint32_t *aggn, uint16_t *agglist, uint32_t listcap) {
     const uint32_t mask = (1u << aggbits) - 1u;
     uint32_t s = (key * 0x9E3779B1u) >> (32u - aggbits);
@@ -441,29 +418,10 @@ __device__ __forceinline__ bool agg_add_rid_bm(uint32_t *aggk, uint32_t *aggc32,
     return false;
 }
 
-// First round of the same probe, written without a loop (round 4).  One trip of the flat sweep finds 64 keys; 99.8 % of them are in
-// their home pair or claim a slot of it, so the common case is ONE pair read and at most three predicated LDS operations: the add on
-// a hit, the compare-and-swap of an empty slot, the bitmap bit of a fresh claim.  The probe loop above -- breaks, a `continue` after a
-// lost claim, a result flag -- compiled to ~60 scalar and ~70 vector instructions of exec-mask bookkeeping per trip, which is what the
-// sweep was bound by (4 waves per SIMD issue one instruction per cycle group each: 108 VALU + 100 SALU per trip).  Returns true when
-// the key is NOT settled (both slots hold other keys, or the claim lost to another key): the caller sends those lanes, ~0.2 % of them,
-// through the loop.
-__device__ __forceinline__ bool agg_add_rid_first(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, uint32_t *bm) {
-    const uint32_t s = ((uint32_t)__umul24(key, 0x9E3779u) >> (32u - aggbits)) & ~1u;
-    const unsigned long long kk = __hip_atomic_load((unsigned long long *)(aggk + s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    const uint32_t k0 = (uint32_t)kk, k1 = (uint32_t)(kk >> 32);
-    const bool hit0 = k0 == key, hit = hit0 || k1 == key, emp0 = k0 == 0xFFFFFFFFu, tryc = !hit && (emp0 || k1 == 0xFFFFFFFFu);
-    const uint32_t sec = hit ? (hit0 ? 0u : 1u) : (emp0 ? 0u : 1u), t = s + sec;
-    uint32_t old = 0u;
-    if (tryc) old = wg_cas(&aggk[t], 0xFFFFFFFFu, key);
-    const bool fresh = tryc && old == 0xFFFFFFFFu, ok = hit || fresh || (tryc && old == key);      // (old == key: a lane with the same key claimed the slot first)
-    if (fresh) wg_or(&bm[t >> 5], 1u << (t & 31u));
-    if (ok) wg_add(&aggc32[s >> 1], sec ? 0x10000u : 1u);
-    return !ok;
-}
-
 #ifdef PLO_BIG_PROFILE
-// the same with a clock after every LDS round trip (profile build): acc[0] pair read, [1] compare-and-swap, [2] bitmap + count
+// First round of the same probe, written without a loop, with a clock after every LDS round trip (profile build): acc[0] pair read,
+// [1] compare-and-swap, [2] bitmap + count.  Returns true when the key is NOT settled (both slots hold other keys, or the claim lost
+// to another key): the caller sends those lanes, ~0.2 % of them, through the loop.
 __device__ __forceinline__ bool agg_add_rid_first_prof(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, uint32_t *bm, unsigned long long *acc) {
     const unsigned long long c0 = clock64();
     const uint32_t s = ((uint32_t)__umul24(key, 0x9E3779u) >> (32u - aggbits)) & ~1u;
@@ -498,9 +456,6 @@ __device__ __forceinline__ int row_find(const uint32_t *ent, uint32_t base, uint
 struct BigShared {
     uint32_t M, theta, ncols, nbadd, nbmul, nmult, naff, dmcount, hlcount, rng, errflag, sel_n, sel_over, invr, fullscans, rebuilds, steps, hlbad, acc0, acc1;
     uint32_t a, b, r, aggn, nspill, keepn; uint64_t kprime; uint64_t selkey;
-#ifdef PLO_BIG_DIRECT
-    uint32_t dn;                   // words of the direct count table the step's sweep has touched (listed for the flush)
-#endif
     uint32_t nbisect, spilltot, listover, nwin, nsearched;   // nwin: windows of the flat sweep beyond the first of a batch of rows (thread 0's wave); nsearched: rows walked by the row search   // diagnostics: tie picks by bisection, entries through the spill list, sweeps whose slot list overflowed
     uint32_t logn, hotn, hotbits, nforced, hotops, logtot_lo, logtot_hi;   // DEFER: log fill, claimed hot slots, hot table size; diagnostics: merges forced by log/hot pressure, updates served by the hot table, log entries written
     uint32_t derr; unsigned long long tmg[4], tmb[4]; uint32_t ngrp; uint32_t outcnt[64];           // DEFER merge: live entries written back per partition of the current group
@@ -516,11 +471,6 @@ struct BigShared {
 };
 
 #define BSYNC() __syncthreads()
-#ifdef PLO_BIG_NOFENCE
-#define PLO_SCHED_FENCE() do { } while (0)
-#else
-#define PLO_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)      /* the machine scheduler keeps the stages of the hand-ordered trip apart */
-#endif
 #ifdef PLO_BIG_PROFILE
 #define PLO_STAMP(q_) do { if (threadIdx.x == 0) { unsigned long long t_ = wall_clock64(); sh.tph[q_] += t_ - tstamp; sh.tpc[sh.M >= 256u ? 0 : sh.M >= 64u ? 1 : sh.M >= 16u ? 2 : 3][q_] += t_ - tstamp; tstamp = t_; } } while (0)
 #else
@@ -861,11 +811,6 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
     auto VT = [&](uint32_t vi) -> uint2 { if constexpr (MODE == 1) return vts[vi]; else return vtg[vi]; };
     const uint16_t *rtid = TB.rtid, *invid = TB.invid; const uint32_t *rval = TB.rval;   // mode 2
     uint32_t *aggk = (uint32_t *)agg, *aggc32 = aggk + (1u << aggbits); uint16_t *aggc16 = (uint16_t *)aggc32;      // mode 2: key array, count array
-    // Direct counts (round 4, mode 2 with deferred updates): behind the hashed table, one word per column c < P.dcols -- low half: entries
-    // of ratio 1 met by the running sweep, high half: ratio -1 -- and a queue of PLO_BIG_QUEUE words per wave (see the flat sweep)
-#ifdef PLO_BIG_DIRECT
-    uint32_t *dcnt = aggc32 + (1u << aggbits) / 2u, *wqueue = dcnt + P.dcols;
-#endif
     uint32_t *aff   = (uint32_t *)(ws + P.o_aff), *ncrptr = (uint32_t *)(ws + P.o_ncrptr), *ncr = (uint32_t *)(ws + P.o_ncr);
     // slots claimed in the aggregation table by the running sweep (the flush walks this list, not the table): mode 2 has room
     // for every slot; the other modes keep a short list in the tie-selection buffer, idle during the sweeps, and walk the
@@ -921,9 +866,6 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
     const uint32_t acb = P.agg_cb; const uint64_t AEMPTY = ~0ull << acb;
     if constexpr (MODE == 2) { for (uint32_t s = tid; s < (1u << aggbits); s += nth) { aggk[s] = 0xFFFFFFFFu; aggc16[s] = 0; } }
     else for (uint32_t s = tid; s < (1u << aggbits); s += nth) agg[s] = AEMPTY;
-#ifdef PLO_BIG_DIRECT
-    if constexpr (MODE == 2 && DEFER) for (uint32_t s = tid; s < P.dcols; s += nth) dcnt[s] = 0u;
-#endif
     if (tid == 0) {
         uint64_t x = seed + 0x9E3779B97F4A7C15ull;
         x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; x ^= x >> 31;
@@ -964,9 +906,6 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                 if (!dfirst) {                                                // the merge worked in the scratch region: the aggregation table is empty again
                     if constexpr (MODE == 2) { for (uint32_t s = tid; s < (1u << aggbits); s += nth) { aggk[s] = 0xFFFFFFFFu; aggc16[s] = 0; } }
                     else for (uint32_t s = tid; s < (1u << aggbits); s += nth) agg[s] = AEMPTY;
-#ifdef PLO_BIG_DIRECT
-                    if constexpr (MODE == 2 && DEFER) for (uint32_t s = tid; s < P.dcols; s += nth) dcnt[s] = 0u;
-#endif
                     BSYNC();
                 }
                 dfirst = false; need_rebuild = true; hbits = sh.hotbits;
@@ -1131,7 +1070,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
         // ---- RemOneCSE :60-194
         const bool swap = gload32(&ucount[a]) < gload32(&ucount[b]);      // :70-88
         const uint32_t l0 = swap ? b : a, l1 = swap ? a : b;
-        if (tid == 0) { sh.naff = 0; sh.aggn = 0; sh.nspill = 0; sh.keepn = 0; PLO_DIRECT_ONLY(sh.dn = 0;) }      // (nothing here uses `swap`: the two counts stay in flight while the row lists are walked)
+        if (tid == 0) { sh.naff = 0; sh.aggn = 0; sh.nspill = 0; sh.keepn = 0; }      // (nothing here uses `swap`: the two counts stay in flight while the row lists are walked)
         if constexpr (FAST) { for (uint32_t w = tid; w < ((1u << aggbits) + 31u) / 32u; w += nth) aggbm[w] = 0u; }      // (the tie pick used the buffer)
         BSYNC();
 #define RL(v_, k_) ((uint32_t)__builtin_amdgcn_readlane((int)(v_), (int)(k_)))
@@ -1161,14 +1100,10 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
 #endif
                 if constexpr (MODE == 2) {
                     // 16-byte record (value indices have 5 bits): positions, row start, length (<= 8192: 14 bits) | value index and +-1 flag of
-                    // the a and b entries, row -- 32 bytes in round 2: 48 MB less written and read per candidate on config 5
-                    // (bits 26-31: the value index of -v_a and "there is one" -- the direct counts of the flat sweep)
-#ifdef PLO_BIG_DIRECT
-                    const uint32_t nva = TB.negidx[PLO_EVI(ea)];
-#else
-                    const uint32_t nva = 0xFFu;
-#endif
-                    *(uint4 *)(aff + 4u * idx) = make_uint4(pa | (pb << 16), base, L | (PLO_EUNIT(ea) << 14) | (PLO_EVI(ea) << 15) | (PLO_EUNIT(eb) << 20) | (PLO_EVI(eb) << 21) | ((nva & 31u) << 26) | (nva != 0xFFu ? 0x80000000u : 0u), i);
+                    // the a and b entries, row -- 32 bytes in round 2: 48 MB less written and read per candidate on config 5.  Bits 26-30 are set and
+                    // bit 31 is clear, always: no reader looks at them (each masks its field).  They stay because without them cse_big_kernel<2, false, true>
+                    // spills two more scalar registers (the register allocation here is on a knife edge)
+                    *(uint4 *)(aff + 4u * idx) = make_uint4(pa | (pb << 16), base, L | (PLO_EUNIT(ea) << 14) | (PLO_EVI(ea) << 15) | (PLO_EUNIT(eb) << 20) | (PLO_EVI(eb) << 21) | 0x7C000000u, i);
                 } else {
                 uint32_t *rec = aff + 8u * idx;                             // record: row, positions (16 bits each), row start and length; the two packed entries
                 *(uint4 *)rec = make_uint4(i, pa | (pb << 16), base, L);
@@ -1184,50 +1119,10 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
             };
             // a searched row stays in the walked list iff it still holds the list's column and does not lose it in this step; the kept
             // rows go to a scratch list and are copied to the front of the walked one behind the barrier below (no order is needed)
-#ifdef PLO_BIG_NOCOMPACT
-            auto keep_row = [&](uint32_t, bool, bool) { };                      // (A/B switch: the lists keep their stale rows, as in rounds 1-3)
-#else
             auto keep_row = [&](uint32_t i, bool has_col, bool affected) { if (has_col && !affected) keep[wg_add(&sh.keepn, 1u)] = i; };
-#endif
 #ifdef PLO_BIG_PROFILE
             if (tid == 0) { sh.tb2[0] += 100ull * ln; sh.tb2[2] += 100ull * (na <= nb ? nb : na); }
 #endif
-#ifdef PLO_BIG_QUATSEARCH
-            // (round 4 experiment, measured SLOWER: row search 91 -> 141 ms per candidate at full load, 49 -> 66 ms alone -- the phase is bound by the number of
-            // scattered 4-byte requests a CU can issue, not by the number of dependent rounds: 6 loads x 4 rounds cost more than 2 x 7.)
-            // One row per thread, both columns searched in lock step by QUATERNARY search: three probes per search and round, all
-            // six loads in flight together, a quarter of the range left -- 3 dependent memory round trips for a row of 64 entries
-            // (5 for 1024) where the binary search of rounds 1-3 needed 7 (11).  The phase is latency-bound (a step's rows are
-            // searched once, by idle threads mostly), so the extra requests are free.  A search keeps the entry it saw at its
-            // upper bound: when it ends that is the entry at the found position.
-            for (uint32_t k = tid; k < ln; k += nth) {
-                const uint32_t i0 = lst[k];
-                const uint32_t bs0 = P.rs[i0], L0 = len[i0];
-                uint32_t lo[2] = {0u, 0u}, hi[2] = {L0, L0}, ev[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
-                for (;;) {
-                    uint32_t v[2][3], pq[2][3]; bool any = false;
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        const uint32_t w = hi[q] - lo[q]; const bool go = w != 0u; any |= go;
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) { pq[q][j] = lo[q] + (((uint32_t)(j + 1) * w) >> 2); v[q][j] = go ? ent[bs0 + pq[q][j]] : 0u; }
-                    }
-                    if (!any) break;
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) if (hi[q] != lo[q]) {
-                        const uint32_t c = q ? b : a;
-                        if (PLO_ECOL(v[q][0]) >= c) { hi[q] = pq[q][0]; ev[q] = v[q][0]; }
-                        else if (PLO_ECOL(v[q][1]) >= c) { lo[q] = pq[q][0] + 1u; hi[q] = pq[q][1]; ev[q] = v[q][1]; }
-                        else if (PLO_ECOL(v[q][2]) >= c) { lo[q] = pq[q][1] + 1u; hi[q] = pq[q][2]; ev[q] = v[q][2]; }
-                        else lo[q] = pq[q][2] + 1u;
-                    }
-                }
-                // (an upper bound that never moved is the row length: ev stays all ones, whose column field matches no column)
-                {   const bool fa = PLO_ECOL(ev[0]) == a && lo[0] < L0, fb = PLO_ECOL(ev[1]) == b && lo[1] < L0;
-                    const bool aff0 = fa && fb && emit(i0, bs0, L0, lo[0], lo[1], ev[0], ev[1]);
-                    keep_row(i0, walk_a ? fa : fb, aff0); }
-            }
-#else
             for (uint32_t k = tid; k < ln; k += 2u * nth) {
                 const bool two = k + nth < ln;
                 const uint32_t i0 = lst[k], i1 = two ? lst[k + nth] : i0;
@@ -1253,11 +1148,9 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                     const bool aff1 = fa && fb && emit(i1, bs1, L1, lo[2], lo[3], ev[2], ev[3]);
                     keep_row(i1, walk_a ? fa : fb, aff1); }
             }
-#endif
         }
         PLO_BIG_FENCE(); BSYNC();
         const uint32_t naff = sh.naff;
-#ifndef PLO_BIG_NOCOMPACT
         {   // the walked list, compacted (it is read next in a later step, many barriers from here)
             const uint32_t nk = sh.keepn, lc = gload32(&clen[a]) <= gload32(&clen[b]) ? a : b;
             uint32_t *dst = lc < n ? tl + P.tptr[lc] : ncr + ncrptr[lc - n];
@@ -1265,7 +1158,6 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
             BSYNC();                                                           // (every thread has read both lengths)
             if (tid == 0) clen[lc] = nk;
         }
-#endif
         PLO_STAMP(2);
         if (naff != M) { if (tid == 0) wg_max(&sh.errflag, (uint32_t)BERR_FREQ); BSYNC(); break; }   // frequency must equal the row count
         // The sweep over the affected rows: rewrite each row (:96-110) and retire its old pairs (:115-118) in one pass over
@@ -1296,16 +1188,8 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                         if (!__builtin_amdgcn_ballot_w64(pend)) return;
                         if (!pend || agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm, &probe_iters)) return;
                     }
-#elif !defined(PLO_BIG_FIRSTPROBE)
-                    if constexpr (FAST) { if (!noagg) { if (agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm)) return; } }
 #else
-                    if constexpr (FAST) {
-                        if (!noagg) {
-                        const bool pend = agg_add_rid_first(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm);
-                        if (!__builtin_amdgcn_ballot_w64(pend)) return;                  // (wave-uniform: nine trips in ten end here)
-                        if (!pend || agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm)) return;
-                        }
-                    }
+                    if constexpr (FAST) { if (!noagg) { if (agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm)) return; } }
 #endif
                     else if (agg_add_rid(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, &sh.aggn, agglist, listcap)) return;
                     const uint32_t bc = rval[rtid[vib * PLO_RSTRIDE + vi]];                                  // v_b / v_c
@@ -1372,7 +1256,6 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
 #ifdef PLO_BIG_PROFILE
             unsigned long long pw0 = 0, pw1 = 0, pw2 = 0, ptr = 0, pit = 0, pact = 0, tl_ = clock64(); const unsigned long long ts_ = tl_;
 #endif
-#ifndef PLO_BIG_ROWSWEEP
             if constexpr (FAST) {
             // Flat sweep (round 3): the entries of the wave's next 64 rows form ONE sequence and every trip takes its next 64
             // entries, whatever rows they belong to -- lanes are full (two rows per trip, a 64-lane chunk each: 53 % on config 5),
@@ -1384,30 +1267,6 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
             // earlier), so no load sees a store.
             uint64_t *fm = sh.sel + 256u + 32u * wave;                  // (the bitmap of claimed slots takes at most the first 2 KB)
             const uint32_t dump = P.nnz + 64u + lane;                   // (the entry array has 128 spare words)
-            // Direct counts (round 4).  On config 5 84 % of the entries carry +-7710: four of five swept entries have ratio 1 or -1 to
-            // their row's v_a, and every trip paid the ratio lookup, the pair read and (96 % of the trips: some lane claims) the
-            // compare-and-swap for all 64 lanes.  Now an entry of ratio +-1 in a column below P.dcols is ONE fire-and-forget add to the
-            // column's word of a direct table (no lookup: v == v_a, or v == -v_a with the index of -v_a carried by the row record);
-            // the other entries are appended to the wave's queue (column, value indices: 30 bits) and go through the hashed table 64 at
-            // a time, full lanes.  The flush reads both tables.  Steps of fewer than PLO_BIG_DIRECT_MIN rows keep to the hashed table
-            // (their flush does not scan the direct one).
-#ifdef PLO_BIG_DIRECT
-            const bool use_direct = P.dcols != 0u && naff >= PLO_BIG_DIRECT_MIN;
-            uint32_t *wq = wqueue + wave * PLO_BIG_QUEUE; uint32_t qn = 0;
-            auto drain = [&](uint32_t cntq) {                           // the first min(cntq, 64) queued entries: hashed table (or its fall-back)
-                __atomic_signal_fence(__ATOMIC_SEQ_CST); __builtin_amdgcn_wave_barrier();
-                const bool on = lane < cntq;
-                const uint32_t raw = on ? __hip_atomic_load(&wq[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0u;
-                if (on) retire_entry((raw & 0x7FFFu) | (((raw >> 15) & 31u) << 16), (raw >> 20) & 31u, (raw >> 25) & 31u, make_uint2(0, 0), make_uint2(0, 0));
-                if (cntq > 64u) {
-                    const bool mv = lane + 64u < cntq;
-                    const uint32_t x_ = mv ? __hip_atomic_load(&wq[lane + 64u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0u;
-                    __atomic_signal_fence(__ATOMIC_SEQ_CST); __builtin_amdgcn_wave_barrier();
-                    if (mv) __hip_atomic_store(&wq[lane], x_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                __atomic_signal_fence(__ATOMIC_SEQ_CST); __builtin_amdgcn_wave_barrier();
-            };
-#endif
             const uint32_t selsh = l0 == a ? 14u : 20u;                 // the new column's entry carries the +-1 flag and the value index of the l0 entry
             for (uint32_t k0 = 0; k0 < nrw; k0 += 64u) {
                 const bool have = k0 + lane < nrw;
@@ -1442,74 +1301,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                         z_ = f_ - S_; ad_ = rb_ + z_;
                         e_ = ent[ok && f_ < T ? ad_ : safe];
                     };
-#if defined(PLO_BIG_PIPETRIP) && !defined(PLO_BIG_PROFILE)
-                    // Round 4: the trip as ONE hand-ordered instruction stream.  Measured with a clock behind every LDS round trip (profile
-                    // build, profiles/r04_sweep_trip_clocks.txt): per trip the wave waited in turn for the record permutes of the next trip
-                    // (~130 cycles), the ratio-identifier lookup (73), the pair read (126) and the compare-and-swap of the few claiming
-                    // lanes (240) -- a chain of ~570 cycles of LDS latency in a trip of ~1,700, with 2 to 4 waves per SIMD to hide it.
-                    // Here (1) the lookup of THIS trip's identifiers is issued first, (2) the next trip's four permutes behind it, (3) the
-                    // pair read as soon as the identifier is back, (4) the next trip's entry request, (5) this trip's stores -- so the
-                    // three latencies overlap -- and (6) a claim is OPTIMISTIC: the compare-and-swap is issued, the bitmap bit and the count
-                    // are added at once, and its returned word is looked at one trip later; a claim that lost its slot to another key (0.2 %
-                    // of the lanes) takes its count back and goes through the probe loop then.  Counts are read by the flush, behind the
-                    // barrier that ends the sweep, so a count that sits on a wrong slot for one trip is seen by nobody.
-                    uint32_t adc, zc, ppc, rzc, ec; prep(0u, adc, zc, ppc, rzc, ec);
-                    __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0): see PLAINTRIP below
-                    uint32_t dk = 0xFFFFFFFFu, dold = 0u, de = 0u, drz = 0u;          // the claim of the trip before: key | second slot << 31, returned word, entry, record bits
-                    auto settle = [&]() {
-                        const bool lost = dk != 0xFFFFFFFFu && dold != 0xFFFFFFFFu && dold != (dk & 0x7FFFFFFFu);
-                        if (__builtin_amdgcn_ballot_w64(lost)) {
-                            if (lost) {
-                                const uint32_t key = dk & 0x7FFFFFFFu, s = ((uint32_t)__umul24(key, 0x9E3779u) >> (32u - aggbits)) & ~1u;
-                                wg_sub(&aggc32[s >> 1], (dk >> 31) ? 0x10000u : 1u);
-                                if (!agg_add_rid_bm(aggk, aggc32, aggbits, key, aggbm)) retire_entry(de, (drz >> 15) & 31u, (drz >> 21) & 31u, make_uint2(0, 0), make_uint2(0, 0), true);
-                            }
-                        }
-                        dk = 0xFFFFFFFFu;
-                    };
-                    for (uint32_t t = 0; t < ntw; ++t) {
-                        // (1) this trip's ratio identifiers (idle lanes look up a valid entry too: no branch around the read)
-                        const uint32_t cE = PLO_ECOL(ec), viE = PLO_EVI(ec) & 31u, viaE = (rzc >> 15) & 31u;
-                        const uint32_t xidE = rtid[cE < a ? (viaE * PLO_RSTRIDE) | viE : (viE * PLO_RSTRIDE) | viaE];
-                        PLO_SCHED_FENCE();
-                        // (2) the next trip's row records
-                        const uint32_t t_ = t + 1u; const bool okn = t_ < ntw;
-                        const uint32_t ml = okn ? RL(mrl, t_ & 31u) : 0u, mh = okn ? RL(mrh, t_ & 31u) : 0u;
-                        const uint32_t m1l = (ml >> 1) | (mh << 31), m1h = mh >> 1;
-                        const int qa = (int)((qlo + (ml & 1u) + __builtin_amdgcn_mbcnt_hi(m1h, __builtin_amdgcn_mbcnt_lo(m1l, 0u))) << 2);
-                        qlo += (uint32_t)__builtin_popcount(ml) + (uint32_t)__builtin_popcount(mh);
-                        const uint32_t rbn = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)R0.y), Sn = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)S);
-                        const uint32_t ppn = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)R0.x), rzn = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)R0.z);
-                        PLO_SCHED_FENCE();
-                        // (3) this trip's pair of aggregation slots
-                        const uint32_t keyE = (cE << PLO_RIDB) | xidE, sE = ((uint32_t)__umul24(keyE, 0x9E3779u) >> (32u - aggbits)) & ~1u;
-                        const unsigned long long kk = __hip_atomic_load((unsigned long long *)(aggk + sE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        PLO_SCHED_FENCE();
-                        // (4) the next trip's entry
-                        const uint32_t fn = w0 + (t_ << 6) + lane, zn = fn - Sn, adn = rbn + zn;
-                        const uint32_t en = ent[okn && fn < T ? adn : safe];
-                        PLO_SCHED_FENCE();
-                        // (5) this trip's row rewrite (:96-110), stores unconditional (idle lanes write their dump word)
-                        const uint32_t pa = ppc & 0xFFFFu, pb = ppc >> 16;
-                        const bool in = w0 + (t << 6) + lane < T, act = in && zc != pa && zc != pb;
-                        ent[act && zc > pa ? adc - 1u - (zc > pb ? 1u : 0u) : dump] = ec;
-                        ent[in && zc + 1u == (rzc & 0x3FFFu) ? adc - 1u : dump] = (((rzc >> selsh) & 63u) << 15) | lm;
-                        PLO_SCHED_FENCE();
-                        // (6) the claims of the trip before, then this trip's keys
-                        settle();
-                        const uint32_t k0 = (uint32_t)kk, k1 = (uint32_t)(kk >> 32);
-                        const bool hit0 = k0 == keyE, hit = hit0 || k1 == keyE, emp0 = k0 == 0xFFFFFFFFu;
-                        const bool tryc = act && !hit && (emp0 || k1 == 0xFFFFFFFFu), full = act && !hit && !tryc;
-                        const uint32_t sec = hit ? (hit0 ? 0u : 1u) : (emp0 ? 0u : 1u), tE = sE + sec;
-                        if (tryc) { dold = wg_cas(&aggk[tE], 0xFFFFFFFFu, keyE); wg_or(&aggbm[tE >> 5], 1u << (tE & 31u)); dk = keyE | (sec << 31); de = ec; drz = rzc; }
-                        if (act && !full) wg_add(&aggc32[sE >> 1], sec ? 0x10000u : 1u);
-                        if (__builtin_amdgcn_ballot_w64(full)) {              // both slots hold other keys: the probe loop (one trip in ten)
-                            if (full) { if (!agg_add_rid_bm(aggk, aggc32, aggbits, keyE, aggbm)) retire_entry(ec, viaE, (rzc >> 21) & 31u, make_uint2(0, 0), make_uint2(0, 0), true); }
-                        }
-                        adc = adn; zc = zn; ppc = ppn; rzc = rzn; ec = en;
-                    }
-                    settle();
-#elif !defined(PLO_BIG_PREFETCH1) && !defined(PLO_BIG_PROFILE)
+#if !defined(PLO_BIG_PROFILE)
                     // Round 4 (default): entries are requested TWO trips ahead and the loop is unrolled three times, so that the three sets
                     // of trip registers (address, position in the row, the row's record words, the entry) rotate by NAME.  The one-ahead loop
                     // below ends in `ec = en`: a copy of the entry requested at the top of the same trip, i.e. a wait for that load at the
@@ -1524,22 +1316,6 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                         // (the two UNCONDITIONAL stores: see the one-ahead loop below)
                         ent[act && zc > pa ? adc - 1u - (zc > pb ? 1u : 0u) : dump] = ec;
                         ent[in && zc + 1u == (rzc & 0x3FFFu) ? adc - 1u : dump] = (((rzc >> selsh) & 63u) << 15) | lm;
-#ifdef PLO_BIG_DIRECT
-                        if (use_direct) {
-                            const uint32_t cE = PLO_ECOL(ec), viE = PLO_EVI(ec) & 31u, viaE = (rzc >> 15) & 31u;
-                            const bool one = viE == viaE, mone = (rzc >> 31) != 0u && viE == ((rzc >> 26) & 31u);
-                            const bool dir = act && cE < P.dcols && (one || mone);
-                            if (dir) wg_add(&dcnt[cE], one ? 1u : 0x10000u);
-                            const bool qd = act && !dir;
-                            const uint64_t qm = __builtin_amdgcn_ballot_w64(qd);
-                            if (qm) {
-                                const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(qm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)qm, 0u));
-                                if (qd) __hip_atomic_store(&wq[qn + rk], cE | (viE << 15) | (viaE << 20) | (((rzc >> 21) & 31u) << 25), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                qn += (uint32_t)__builtin_popcountll(qm);
-                                if (qn >= 64u) { drain(qn); qn -= 64u; }
-                            }
-                        } else
-#endif
                         if (act) retire_entry(ec, (rzc >> 15) & 31u, (rzc >> 21) & 31u, make_uint2(0, 0), make_uint2(0, 0));
                     };
                     uint32_t a0_, z0_, p0_, r0_, e0_, a1_, z1_, p1_, r1_, e1_, a2_, z2_, p2_, r2_, e2_;
@@ -1571,22 +1347,6 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
 #ifdef PLO_BIG_PROFILE
                         __builtin_amdgcn_wave_barrier(); const unsigned long long t1_ = clock64(); probe_iters = 0;
 #endif
-#if defined(PLO_BIG_DIRECT) && !defined(PLO_BIG_PROFILE)
-                        if (use_direct) {
-                            const uint32_t cE = PLO_ECOL(ec), viE = PLO_EVI(ec) & 31u, viaE = (rzc >> 15) & 31u;
-                            const bool one = viE == viaE, mone = (rzc >> 31) != 0u && viE == ((rzc >> 26) & 31u);
-                            const bool dir = act && cE < P.dcols && (one || mone);
-                            if (dir) wg_add(&dcnt[cE], one ? 1u : 0x10000u);
-                            const bool qd = act && !dir;
-                            const uint64_t qm = __builtin_amdgcn_ballot_w64(qd);
-                            if (qm) {
-                                const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(qm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)qm, 0u));
-                                if (qd) __hip_atomic_store(&wq[qn + rk], cE | (viE << 15) | (viaE << 20) | (((rzc >> 21) & 31u) << 25), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                qn += (uint32_t)__builtin_popcountll(qm);          // (below 64 before: never beyond the queue's 128 words)
-                                if (qn >= 64u) { drain(qn); qn -= 64u; }
-                            }
-                        } else
-#endif
                         if (act) retire_entry(ec, (rzc >> 15) & 31u, (rzc >> 21) & 31u, make_uint2(0, 0), make_uint2(0, 0));
 #ifdef PLO_BIG_PROFILE
                         {   __builtin_amdgcn_wave_barrier(); const unsigned long long t2_ = clock64(); pw0 += t1_ - t0_; pw1 += t2_ - t1_; pw2 += t0_ - tl_; tl_ = t2_; ++ptr;
@@ -1598,11 +1358,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
 #endif
                 }
             }
-#ifdef PLO_BIG_DIRECT
-            if (qn) drain(qn);                                          // what the wave's queue still holds
-#endif
             } else
-#endif
             for (uint32_t k0 = 0; k0 < nrw; k0 += 64u) {
                 // two rows per trip; the first chunks of the next pair are requested before the current pair is worked on
                 const bool have = k0 + lane < nrw;
@@ -1700,74 +1456,25 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                 else { gstore64(&tab[sl], v - (uint64_t)M); retired(key, M, M); }
             }
             const uint32_t nent = sh.aggn, nslot = FAST ? (1u << aggbits) / 16u : nent <= listcap ? nent : (1u << aggbits);     // few entries: walk the slot list, not the table (FAST: the bitmap, 16 slots per thread and round)
-            // FAST: behind the bitmap words of the hashed table, the words of the direct table (columns below the new one) when the step's sweep used it
-            // (its non-zero words are first listed -- a light pass, 16-bit column numbers in the waves' queue space, idle by now -- so that the
-            // rounds below are as many as the touched columns need, not as many as the table has; a list that overflows: the whole table)
-#ifdef PLO_BIG_DIRECT
-            uint32_t ndir = 0; bool dlisted = false;
-            uint16_t *dlist = (uint16_t *)wqueue;
-            if constexpr (FAST) {
-                if (P.dcols != 0u && naff >= PLO_BIG_DIRECT_MIN) {
-                    const uint32_t nd0 = lm < P.dcols ? lm : P.dcols;
-                    for (uint32_t w0 = 0; w0 < nd0; w0 += nth) {
-                        const uint32_t w = w0 + tid;
-                        const bool nz = w < nd0 && dcnt[w] != 0u;
-                        const uint64_t bm_ = __builtin_amdgcn_ballot_w64(nz);
-                        if (bm_) {
-                            uint32_t base_ = 0;
-                            if (lane == 0) base_ = wg_add(&sh.dn, (uint32_t)__builtin_popcountll(bm_));
-                            base_ = (uint32_t)__builtin_amdgcn_readfirstlane((int)base_);
-                            const uint32_t ix = base_ + __builtin_amdgcn_mbcnt_hi((uint32_t)(bm_ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm_, 0u));
-                            if (nz && ix < 2u * PLO_BIG_QUEUE_WORDS) dlist[ix] = (uint16_t)w;
-                        }
-                    }
-                    BSYNC();
-                    const uint32_t dn = sh.dn;
-                    dlisted = dn <= 2u * PLO_BIG_QUEUE_WORDS;
-                    ndir = dlisted ? dn : nd0;
-                }
-            }
-#endif
             uint32_t nhot = 0;
-#ifndef PLO_BIG_DIRECT
-            const uint32_t ndir = 0;
-#endif
-            for (uint32_t s0 = 0; s0 < nslot + ndir; s0 += nth) {
+            for (uint32_t s0 = 0; s0 < nslot; s0 += nth) {
               const uint32_t e_ = s0 + tid;
-              uint32_t bits_ = 0; PLO_DIRECT_ONLY(uint32_t dw_ = 0; uint32_t dcol_ = 0; const bool isdir = e_ >= nslot;)
+              uint32_t bits_ = 0;
               if constexpr (FAST) {
                   if (e_ < nslot) bits_ = (aggbm[e_ >> 1] >> ((e_ & 1u) << 4)) & 0xFFFFu;
-#ifdef PLO_BIG_DIRECT
-                  else if (e_ - nslot < ndir) { dcol_ = dlisted ? (uint32_t)dlist[e_ - nslot] : e_ - nslot; dw_ = dcnt[dcol_]; if (dw_) dcnt[dcol_] = 0u; bits_ = ((dw_ & 0xFFFFu) ? 1u : 0u) | ((dw_ >> 16) ? 2u : 0u); }
-#endif
               }
               for (bool more_ = true; more_;) {
                 bool valid; uint32_t s;
-#ifdef PLO_BIG_DIRECT
-                if constexpr (FAST) { valid = bits_ != 0u; s = valid ? (isdir ? (uint32_t)__builtin_ctz(bits_) : e_ * 16u + (uint32_t)__builtin_ctz(bits_)) : 0u; bits_ &= bits_ - 1u; }
-#else
                 if constexpr (FAST) { valid = bits_ != 0u; s = valid ? e_ * 16u + (uint32_t)__builtin_ctz(bits_) : 0u; bits_ &= bits_ - 1u; }
-#endif
                 else { valid = e_ < nslot; s = valid ? (nent <= listcap ? (uint32_t)agglist[e_] : e_) : 0u; }
                 uint32_t c = 0, x = 0, y = 0, d = 0;
                 if constexpr (MODE == 2) {
-#ifdef PLO_BIG_DIRECT
-                    if (FAST && isdir) {
-                        if (valid) {
-                            const uint32_t xid = s ? P.id_mone : P.id_one;
-                            d = s ? dw_ >> 16 : dw_ & 0xFFFFu; c = dcol_;
-                            x = rval[xid]; y = rval[c > a ? (uint32_t)invid[xid] : xid];
-                        }
-                    } else
-#endif
-                    {
                     const uint32_t kq = valid ? aggk[s] : 0xFFFFFFFFu;
                     valid = kq != 0xFFFFFFFFu;
                     if (valid) {
                         d = aggc16[s]; aggk[s] = 0xFFFFFFFFu; aggc16[s] = 0; c = kq >> PLO_RIDB;
                         const uint32_t xid = kq & ((1u << PLO_RIDB) - 1u);
                         x = rval[xid]; y = rval[c > a ? (uint32_t)invid[xid] : xid];
-                    }
                     }
                 } else {
                     const uint64_t v = valid ? agg[s] : AEMPTY;
@@ -2315,11 +2022,7 @@ template <int MODE, bool DEFER, bool IDK = false> __global__ __launch_bounds__(P
     __shared__ unsigned long long cur;
     uint32_t *hist = bigdyn;
     uint32_t *nextw = bigdyn + ((P.maxf0 + 2u) & ~1u);
-#ifdef PLO_BIG_DIRECT
-    BigTabs TB{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-#else
     BigTabs TB{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-#endif
     if constexpr (MODE == 1) {                                     // {value, inverse} per value index
         uint2 *vts = (uint2 *)nextw; nextw += 2u * ((P.nv + 1u) & ~1u);
         for (uint32_t k = threadIdx.x; k < P.nv; k += blockDim.x) vts[k] = P.vt[k];
@@ -2332,11 +2035,6 @@ template <int MODE, bool DEFER, bool IDK = false> __global__ __launch_bounds__(P
         for (uint32_t k = threadIdx.x; k < P.nr; k += blockDim.x) { rv[k] = P.rval[k]; iv[k] = P.invid[k]; }
         for (uint32_t k = threadIdx.x; k < PLO_RSTRIDE * PLO_RSTRIDE; k += blockDim.x) rt[k] = P.rtid[k];
         TB.rval = rv; TB.rtid = rt; TB.invid = iv;
-#ifdef PLO_BIG_DIRECT
-        uint8_t *ng = (uint8_t *)nextw; nextw += PLO_RSTRIDE / 4u;
-        if (threadIdx.x < PLO_RSTRIDE) ng[threadIdx.x] = P.negidx[threadIdx.x];
-        TB.negidx = ng;
-#endif
         if constexpr (!DEFER) { TB.list = (uint16_t *)nextw; nextw += (1u << P.aggbits) / 2u; }
     }
     if constexpr (DEFER) { TB.bloom = nextw; nextw += PLO_DBLOOM_WORDS; }           // Bloom filter of the hot triples; with the scratch region behind it: the merge's 64 KB
