@@ -532,6 +532,8 @@ int launch_big(plo_plan *pl, plo::BigJob J, plo_stats_t *st)
             fprintf(stderr, "# big kernel (last candidate): steps %u, full scans %u, level rebuilds %u; phase us: level %u select %u rows %u sweep1 %u flush1 %u sweep2 %u flush2 %u tail %u\n",
                     hs[0], hs[1], hs[2], hs[4], hs[5], hs[6], hs[7], hs[8], hs[9], hs[10], hs[11]);
             fprintf(stderr, "# big kernel (last candidate): image load + CSE phase %u us, ProgramGen %u us\n", hs[55], hs[56]);
+            fprintf(stderr, "# big kernel (last candidate): image load alone %u us; ProgramGen us: table fill + flags %u, expand + A1 %u, A2 %u, A3 + B + count %u, Triangle set-up %u, Triangle %u, D %u\n",
+                    hs[12], hs[57], hs[58], hs[59], hs[60], hs[61], hs[62], hs[63]);
 #ifdef PLO_BIG_PROFILE
             { unsigned long long g2[40] = {0}; if (hipMemcpyFromSymbol(g2, HIP_SYMBOL(plo::g_prof2), sizeof g2) == hipSuccess && g2[32]) {
                 static const char *cls[4] = {">=256", "64..255", "16..63", "<16"};

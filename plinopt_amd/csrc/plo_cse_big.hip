@@ -461,6 +461,7 @@ struct BigShared {
     uint32_t derr; unsigned long long tmg[4], tmb[4]; uint32_t ngrp; uint32_t outcnt[64];           // DEFER merge: live entries written back per partition of the current group
     uint32_t cblk[512];            // level-M triple counts per block of 64 first columns (NCmax <= 32768)
     unsigned long long tph[8];     // phase clocks (100 MHz ticks): level, select, rows, sweep1, flush1, sweep2, flush2, tail
+    unsigned long long tpg[7], tld; // ProgramGen: table fill + flags, expand + A1, A2, A3 + B + count, Triangle set-up, Triangle, D; tld: the image load
 #ifdef PLO_BIG_PROFILE
     unsigned long long tb1[4], tb2[4]; uint32_t nb[4], fb1, fb2, fl1, fl2;   // sweep clocks by step size class, fallbacks, flushed keys
     unsigned long long tpc[4][8];  // phase clocks by step size class
@@ -833,6 +834,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
 #define BKEY(a_, b_, r_) (((uint64_t)(a_) << abits) | ((uint64_t)(b_) << kb) | (uint64_t)key_ratio(r_))
 
     // ---- load the candidate image
+    const unsigned long long tld0 = wall_clock64();
     {   // 16-byte copies, 4 in flight per thread (all buffers are 256-byte aligned, sizes padded by the host)
         const uint4 *s4 = (const uint4 *)P.tab0; uint4 *d4 = (uint4 *)tab;
         const uint64_t n4 = DEFER ? 0ull : cap >> 1;                                                // (DEFER: the store image is copied partition by partition below)
@@ -879,6 +881,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
         sh.logn = 0; sh.hotn = 0; sh.hotbits = P.hotbits_min; sh.derr = 0; for (int q = 0; q < 4; ++q) { sh.tmg[q] = 0; sh.tmb[q] = 0; } sh.ngrp = 0; sh.nforced = 0; sh.hotops = 0; sh.logtot_lo = 0; sh.logtot_hi = 0;
     }
     PLO_BIG_FENCE(); BSYNC();
+    if (tid == 0) sh.tld = wall_clock64() - tld0;
     bool dfirst = true;                                                       // DEFER: the first merge only chooses the window
 
     bool need_rebuild = true;
@@ -1735,14 +1738,20 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
 #define PLO_TRI_R 4u               /* Triangle: registers per lane holding the rows of a column (64 rows each) */
 #endif
 #define PLO_PGFLAG 0x8000u
+// wall-clock stamps of ProgramGen's passes (thread 0, 100 MHz ticks; printed with PLO_BIG_STATS)
+#define PLO_PGSTAMP(q_) do { if (tid == 0) { const unsigned long long t_ = wall_clock64(); sh.tpg[q_] = t_ - tpg0; tpg0 = t_; } } while (0)
 #define PLO_PGCNT 0x7FFFu
 #define PLO_BFRESH 0xFFFFFFFFu
 
 // ProgramGen at scale, counts only (reference :513-611; counting rules derived in
-// plo_cse_wave.hip).  Workgroup-parallel for the factoring passes and the output
-// count; the Triangle pass walks, with one wave, only the columns that still hold
-// two or more non +-1 entries (after FactorOutColumns those have pairwise distinct
-// |values|, so they are few and short).
+// plo_cse_wave.hip).  Rows are short by now (config 5: 2.8 entries on average), so every
+// pass that treats a row on its own takes ONE ROW PER THREAD, and passes over the same
+// data are fused: expand + A1; A3 + FactorOutRows + Triangle's count per column (rows of
+// more than 64 entries go to whole waves: FactorOutRows is quadratic in the row); the
+// Triangle columns are compacted in order by a workgroup prefix sum.  The Triangle pass
+// walks, with one wave, only the columns that still hold two or more non +-1 entries
+// (after FactorOutColumns those have pairwise distinct |values|, so they are few and
+// short).  DESIGN.md 2.2 has the stamps of every pass before and after.
 __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *ws, BigShared &sh, uint32_t *scratch, uint32_t *errw)
 {
     // (the {value, inverse} table is read from global memory here: `scratch` may overlap its LDS copy)
@@ -1755,7 +1764,8 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
     const uint32_t p = P.p, rb = P.rb, m = P.m, ncols0 = sh.ncols, mers = P.mers;
     const uint64_t mu = P.mu;
 
-    if (tid == 0) { sh.acc0 = 0; sh.acc1 = 0; sh.errflag = 0; }
+    unsigned long long tpg0 = wall_clock64();
+    if (tid == 0) { sh.acc0 = 0; sh.acc1 = 0; sh.errflag = 0; sh.naff = 0; for (int q = 0; q < 7; ++q) sh.tpg[q] = 0; }
     BSYNC();
     if (P.unit) {                                                      // all +-1: len-1 additions per row (:576)
         uint32_t acc = 0;
@@ -1764,15 +1774,6 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
         BSYNC();
         return ((uint64_t)(sh.nbadd + sh.acc0) << 32) | sh.nbmul;
     }
-    // ProgramGen creates values (FactorOutRows sums, Triangle quotients): expand the packed rows to col / val / inv
-    {
-        const uint32_t *ent = (const uint32_t *)(ws + P.o_ent);
-        for (uint32_t i = wave; i < m; i += nwaves) {
-            const uint32_t base = P.rs[i], L = len[i];
-            for (uint32_t z = lane; z < L; z += 64u) { const uint32_t e = ent[base + z]; const uint2 V = P.vt[PLO_EVI(e)]; col[base + z] = PLO_ECOL(e); val[base + z] = V.x; inv[base + z] = V.y; }
-        }
-    }
-    PLO_BIG_FENCE(); BSYNC();
     // table region for the (column,|v|) multiset, sized by the live entries
     {
         uint32_t acc = 0;
@@ -1783,53 +1784,113 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
     const uint32_t live = sh.acc0 + sh.nmult;
     uint32_t hb = 6; while ((1ull << hb) < 4ull * live + 64ull && hb < P.hbits) ++hb;
     if ((1ull << hb) < 2ull * live + 16ull) { if (tid == 0) { atomicMax(errw, (uint32_t)BERR_PGEN); sh.errflag = BERR_PGEN; } BSYNC(); return 0; }
-    for (uint64_t s = tid; s < (1ull << hb); s += nth) tab[s] = PLO_GEMPTY;
+    {   // 16-byte stores, two slots each (the table is 256-byte aligned and holds at least 64 slots)
+        uint4 *t4 = (uint4 *)tab; const uint4 E = make_uint4((uint32_t)PLO_GEMPTY, (uint32_t)(PLO_GEMPTY >> 32), (uint32_t)PLO_GEMPTY, (uint32_t)(PLO_GEMPTY >> 32));
+        for (uint64_t s = tid; s < (1ull << (hb - 1u)); s += nth) t4[s] = E;
+    }
+    for (uint32_t c = tid; c < ncols0; c += nth) tcnt[c] = 0u;             // Triangle's entry counts per column (pass A3 + B below)
     BSYNC();
     if (tid == 0) sh.acc0 = 0;
     PLO_BIG_FENCE(); BSYNC();
     for (uint32_t k = tid; k < sh.nmult; k += nth)
         if (!gtab_flag(tab, ((uint64_t)multc[k] << rb) | multv[k], PLO_PGFLAG, hb)) wg_max(&sh.errflag, (uint32_t)BERR_TABLE);
     PLO_BIG_FENCE(); BSYNC();
-    // A1 occurrences of (j,e)
-    for (uint32_t i = wave; i < m; i += nwaves) {
-        const uint32_t base = P.rs[i], L = len[i];
-        for (uint32_t z = lane; z < L; z += 64u) {
-            const uint32_t e = babs(val[base + z], p);
-            if (!babsone(e, p)) if (!gtab_add(tab, ((uint64_t)col[base + z] << rb) | e, 1u, hb)) wg_max(&sh.errflag, (uint32_t)BERR_TABLE);
-        }
-    }
-    PLO_BIG_FENCE(); BSYNC();
-    // A2 one multiplication per repeated (j,e) not yet in multiples (:335-352)
+    PLO_PGSTAMP(0);
+    // One row per thread from here on: a row is a few entries (config 5: 2.8 on average, 17 at most), so a wave per row
+    // kept 3 of 64 lanes busy and made every row a dependent round trip of its own.
+    // ProgramGen creates values (FactorOutRows sums, Triangle quotients): expand the packed rows to col / val / inv,
+    // and count A1 the occurrences of (j,e) on the way
     {
-        uint32_t cnt = 0;
-        for (uint64_t s = tid; s < (1ull << hb); s += nth) {
-            uint64_t v = gload64(&tab[s]);
-            if (v != PLO_GEMPTY && ((uint32_t)v & PLO_PGCNT) >= 2u && !((uint32_t)v & PLO_PGFLAG)) { ++cnt; wg_or((unsigned long long *)&tab[s], (unsigned long long)PLO_PGFLAG); }
-        }
-        if (cnt) wg_add(&sh.acc1, cnt);
-    }
-    PLO_BIG_FENCE(); BSYNC();
-    if (tid == 0) { sh.nbmul += sh.acc1; sh.acc1 = 0; }
-    // A3 repeated entries become +-1 entries of a fresh column (:358-368)
-    for (uint32_t i = wave; i < m; i += nwaves) {
-        const uint32_t base = P.rs[i], L = len[i];
-        for (uint32_t z = lane; z < L; z += 64u) {
-            const uint32_t v = val[base + z], e = babs(v, p), c = col[base + z];
-            if (!babsone(e, p) && (gtab_find(tab, ((uint64_t)c << rb) | e, hb) & PLO_PGCNT) >= 2u) {
-                const uint32_t u = (v == e) ? 1u : p - 1u;
-                col[base + z] = PLO_BFRESH; val[base + z] = u; inv[base + z] = u;
+        const uint32_t *ent = (const uint32_t *)(ws + P.o_ent);
+        for (uint32_t i = tid; i < m; i += nth) {
+            const uint32_t base = P.rs[i], L = len[i];
+            for (uint32_t z = 0; z < L; ++z) {
+                const uint32_t w = ent[base + z], c = PLO_ECOL(w); const uint2 V = P.vt[PLO_EVI(w)];
+                col[base + z] = c; val[base + z] = V.x; inv[base + z] = V.y;
+                const uint32_t e = babs(V.x, p);
+                if (!babsone(e, p)) if (!gtab_add(tab, ((uint64_t)c << rb) | e, 1u, hb)) wg_max(&sh.errflag, (uint32_t)BERR_TABLE);
             }
         }
     }
     PLO_BIG_FENCE(); BSYNC();
-    // B FactorOutRows on every row (:375-420): |v| values of the row in per-wave LDS scratch
+    PLO_PGSTAMP(1);
+    // A2 one multiplication per repeated (j,e) not yet in multiples (:335-352); 4 independent loads in flight per thread
     {
+        uint32_t cnt = 0;
+        const uint64_t ns = 1ull << hb;
+        for (uint64_t s = tid; s < ns; s += 4ull * nth) {
+            uint64_t v[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) v[u] = s + u * nth < ns ? gload64(&tab[s + u * nth]) : PLO_GEMPTY;
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u)
+                if (v[u] != PLO_GEMPTY && ((uint32_t)v[u] & PLO_PGCNT) >= 2u && !((uint32_t)v[u] & PLO_PGFLAG)) { ++cnt; wg_or((unsigned long long *)&tab[s + u * nth], (unsigned long long)PLO_PGFLAG); }
+        }
+        if (cnt) wg_add(&sh.acc1, cnt);
+    }
+    PLO_BIG_FENCE(); BSYNC();
+    PLO_PGSTAMP(2);
+    if (tid == 0) { sh.nbmul += sh.acc1; sh.acc1 = 0; }
+    // A3 repeated entries become +-1 entries of a fresh column (:358-368), B FactorOutRows (:375-420) and the count of the
+    // non +-1 entries per column that Triangle starts from: all three look at one row only, in row order.  B is quadratic in
+    // the row's length: rows of more than 64 entries are listed and left to whole waves below.
+    uint32_t *longrow = (uint32_t *)(ws + P.o_aff);                       // (the CSE phase's list of affected rows, idle by now: 8 m words)
+    {
+        uint32_t addacc = 0;
+        for (uint32_t i = tid; i < m; i += nth) {
+            const uint32_t base = P.rs[i], L = len[i];
+            if (L > 64u) { longrow[wg_add(&sh.naff, 1u)] = i; continue; }
+            bool any = false;
+            for (uint32_t z = 0; z < L; ++z) {
+                const uint32_t v = val[base + z], e = babs(v, p);
+                if (babsone(e, p)) continue;
+                if ((gtab_find(tab, ((uint64_t)col[base + z] << rb) | e, hb) & PLO_PGCNT) >= 2u) {
+                    const uint32_t u = (v == e) ? 1u : p - 1u;
+                    col[base + z] = PLO_BFRESH; val[base + z] = u; inv[base + z] = u;
+                } else any = true;
+            }
+            if (!any) continue;
+            // In place, front to back: the entries before z are compacted already -- of a group of equal |v| exactly the leader is
+            // among them, holding |v| itself --, the entries behind z are untouched.
+            uint32_t kept = 0;
+            for (uint32_t z = 0; z < L; ++z) {
+                const uint32_t c = col[base + z], v = val[base + z], iv = inv[base + z];
+                uint32_t e = babs(v, p); if (babsone(e, p)) e = 0u;
+                uint32_t f = 0;
+                if (e != 0u) {
+                    bool dup = false;
+                    for (uint32_t y = 0; y < kept; ++y) dup |= babs(val[base + y], p) == e;
+                    if (dup) continue;                                     // its group has a leader
+                    for (uint32_t y = z + 1u; y < L; ++y) f += babs(val[base + y], p) == e ? 1u : 0u;
+                }
+                if (f) { addacc += f; col[base + kept] = PLO_BFRESH; val[base + kept] = e; inv[base + kept] = (v == e) ? iv : p - iv; }
+                else {
+                    if (kept != z) { col[base + kept] = c; val[base + kept] = v; inv[base + kept] = iv; }
+                    if (e != 0u && c != PLO_BFRESH) wg_add(&tcnt[c], 1u);
+                }
+                ++kept;
+            }
+            len[i] = kept;
+        }
+        if (addacc) wg_add(&sh.acc0, addacc);
+    }
+    PLO_BIG_FENCE(); BSYNC();
+    {   // the long rows, one wave each: |v| values of the row in per-wave LDS scratch
+        const uint32_t nlong = sh.naff;
         uint32_t *sc = scratch + (size_t)wave * P.scr_stride;             // per-wave scratch, stride = longest input row
         uint32_t addacc = 0;
-        for (uint32_t i = wave; i < m; i += nwaves) {
-            const uint32_t base = P.rs[i], L = len[i];
+        for (uint32_t li = wave; li < nlong; li += nwaves) {
+            const uint32_t i = longrow[li], base = P.rs[i], L = len[i];
             bool any = false;
-            for (uint32_t z = lane; z < L; z += 64u) { uint32_t e = babs(val[base + z], p); if (babsone(e, p)) e = 0u; sc[z] = e; any |= e != 0u; }
+            for (uint32_t z = lane; z < L; z += 64u) {
+                const uint32_t v = val[base + z]; uint32_t e = babs(v, p);
+                if (babsone(e, p)) e = 0u;
+                else if ((gtab_find(tab, ((uint64_t)col[base + z] << rb) | e, hb) & PLO_PGCNT) >= 2u) {
+                    const uint32_t u = (v == e) ? 1u : p - 1u;
+                    col[base + z] = PLO_BFRESH; val[base + z] = u; inv[base + z] = u; e = 0u;
+                }
+                sc[z] = e; any |= e != 0u;
+            }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
             if (!__ballot(any)) continue;
             uint32_t kept = 0;                                             // entries written so far (wave-uniform)
@@ -1846,7 +1907,7 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
                 if (keep) {
                     const uint32_t np = base + kept + (uint32_t)__popcll(km & ((1ull << lane) - 1ull));
                     if (leader) { col[np] = PLO_BFRESH; val[np] = e; inv[np] = (v == e) ? iv : p - iv; }
-                    else { col[np] = c; val[np] = v; inv[np] = iv; }
+                    else { col[np] = c; val[np] = v; inv[np] = iv; if (e != 0u && c != PLO_BFRESH) wg_add(&tcnt[c], 1u); }
                 }
                 kept += (uint32_t)__popcll(km);
             }
@@ -1856,34 +1917,37 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
         if (addacc) wg_add(&sh.acc0, addacc);
     }
     PLO_BIG_FENCE(); BSYNC();
+    PLO_PGSTAMP(3);
     if (tid == 0) { sh.nbadd += sh.acc0; sh.acc0 = 0; }
     // C Triangle (:427-507).  Columns with >= 2 non +-1 entries, ascending; rows of each in ascending order.
-    for (uint32_t c = tid; c < ncols0; c += nth) tcnt[c] = 0u;
-    PLO_BIG_FENCE(); BSYNC();
-    for (uint32_t i = wave; i < m; i += nwaves) {
-        const uint32_t base = P.rs[i], L = len[i];
-        for (uint32_t z = lane; z < L; z += 64u) { const uint32_t c = col[base + z]; if (c != PLO_BFRESH && !babsone(val[base + z], p)) wg_add(&tcnt[c], 1u); }
-    }
-    PLO_BIG_FENCE(); BSYNC();
-    if (tid == 0) {                                                        // ordered compaction (a few thousand columns)
-        uint32_t nc2 = 0, off = 0;
-        for (uint32_t c = 0; c < ncols0; ++c) { const uint32_t k = gload32(&tcnt[c]); if (k >= 2u) { cols2[nc2] = c; tptr2[nc2] = off; off += k; ++nc2; } }
-        tptr2[nc2] = off; sh.naff = nc2;
+    {   // ordered compaction by a workgroup prefix sum: a thread takes a contiguous chunk of columns, so ascending threads write ascending columns
+        static_assert(PLO_BIG_THREADS <= 512, "the wave totals of the scan sit in sh.part[8] and scratch[8]");
+        const uint32_t K = (ncols0 + nth - 1u) / nth, c0 = tid * K < ncols0 ? tid * K : ncols0, c1 = c0 + K < ncols0 ? c0 + K : ncols0;
+        uint32_t cnt = 0, sum = 0;
+        for (uint32_t c = c0; c < c1; ++c) { const uint32_t k = gload32(&tcnt[c]); cnt += k >= 2u ? 1u : 0u; sum += k >= 2u ? k : 0u; }
+        const uint32_t incc = wave_incl_scan(cnt), incs = wave_incl_scan(sum);
+        if (lane == 63u) { sh.part[wave] = incc; scratch[wave] = incs; }
+        BSYNC();
+        uint32_t nc = incc - cnt, off = incs - sum;
+        for (uint32_t w = 0; w < wave; ++w) { nc += sh.part[w]; off += scratch[w]; }
+        // tcnt[c] becomes the column's write position in tlist (top bit: not a Triangle column), so the fill needs no search
+        for (uint32_t c = c0; c < c1; ++c) {
+            const uint32_t k = gload32(&tcnt[c]);
+            if (k >= 2u) { cols2[nc] = c; tptr2[nc] = off; tcnt[c] = off; off += k; ++nc; } else tcnt[c] = 0x80000000u;
+        }
+        if (tid == nth - 1u) { tptr2[nc] = off; sh.naff = nc; }
     }
     PLO_BIG_FENCE(); BSYNC();
     const uint32_t nc2 = sh.naff;
     if (nc2) {
-        // fill the row lists (binary search of the column in cols2), then sort each list
-        for (uint32_t c = tid; c < ncols0; c += nth) tcnt[c] = 0u;
-        PLO_BIG_FENCE(); BSYNC();
-        for (uint32_t i = wave; i < m; i += nwaves) {
+        // fill the row lists, then sort each list
+        for (uint32_t i = tid; i < m; i += nth) {
             const uint32_t base = P.rs[i], L = len[i];
-            for (uint32_t z = lane; z < L; z += 64u) {
+            for (uint32_t z = 0; z < L; ++z) {
                 const uint32_t c = col[base + z];
                 if (c == PLO_BFRESH || babsone(val[base + z], p)) continue;
-                uint32_t lo = 0, hi = nc2;
-                while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (cols2[mid] < c) lo = mid + 1; else hi = mid; }
-                if (lo < nc2 && cols2[lo] == c) tlist[tptr2[lo] + wg_add(&tcnt[c], 1u)] = i;
+                const uint32_t pos = wg_add(&tcnt[c], 1u);
+                if (pos < 0x80000000u) tlist[pos] = i;
             }
         }
         PLO_BIG_FENCE(); BSYNC();
@@ -1892,6 +1956,7 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
             for (uint32_t u = 1; u < k; ++u) { uint32_t t = l[u], w = u; while (w > 0 && l[w - 1] > t) { l[w] = l[w - 1]; --w; } l[w] = t; }
         }
         PLO_BIG_FENCE(); BSYNC();
+        PLO_PGSTAMP(4);
         if (wave == 0) {
             // A column's rows sit one per lane in PLO_TRI_R registers (round 4: 256 rows; one register = 64 rows until round 3): position
             // q = 64 r + lane, ascending q = ascending row -- the order in which the reference scans the column (:433-447).
@@ -1985,20 +2050,21 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
                         addone = f - 1u;
                     }
                     addacc += (uint32_t)__shfl((int)addone, 0);
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __builtin_amdgcn_wave_barrier();   // lane 0's stores before the other lanes' loads (same wave: the candidate's scope is enough)
                 }
             }
             if (lane == 0) { sh.nbmul += mulacc; sh.nbadd += addacc; }
         }
         PLO_BIG_FENCE(); BSYNC();
-    }
+        PLO_PGSTAMP(5);
+    } else PLO_PGSTAMP(4);
     // D output rows (:547-604)
     {
         uint32_t addacc = 0, mulacc = 0;
-        for (uint32_t i = wave; i < m; i += nwaves) {
+        for (uint32_t i = tid; i < m; i += nth) {
             const uint32_t base = P.rs[i], L = len[i];
-            if (lane == 0 && L > 1u) addacc += L - 1u;
-            for (uint32_t z = lane; z < L; z += 64u) {
+            if (L > 1u) addacc += L - 1u;
+            for (uint32_t z = 0; z < L; ++z) {
                 const uint32_t e = babs(val[base + z], p), c = col[base + z];
                 if (!babsone(e, p)) {
                     const bool reuse = c != PLO_BFRESH && (gtab_find(tab, ((uint64_t)c << rb) | e, hb) & PLO_PGFLAG);
@@ -2010,6 +2076,7 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
         if (mulacc) wg_add(&sh.acc1, mulacc);
     }
     BSYNC();
+    PLO_PGSTAMP(6);
     if (sh.errflag) { if (tid == 0) atomicMax(errw, sh.errflag); return 0; }
     return ((uint64_t)(sh.nbadd + sh.acc0) << 32) | (sh.nbmul + sh.acc1);
 }
@@ -2063,7 +2130,7 @@ template <int MODE, bool DEFER, bool IDK = false> __global__ __launch_bounds__(P
             const uint32_t a = (uint32_t)(res >> 32), mu_ = (uint32_t)res;
             if (J.adds) J.adds[c] = a;
             if (J.muls) J.muls[c] = mu_;
-            if (J.stats) { atomicAdd(&J.stats[32], sh.steps); atomicAdd(&J.stats[33], sh.fullscans); atomicAdd(&J.stats[34], sh.rebuilds); atomicAdd(&J.stats[35], sh.nbisect); atomicAdd(&J.stats[36], sh.spilltot); atomicAdd(&J.stats[37], sh.listover); atomicAdd(&J.stats[38], 1u); atomicAdd(&J.stats[39], sh.nforced); atomicMax(&J.stats[43], sh.derr); for (int q = 0; q < 4; ++q) { J.stats[44 + q] = (uint32_t)(sh.tmg[q] / 100ull); J.stats[48 + q] = (uint32_t)(sh.tmb[q] / 100ull); } J.stats[52] = sh.ngrp; J.stats[55] = (uint32_t)((tk1 - tk0) / 100ull); J.stats[56] = (uint32_t)((tk2 - tk1) / 100ull); atomicAdd(&J.stats[53], sh.nwin); atomicAdd(&J.stats[54], sh.nsearched); atomicAdd(&J.stats[40], sh.hotops); { const uint32_t lo_ = atomicAdd(&J.stats[41], sh.logtot_lo); if (lo_ + sh.logtot_lo < lo_) atomicAdd(&J.stats[42], 1u); atomicAdd(&J.stats[42], sh.logtot_hi); }
+            if (J.stats) { atomicAdd(&J.stats[32], sh.steps); atomicAdd(&J.stats[33], sh.fullscans); atomicAdd(&J.stats[34], sh.rebuilds); atomicAdd(&J.stats[35], sh.nbisect); atomicAdd(&J.stats[36], sh.spilltot); atomicAdd(&J.stats[37], sh.listover); atomicAdd(&J.stats[38], 1u); atomicAdd(&J.stats[39], sh.nforced); atomicMax(&J.stats[43], sh.derr); for (int q = 0; q < 4; ++q) { J.stats[44 + q] = (uint32_t)(sh.tmg[q] / 100ull); J.stats[48 + q] = (uint32_t)(sh.tmb[q] / 100ull); } J.stats[52] = sh.ngrp; J.stats[55] = (uint32_t)((tk1 - tk0) / 100ull); J.stats[56] = (uint32_t)((tk2 - tk1) / 100ull); J.stats[12] = (uint32_t)(sh.tld / 100ull); for (int q = 0; q < 7; ++q) J.stats[57 + q] = ok ? (uint32_t)(sh.tpg[q] / 100ull) : 0u; atomicAdd(&J.stats[53], sh.nwin); atomicAdd(&J.stats[54], sh.nsearched); atomicAdd(&J.stats[40], sh.hotops); { const uint32_t lo_ = atomicAdd(&J.stats[41], sh.logtot_lo); if (lo_ + sh.logtot_lo < lo_) atomicAdd(&J.stats[42], 1u); atomicAdd(&J.stats[42], sh.logtot_hi); }
                 J.stats[0] = sh.steps; J.stats[1] = sh.fullscans; J.stats[2] = sh.rebuilds; for (int q = 0; q < 8; ++q) J.stats[4 + q] = (uint32_t)(sh.tph[q] / 100ull);
 #ifdef PLO_BIG_PROFILE
                 for (int q = 0; q < 4; ++q) { J.stats[16 + q] = (uint32_t)(sh.tb1[q] / 100ull); J.stats[20 + q] = (uint32_t)(sh.tb2[q] / 100ull); J.stats[24 + q] = sh.nb[q]; }
