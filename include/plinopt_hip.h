@@ -298,7 +298,7 @@ int  plo_lin_search_multi(const plo_qcsr_t *A, uint64_t seed0, uint64_t nseeds, 
  * modulus 0 is Q: the rows of L and R and the columns of P are scaled to integers on the host, and the counts are exact.
  * PLO_E_UNSUPPORTED: a modulus of 2^31 or more, a denominator that is no unit modulo the modulus, or a Q input whose
  * transformed entries are not provably below 2^62 (row L1 norm times 2^(s-2)).  PLO_E_CAPACITY: m, k or n above 16, more
- * than 4096 rows, more than 2^20 transformed entries, or an input that does not fit LDS.  PLO_E_ARG: shapes that are not
+ * than 4096 rows, 2^21 transformed entries or more, or an input that does not fit LDS.  PLO_E_ARG: shapes that are not
  * m k, k n, m n. */
 #define PLO_ORBIT_BASE_SEED 0xFFFFFFFFFFFFFFFFull     /* U = V = W = identity: the input itself */
 #define PLO_ORBIT_DENSITY   0                          /* -s */

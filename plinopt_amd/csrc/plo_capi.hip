@@ -2264,7 +2264,9 @@ int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
     const uint32_t nnz = (uint32_t)val.size(), nrows = 3u * r, smax = std::max(m, std::max(k, n));
     plo_orbit_plan *pl = new plo_orbit_plan();
     plo::OrbitPlan &Q = pl->P;
-    Q.m = m; Q.k = k; Q.n = n; Q.r = r; Q.nnz = nnz; Q.measure = (uint32_t)measure; Q.p = modulus;
+    Q.m = m; Q.k = k; Q.n = n; Q.r = r; Q.nnz = nnz; Q.p = modulus;
+    // modulo a number every run scores by density, whatever `measure` says (reference src/orbiter.cpp:425)
+    Q.measure = modulus ? (uint32_t)PLO_ORBIT_DENSITY : (uint32_t)measure;
     // shared LDS: values, scales, row pointers, positions
     Q.off_scale = round_up(8u * nnz, 16); Q.off_rp = Q.off_scale + round_up(8u * nrows, 16); Q.off_pos = Q.off_rp + round_up(4u * (nrows + 1u), 16);
     Q.shared_bytes = Q.off_pos + round_up(2u * nnz, 16);

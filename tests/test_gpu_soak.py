@@ -10,6 +10,10 @@ against the product's host engines.
   in-place trilinear   500 triples (+-1 and rational, plain and `-e`) x 12 seeds x both variants          (soak_misc.py)
   change of basis      300 groups of 1-4 enumerations, single and batched launches                         (soak_misc.py --cob)
   schedule enumeration 500 matrices x 96 schedules of the exhaustive tree (-E)                              (soak_misc.py --enum)
+  in-place linear      58 edge-shape matrices (empty rows, 64-entry rows, 129 rows, column 16381, 1 wave per
+                        workgroup, 160 KiB of LDS) x 11 seeds, against tests/lin_oracle.py                  (test_gpu_lin_orbit_synth.py)
+  orbit                45 edge-shape triples (dimensions 1 to 16, 1/2/4 waves per workgroup, composite and 31-bit
+                        moduli, Q next to the int64 bound) x 11 seeds, against tests/orbit_oracle.py        (test_gpu_lin_orbit_synth.py)
 
 A refusal the header documents (PLO_E_CAPACITY / PLO_E_UNSUPPORTED) is counted and bounded, anything else fails."""
 import os
