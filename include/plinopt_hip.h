@@ -55,7 +55,7 @@ typedef struct {
     uint32_t waves_per_wg;   /* candidates in flight per workgroup */
     uint32_t grid;           /* workgroups per launch */
     uint64_t algo_bytes;     /* algorithmic bytes per candidate, B_cand = 8*nnz + 12*P0 + 8 */
-    uint32_t reduce;         /* plo_*_search_multi: 1 = the minimum over the devices is the result of the RCCL MIN all-reduce (and equals the host's) */
+    uint32_t reduce;         /* plo_*_search_multi: 1 = the RCCL MIN all-reduce over the devices ran and gave the host's minimum (the one returned) */
     uint32_t reserved;
     double   reduce_seconds; /* plo_*_search_multi: wall time inside the all-reduce (two 8-byte MIN all-reduces; communicator set-up excluded: cached) */
 } plo_stats_t;
@@ -118,12 +118,12 @@ int plo_cse_search(const plo_csr_t *A, uint32_t p, uint64_t seed0, uint64_t nsee
  * bin/optimizer --gpu N uses), one host thread and one device per shard (devices[k], or 0..ndev-1 when devices is NULL;
  * the same ordinal may be listed twice), each thread with its own stream and plan; the result is the minimum under the
  * total order (cmpOpCount key of include/plinopt_optimize.h:53-64, seed) -- what the `#pragma omp critical` of
- * include/plinopt_optimize.inl:1214-1237 keeps.  stats->kernel_ms is the slowest shard's kernel time.  With two or more
- * DISTINCT devices the minimum is taken by RCCL over a communicator of the devices (librccl loaded at run time, the
- * communicator kept for the life of the process): one 8-byte MIN all-reduce of the cost key, one of the seed offset among the
- * shards that hold the minimal key -- the lexicographic minimum whatever the width of the costs.  The host minimum is its check:
- * a difference is a '#' diagnostic on stderr and the host value is returned.  stats->reduce says whether the all-reduce gave the
- * result, stats->reduce_seconds its wall time.  PLO_MULTI_REDUCE=host|rccl overrides (rccl: also with one device; then a missing
+ * include/plinopt_optimize.inl:1214-1237 keeps.  stats->kernel_ms is the slowest shard's kernel time.  The minimum of the
+ * shards is taken on the host and returned.  With two or more DISTINCT devices RCCL cross-checks it over a communicator of the
+ * devices (librccl loaded at run time, the communicator kept for the life of the process): one 8-byte MIN all-reduce of the cost
+ * key, one of the seed offset among the shards that hold the minimal key -- the lexicographic minimum whatever the width of the
+ * costs.  A difference is a '#' diagnostic on stderr.  stats->reduce says whether the all-reduce ran and agreed,
+ * stats->reduce_seconds its wall time.  PLO_MULTI_REDUCE=host|rccl overrides (rccl: also with one device; then a missing
  * librccl is an error).  A shard the device refuses (PLO_E_CAPACITY / PLO_E_UNSUPPORTED) makes the call return that code.
  * Across processes bench.py and plinopt_amd/dist.py reduce the same words with torch.distributed (RCCL). */
 int plo_cse_search_multi(const plo_csr_t *A, uint32_t p, uint64_t seed0, uint64_t nseeds, int cost_mode,
@@ -248,7 +248,7 @@ int  plo_tril_plan_create_q(const plo_qcsr_t *A, const plo_qcsr_t *B, const plo_
 void plo_tril_plan_destroy(plo_tril_plan_t *plan);
 /* ops6[6k..6k+5] = ADD,SCA,MUL of variant 0 then of variant 1 for candidate k (seeds[k], or seed0+k when seeds==NULL) */
 int  plo_tril_cost_many(plo_tril_plan_t *plan, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats);
-int  plo_tril_search(plo_tril_plan_t *plan, uint64_t seed0, uint64_t nseeds, plo_tril_best_t *best, plo_stats_t *stats);
+int  plo_tril_search(plo_tril_plan_t *plan, uint64_t seed0, uint64_t nseeds, plo_tril_best_t *best, plo_stats_t *stats);   /* PLO_E_HIP without plo_init, as plo_lin_search (no live plan exists then) */
 /* The restart loop of SearchTriLinearAlgorithm (include/plinopt_inplace.inl:837-924) over `ndev` devices from one process --
  * BASELINE configs[3], `bin/trilplacer L R P` seed-sharded over the GPUs of a node with an RCCL MIN: contiguous shards of the seed
  * range, one host thread, one device and one plan (plo_tril_plan_create_q of the three matrices) each; the winner is the minimum

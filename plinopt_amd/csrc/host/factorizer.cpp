@@ -12,9 +12,6 @@
 #include "plo_sparsify.hpp"
 
 #include <chrono>
-#ifdef _OPENMP
-#include <omp.h>
-#endif
 
 using namespace plo;
 
@@ -109,9 +106,7 @@ template <class F> int tfactorizer(const F &f, const SparseMat<typename F::Elt> 
 
 int main(int argc, char **argv)
 {
-#ifdef _OPENMP
-    if (!getenv("OMP_NUM_THREADS")) omp_set_num_threads(std::min(omp_get_max_threads(), 64));
-#endif
+    cap_omp_threads();
     Fmt fmt = PRETTY; std::string filename; size_t innerdim = 0, loops = 100, maxnumcoeff = 11, blocksize = 4; uint64_t q = 0, seed0 = 0;
     bool initialSparsification = false, initialElimination = true;
     for (int i = 1; i < argc; ++i) {

@@ -15,46 +15,21 @@
 // ==========================================================================
 #include "plo_inplace.hpp"
 #include "plo_dl.hpp"
-#include "../../../include/plinopt_hip.h"
 #include <chrono>
 #include <fstream>
-#include <omp.h>
 #include <tuple>
 
 using namespace plo;
 
 namespace {
 struct HipLin {
-    void *h = nullptr;
-    decltype(&plo_init) init = nullptr; decltype(&plo_last_error) last_error = nullptr;
-    decltype(&plo_lin_plan_create_q) create = nullptr; decltype(&plo_lin_plan_destroy) destroy = nullptr; decltype(&plo_lin_search) search = nullptr;
-    decltype(&plo_lin_search_multi) search_multi = nullptr;
-    bool load() {
-        h = open_hip_lib();
-        if (!h) return false;
-        init = (decltype(init))dlsym(h, "plo_init"); last_error = (decltype(last_error))dlsym(h, "plo_last_error");
-        create = (decltype(create))dlsym(h, "plo_lin_plan_create_q"); destroy = (decltype(destroy))dlsym(h, "plo_lin_plan_destroy");
-        search = (decltype(search))dlsym(h, "plo_lin_search"); search_multi = (decltype(search_multi))dlsym(h, "plo_lin_search_multi");
-        return init && last_error && create && destroy && search && search_multi;
-    }
+    void *h = open_hip_lib(); bool ok = h != nullptr;
+    PLO_SYM(init, plo_init); PLO_SYM(last_error, plo_last_error);
+    PLO_SYM(create, plo_lin_plan_create_q); PLO_SYM(destroy, plo_lin_plan_destroy);
+    PLO_SYM(search, plo_lin_search); PLO_SYM(search_multi, plo_lin_search_multi);
 };
 
 bool better(const Tricount &l, const Tricount &r) { return l[0] < r[0] || (l[0] == r[0] && l[1] < r[1]); }   // :637-641, :655-659
-
-// rational CSR for plo_lin_plan_create_q; wide: a coefficient that does not fit the C-ABI's 64-bit numerators and denominators
-struct QCsr { std::vector<uint32_t> rp{0}, col; std::vector<int64_t> num, den; bool wide = false; };
-QCsr qcsr(const QMat &M) {
-    QCsr c;
-    for (const auto &row : M.rows) {
-        for (const auto &e : row) {
-            c.col.push_back((uint32_t)e.first);
-            if (e.second.n > (__int128)INT64_MAX || e.second.n < -(__int128)INT64_MAX || e.second.d > (__int128)INT64_MAX || e.second.d < -(__int128)INT64_MAX) c.wide = true;
-            c.num.push_back((int64_t)e.second.n); c.den.push_back((int64_t)e.second.d);
-        }
-        c.rp.push_back((uint32_t)c.col.size());
-    }
-    return c;
-}
 
 struct Opts { size_t loops = 30; uint64_t seed0 = 0; int gpu = 1; bool transposed = false, costs = false, cand = false; uint64_t cseed = 0; int cvar = 0; };
 
@@ -107,8 +82,8 @@ int find_program(std::istream &in, const Opts &o) {
         std::string why = "a coefficient wider than 64 bits";
         if (o.gpu && !ca.wide) {
             HipLin L;
-            if (!L.load()) { std::cerr << "# \033[1;31mERROR: libplinopt_hip.so cannot be loaded or lacks plo_lin_search\033[0m\n"; return 2; }   // no silent fallback: --gpu 0 selects the host loop
-            const plo_qcsr_t a{(uint32_t)A.rowdim(), (uint32_t)A.coldim(), ca.rp.data(), ca.col.data(), ca.num.data(), ca.den.data()};
+            if (!L.ok) { std::cerr << "# \033[1;31mERROR: libplinopt_hip.so cannot be loaded or lacks plo_lin_search\033[0m\n"; return 2; }   // no silent fallback: --gpu 0 selects the host loop
+            const plo_qcsr_t a = ca.view();
             plo_lin_best_t r{}; plo_stats_t st{};
             int rc;
             if (o.gpu >= 2) {
@@ -160,9 +135,7 @@ int find_program(std::istream &in, const Opts &o) {
 } // namespace
 
 int main(int argc, char **argv) {
-#ifdef _OPENMP
-    if (!getenv("OMP_NUM_THREADS")) omp_set_num_threads(std::min(omp_get_max_threads(), 64));   // cgroup-limited boxes report all host cores
-#endif
+    cap_omp_threads();
     Opts o; std::vector<std::string> files;
     for (int i = 1; i < argc; ++i) {
         std::string a(argv[i]);

@@ -13,16 +13,10 @@
 #include "plo_host.hpp"
 #include "plo_fast.hpp"
 #include "plo_compact.hpp"
-#include "../../../include/plinopt_hip.h"
+#include "plo_dl.hpp"
 
 #include <chrono>
 #include <memory>
-#include <dlfcn.h>
-#include <libgen.h>
-#include <unistd.h>
-#ifdef _OPENMP
-#include <omp.h>
-#endif
 
 using namespace plo;
 using Ops = std::pair<size_t, size_t>;
@@ -32,41 +26,18 @@ namespace {
 static int g_failures = 0;   // GPU calls that failed and replays that disagreed with the search: the exit status is non-zero when any happened
 
 struct HipLib {
-    void *h = nullptr;
-    decltype(&plo_init) init = nullptr;
-    decltype(&plo_last_error) last_error = nullptr;
-    decltype(&plo_cse_search) cse_search = nullptr;
-    decltype(&plo_cse_search_multi) cse_search_multi = nullptr;
-    decltype(&plo_cse_chain_create) chain_create = nullptr;
-    decltype(&plo_cse_chain_search) chain_search = nullptr;
-    decltype(&plo_cse_chain_destroy) chain_destroy = nullptr;
-    decltype(&plo_shutdown) shutdown = nullptr;
-    decltype(&plo_cse_plan_create) plan_create = nullptr;
-    decltype(&plo_cse_plan_destroy) plan_destroy = nullptr;
-    decltype(&plo_cse_enum_search_plan) enum_search = nullptr;
-    decltype(&plo_cse_chain_batch) chain_batch = nullptr;
-    decltype(&plo_kernel_search) kernel_search = nullptr;   // optional: -K with the decompositions on the device
-    decltype(&plo_kernel_search_multi) kernel_search_multi = nullptr;   // optional: the same over N devices from this process
-    bool load(const char *argv0) {
-        std::vector<std::string> cand;
-        for (const char *v : {"PLO_HIP_LIB", "PLINOPT_HIP_LIB"}) if (const char *e = getenv(v)) cand.emplace_back(e);   // (one name for the tools and plinopt_amd/capi.py; the older one still works)
-        char buf[4096]; ssize_t k = readlink("/proc/self/exe", buf, sizeof buf - 1);
-        if (k > 0) { buf[k] = 0; std::string d = dirname(buf); cand.push_back(d + "/../plinopt_amd/libplinopt_hip.so"); cand.push_back(d + "/libplinopt_hip.so"); }
-        cand.emplace_back("libplinopt_hip.so");
-        for (auto &c : cand) { h = dlopen(c.c_str(), RTLD_NOW | RTLD_GLOBAL); if (h) break; }
-        (void)argv0;
-        if (!h) { ++g_failures, std::cerr << "# \033[1;31mERROR: cannot load libplinopt_hip.so: " << dlerror() << "\033[0m\n"; return false; }
-        init = (decltype(init))dlsym(h, "plo_init"); last_error = (decltype(last_error))dlsym(h, "plo_last_error");
-        cse_search = (decltype(cse_search))dlsym(h, "plo_cse_search"); cse_search_multi = (decltype(cse_search_multi))dlsym(h, "plo_cse_search_multi"); shutdown = (decltype(shutdown))dlsym(h, "plo_shutdown");
-        chain_create = (decltype(chain_create))dlsym(h, "plo_cse_chain_create"); chain_search = (decltype(chain_search))dlsym(h, "plo_cse_chain_search");
-        chain_destroy = (decltype(chain_destroy))dlsym(h, "plo_cse_chain_destroy");
-        plan_create = (decltype(plan_create))dlsym(h, "plo_cse_plan_create"); plan_destroy = (decltype(plan_destroy))dlsym(h, "plo_cse_plan_destroy");
-        enum_search = (decltype(enum_search))dlsym(h, "plo_cse_enum_search_plan");
-        chain_batch = (decltype(chain_batch))dlsym(h, "plo_cse_chain_batch");
-        kernel_search = (decltype(kernel_search))dlsym(h, "plo_kernel_search");
-        kernel_search_multi = (decltype(kernel_search_multi))dlsym(h, "plo_kernel_search_multi");
-        return init && last_error && cse_search && shutdown && chain_create && chain_search && chain_destroy && plan_create && plan_destroy && enum_search && chain_batch;
-    }
+    void *h; bool ok;
+    PLO_SYM(init, plo_init); PLO_SYM(last_error, plo_last_error); PLO_SYM(shutdown, plo_shutdown);
+    PLO_SYM(cse_search, plo_cse_search);
+    PLO_SYM_OPT(cse_search_multi, plo_cse_search_multi);
+    PLO_SYM(chain_create, plo_cse_chain_create); PLO_SYM(chain_search, plo_cse_chain_search); PLO_SYM(chain_destroy, plo_cse_chain_destroy);
+    PLO_SYM(plan_create, plo_cse_plan_create); PLO_SYM(plan_destroy, plo_cse_plan_destroy);
+    PLO_SYM(enum_search, plo_cse_enum_search_plan);
+    PLO_SYM(chain_batch, plo_cse_chain_batch);
+    PLO_SYM_OPT(kernel_search, plo_kernel_search);   // optional: -K with the decompositions on the device
+    PLO_SYM_OPT(kernel_search_multi, plo_kernel_search_multi);   // optional: the same over N devices from this process
+    explicit HipLib(void *lib = nullptr) : h(lib), ok(lib != nullptr) {}   // empty until load(): the methods load it only when they use the GPU
+    bool load() { *this = HipLib(open_hip_lib()); if (!h) ++g_failures; return ok; }
 };
 
 bool g_fork_shards = false;   // --fork-shards: --gpu N with one forked child per device instead of one thread per device
@@ -135,12 +106,12 @@ template <class E> void to_csr(const SparseMat<E> &A, std::vector<uint32_t> &rp,
 
 // LUOptimiser :1021-1109.  Returns false when the method could not run (reported on stderr).
 template <class F> bool lu_method(const F &f, const SparseMat<typename F::Elt> &lM, uint64_t seed0, size_t loops, int gpu, uint32_t q,
-                                  int verbose, Ops &gops, std::string &gtext, const char *argv0) {
+                                  int verbose, Ops &gops, std::string &gtext) {
     const LUFactors<F> lu = sparse_lu(f, lM);
     uint64_t seed = 0; Ops best; bool have = false;
     if constexpr (std::is_same<F, ZpField>::value) if (q != 0 && gpu > 0) {
         HipLib L;
-        if (!L.load(argv0) || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -G: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return false; }
+        if (!L.load() || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -G: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return false; }
         std::vector<uint32_t> rp1, c1, v1, rp2, c2, v2;
         to_csr(lu.U, rp1, c1, v1); to_csr(lu.L, rp2, c2, v2);
         plo_csr_t A{(uint32_t)lu.U.rowdim(), (uint32_t)lu.U.coldim(), rp1.data(), c1.data(), v1.data()};
@@ -184,13 +155,13 @@ template <class F> std::string ab_text(const F &f, const ABFactors<F> &ab, uint6
 
 // ABOptimiser :1114-1186 for the inner dimension coldim(M).  Returns false when the method could not run.
 template <class F> bool ab_method(const F &f, const SparseMat<typename F::Elt> &lM, uint64_t seed0, size_t loops, int gpu, uint32_t q,
-                                  int verbose, Ops &gops, std::string &gtext, const char *argv0, size_t innerdim = 0) {
+                                  int verbose, Ops &gops, std::string &gtext, size_t innerdim = 0) {
     if (lM.rowdim() < lM.coldim()) { std::clog << "# -A skipped: fewer rows than columns" << std::endl; return false; }
     const ABFactors<F> ab = ab_factorize(f, lM, 1 + (loops >> 3), seed0, innerdim);                         // :1129-1130
     uint64_t seed = 0; Ops best; bool have = false;
     if constexpr (std::is_same<F, ZpField>::value) if (q != 0 && gpu > 0) {
         HipLib L;
-        if (!L.load(argv0) || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -A: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return false; }
+        if (!L.load() || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -A: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return false; }
         std::vector<uint32_t> rp1, c1, v1, rp2, c2, v2;
         to_csr(ab.CoB, rp1, c1, v1); to_csr(ab.Alt, rp2, c2, v2);
         plo_csr_t A{(uint32_t)ab.CoB.rowdim(), (uint32_t)ab.CoB.coldim(), rp1.data(), c1.data(), v1.data()};
@@ -300,13 +271,13 @@ template <class F> bool kernel_batch_gpu(HipLib &L, const std::vector<KernelDeco
 }
 
 template <class F> bool kernel_method(const F &f, const SparseMat<typename F::Elt> &lM, uint64_t seed0, size_t loops, int gpu, uint32_t q,
-                                      int verbose, Ops &gops, std::string &gtext, const char *argv0) {
+                                      int verbose, Ops &gops, std::string &gtext) {
     uint64_t seed = 0, bdec = 0; Ops best; bool have = false, on_device = false; double kms = 0; uint64_t ncand = 0;
     const uint64_t nblocks = (loops + PLO_KERNEL_BLOCK - 1) / PLO_KERNEL_BLOCK;
     bool use_gpu = false;
     HipLib L;
     if constexpr (std::is_same<F, ZpField>::value) if (q != 0 && gpu > 0 && !g_kshard.done) {
-        if (!L.load(argv0) || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -K: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return false; }
+        if (!L.load() || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -K: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return false; }
         use_gpu = true;
     }
     const uint64_t full = loops / PLO_KERNEL_BLOCK;                    // full blocks go to the GPU in batches of one launch each
@@ -392,7 +363,7 @@ template <class F> bool kernel_method(const F &f, const SparseMat<typename F::El
 // Orders that give the same decomposition (same computed rows, same combinations) are searched once; the restarts are
 // shared out between the distinct decompositions.
 template <class F> bool allkernels_method(const F &f, const SparseMat<typename F::Elt> &lM, uint64_t seed0, size_t loops, int gpu, uint32_t q,
-                                          int verbose, Ops &gops, std::string &gtext, const char *argv0) {
+                                          int verbose, Ops &gops, std::string &gtext) {
     const size_t m = lM.rowdim();
     if (m > 9) { std::clog << "# -N skipped: " << m << "! row orders (this build walks up to 9!)" << std::endl; return false; }
     std::vector<size_t> ord(m);
@@ -409,7 +380,7 @@ template <class F> bool allkernels_method(const F &f, const SparseMat<typename F
     } while (std::next_permutation(ord.begin(), ord.end()));
     bool use_gpu = false; HipLib L;
     if constexpr (std::is_same<F, ZpField>::value) if (q != 0 && gpu > 0) {
-        if (!L.load(argv0) || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -N: cannot use the GPU\033[0m" << std::endl; return false; }
+        if (!L.load() || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -N: cannot use the GPU\033[0m" << std::endl; return false; }
         use_gpu = true;
     }
     const uint64_t per = std::max<uint64_t>(1, loops / distinct.size());
@@ -466,14 +437,14 @@ template <class F> std::string schedule_text(const F &f, const SparseMat<typenam
 // but toy inputs).  Returns false when the method could not run.
 bool g_recsub_order = false;   // --recsub: choose the schedule as RecSub does (:950-959): additions, then ITS multiplication count (before ProgramGen)
 template <class F> bool exhaustive_method(const F &f, const SparseMat<typename F::Elt> &lM, uint64_t budget, int gpu, uint32_t q,
-                                          int verbose, Ops &gops, std::string &gtext, const char *argv0) {
+                                          int verbose, Ops &gops, std::string &gtext) {
     Ops best; uint64_t bidx = 0, maxprod = 1, done = 0; bool have = false, on_gpu = false; double kms = 0;
     // `best` holds the SELECTION key: (adds, muls of the program), or with --recsub (adds, RecSub's multiplication count)
     auto better = [](const Ops &a, const Ops &b) { return cmp_op_count(a, b, 1); };
     HipLib L; plo_plan_t *plan = nullptr;
     std::vector<uint32_t> rp, cc, vv;
     if constexpr (std::is_same<F, ZpField>::value) if (q != 0 && gpu > 0) {
-        if (!L.load(argv0) || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -E: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return false; }
+        if (!L.load() || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -E: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return false; }
         to_csr(lM, rp, cc, vv);
         plo_csr_t A{(uint32_t)lM.rowdim(), (uint32_t)lM.coldim(), rp.data(), cc.data(), vv.data()};
         if (L.plan_create(&A, q, &plan) != PLO_OK) { std::clog << "# -E skipped: " << L.last_error() << std::endl; return false; }
@@ -527,7 +498,7 @@ template <class F> bool exhaustive_method(const F &f, const SparseMat<typename F
 
 template <class F>
 int run(const F &f, const QMat &MQ, size_t loops, uint64_t seed0, int gpu, bool tryDirect, bool tryKernel, bool tryLU,
-        bool tryAB, bool mostCSE, bool allkernels, bool kfi, int verbose, uint32_t q, const char *argv0)
+        bool tryAB, bool mostCSE, bool allkernels, bool kfi, int verbose, uint32_t q)
 {
     auto t0 = std::chrono::steady_clock::now();
     std::clog << std::string(40, '#') << std::endl;
@@ -559,7 +530,7 @@ int run(const F &f, const QMat &MQ, size_t loops, uint64_t seed0, int gpu, bool 
     };
     if constexpr (std::is_same<F, ZpField>::value) if (tryDirect && q != 0 && gpu >= 2 && loops > 0 && !use_forks) {
         HipLib L;
-        if (!L.load(argv0) || !L.cse_search_multi) { ++g_failures; std::cerr << "# \033[1;31mERROR: shard failed: libplinopt_hip.so " << (L.cse_search ? "lacks plo_cse_search_multi" : "cannot be loaded") << "\033[0m" << std::endl; return 2; }
+        if (!L.load() || !L.cse_search_multi) { ++g_failures; std::cerr << "# \033[1;31mERROR: shard failed: libplinopt_hip.so " << (L.cse_search ? "lacks plo_cse_search_multi" : "cannot be loaded") << "\033[0m" << std::endl; return 2; }
         std::vector<uint32_t> rp(1, 0), cc, vv;
         for (auto &r : lM.rows) { for (auto &e : r) { cc.push_back((uint32_t)e.first); vv.push_back((uint32_t)e.second); } rp.push_back((uint32_t)cc.size()); }
         std::vector<int> devs((size_t)gpu); for (int r = 0; r < gpu; ++r) devs[(size_t)r] = shard_device(r);
@@ -591,7 +562,7 @@ int run(const F &f, const QMat &MQ, size_t loops, uint64_t seed0, int gpu, bool 
                 return o;
             }
             HipLib L;
-            if (!L.load(argv0) || L.init(device) != PLO_OK) { snprintf(o.msg, sizeof o.msg, "device %d: %s", device, L.last_error ? L.last_error() : "library missing"); return o; }
+            if (!L.load() || L.init(device) != PLO_OK) { snprintf(o.msg, sizeof o.msg, "device %d: %s", device, L.last_error ? L.last_error() : "library missing"); return o; }
             plo_csr_t A{(uint32_t)lM.rowdim(), (uint32_t)lM.coldim(), rp.data(), cc.data(), vv.data()};
             plo_best_t b{}; plo_stats_t st{};
             const int rc = L.cse_search(&A, q, s0, cnt, PLO_COST_SUM_THEN_ADD, &b, &st);
@@ -629,7 +600,7 @@ int run(const F &f, const QMat &MQ, size_t loops, uint64_t seed0, int gpu, bool 
             std::vector<uint32_t> rp, cc, vv; to_csr(lM, rp, cc, vv);
             if (!use_forks) {
                 HipLib L;
-                if (!L.load(argv0) || !L.kernel_search_multi) { ++g_failures; std::cerr << "# \033[1;31mERROR: -K shard failed: libplinopt_hip.so " << (L.cse_search ? "lacks plo_kernel_search_multi" : "cannot be loaded") << "\033[0m" << std::endl; return 2; }
+                if (!L.load() || !L.kernel_search_multi) { ++g_failures; std::cerr << "# \033[1;31mERROR: -K shard failed: libplinopt_hip.so " << (L.cse_search ? "lacks plo_kernel_search_multi" : "cannot be loaded") << "\033[0m" << std::endl; return 2; }
                 std::vector<int> devs((size_t)gpu); for (int r = 0; r < gpu; ++r) devs[(size_t)r] = shard_device(r);
                 plo_csr_t A{(uint32_t)lM.rowdim(), (uint32_t)lM.coldim(), rp.data(), cc.data(), vv.data()};
                 plo_best_t b{}; plo_stats_t st{};
@@ -648,7 +619,7 @@ int run(const F &f, const QMat &MQ, size_t loops, uint64_t seed0, int gpu, bool 
                 ShardOut o{};
                 if (cnt == 0) { o.ok = 1; o.a = o.b = 0xFFFFFFFFu; return o; }
                 HipLib L;
-                if (!L.load(argv0) || !L.kernel_search || L.init(device) != PLO_OK) { snprintf(o.msg, sizeof o.msg, "device %d: %s", device, L.last_error ? L.last_error() : "library missing"); return o; }
+                if (!L.load() || !L.kernel_search || L.init(device) != PLO_OK) { snprintf(o.msg, sizeof o.msg, "device %d: %s", device, L.last_error ? L.last_error() : "library missing"); return o; }
                 plo_csr_t A{(uint32_t)lM.rowdim(), (uint32_t)lM.coldim(), rp.data(), cc.data(), vv.data()};
                 plo_best_t b{}; plo_stats_t st{};
                 const int rc = L.kernel_search(&A, q, s0, cnt, 1u, PLO_COST_SUM_THEN_ADD, nullptr, nullptr, nullptr, &b, &st);
@@ -684,7 +655,7 @@ int run(const F &f, const QMat &MQ, size_t loops, uint64_t seed0, int gpu, bool 
         // every inner dimension from the column count to the row count - 1 (:1437-1439); a square matrix has the identity factorization only
         const size_t id0 = lM.coldim(), id1 = std::max<size_t>(lM.rowdim(), id0 + 1);
         for (size_t id = id0; id < id1; ++id) {
-            try { ab_method(f, lM, seed0, loops, gpu, q, verbose, nbops, text, argv0, id); }
+            try { ab_method(f, lM, seed0, loops, gpu, q, verbose, nbops, text, id); }
             catch (const std::exception &e) { std::clog << "# -A skipped: " << e.what() << std::endl; }
         }
     }
@@ -695,7 +666,7 @@ int run(const F &f, const QMat &MQ, size_t loops, uint64_t seed0, int gpu, bool 
         if constexpr (std::is_same<F, ZpField>::value) if (q != 0 && gpu > 0 && !sharded.done && !d_refused) {
             on_gpu = true;
             HipLib L;
-            if (!L.load(argv0)) return 2;
+            if (!L.load()) return 2;
             if (L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: " << L.last_error() << "\033[0m" << std::endl; return 2; }
             std::vector<uint32_t> rp(1, 0), cc, vv;
             for (auto &r : lM.rows) { for (auto &e : r) { cc.push_back((uint32_t)e.first); vv.push_back((uint32_t)e.second); } rp.push_back((uint32_t)cc.size()); }
@@ -736,7 +707,7 @@ int run(const F &f, const QMat &MQ, size_t loops, uint64_t seed0, int gpu, bool 
         }
     }
     if (tryKernel && !kfi) {                                                          // :1450-1462
-        try { kernel_method(f, lM, seed0, loops, gpu, q, verbose, nbops, text, argv0); }
+        try { kernel_method(f, lM, seed0, loops, gpu, q, verbose, nbops, text); }
         catch (const std::exception &e) { std::clog << "# -K skipped: " << e.what() << std::endl; }
     }
     if (tryKernel && kfi) {
@@ -749,7 +720,7 @@ int run(const F &f, const QMat &MQ, size_t loops, uint64_t seed0, int gpu, bool 
             auto Mx = lM; const size_t m = lM.rowdim();
             for (size_t i = 0; i < lM.coldim(); ++i) { Mx.rows.emplace_back(); Mx.rows.back().emplace_back(i, f.one()); }
             Ops kops{~(size_t)0 >> 1, 0}; std::string ktext;
-            if (kernel_method(f, Mx, seed0, loops, gpu, q, verbose, kops, ktext, argv0) && !ktext.empty()) {
+            if (kernel_method(f, Mx, seed0, loops, gpu, q, verbose, kops, ktext) && !ktext.empty()) {
                 std::istringstream in(ktext);
                 std::vector<compact::Line> Pg = compact::parse(in);
                 auto ren = [](std::string &t) { if (t.size() > 1 && t[0] == 'o' && isdigit((unsigned char)t[1])) t[0] = 'q'; };
@@ -767,15 +738,15 @@ int run(const F &f, const QMat &MQ, size_t loops, uint64_t seed0, int gpu, bool 
         } catch (const std::exception &e) { std::clog << "# -K -F skipped: " << e.what() << std::endl; }
     }
     if (tryLU) {
-        try { lu_method(f, lM, seed0, loops, gpu, q, verbose, nbops, text, argv0); }
+        try { lu_method(f, lM, seed0, loops, gpu, q, verbose, nbops, text); }
         catch (const std::exception &e) { std::clog << "# -G skipped: " << e.what() << std::endl; }
     }
     if (allkernels) {                                                                 // :1463-1465
-        try { allkernels_method(f, lM, seed0, loops, gpu, q, verbose, nbops, text, argv0); }
+        try { allkernels_method(f, lM, seed0, loops, gpu, q, verbose, nbops, text); }
         catch (const std::exception &e) { std::clog << "# -N skipped: " << e.what() << std::endl; }
     }
     if (mostCSE) {                                                                    // :1469-1471
-        try { exhaustive_method(f, lM, std::max<uint64_t>(loops, 1ull << 22), gpu, q, verbose, nbops, text, argv0); }
+        try { exhaustive_method(f, lM, std::max<uint64_t>(loops, 1ull << 22), gpu, q, verbose, nbops, text); }
         catch (const std::exception &e) { std::clog << "# -E skipped: " << e.what() << std::endl; }
     }
 
@@ -846,9 +817,7 @@ int main(int argc, char **argv)
         else if (a == "--only" && i + 1 < argc) { only = argv[++i]; }   // run exactly one method (D, G or A): for tests and timing
         else filename = a;
     }
-#ifdef _OPENMP
-    if (!getenv("OMP_NUM_THREADS")) omp_set_num_threads(std::min(omp_get_max_threads(), 64));   // cgroup-limited boxes report all host cores
-#endif
+    cap_omp_threads();
     if (!only.empty()) { tryDirect = only == "D"; tryLU = only == "G"; tryAB = only == "A"; tryKernel = only == "K"; mostCSE = only == "E"; allkernels = only == "N"; }
     else if (!tryKernel && !tryDirect && !tryLU) tryLU = tryDirect = tryKernel = true;      // src/optimizer.cpp:208-211
     try {
@@ -883,11 +852,11 @@ int main(int argc, char **argv)
             if (q < 3 || q >= (1ull << 62)) { std::cerr << "# ERROR: modulus must be an odd prime below 2^62 in this build" << std::endl; return -1; }
             if (q >= (1ull << 31)) {                       // the kernels keep 31-bit residues: larger moduli run the host loops (the reference's field is Modular<Integer>, src/optimizer.cpp:131)
                 std::clog << "# modulus above 2^31: host loops (the GPU kernels hold 31-bit residues)" << std::endl;
-                return run(Zp64Field(q), MQ, loops, seed0, 0, tryDirect, tryKernel, tryLU, tryAB, mostCSE, allkernels, kfi, verbose, 0, argv[0]);
+                return run(Zp64Field(q), MQ, loops, seed0, 0, tryDirect, tryKernel, tryLU, tryAB, mostCSE, allkernels, kfi, verbose, 0);
             }
-            return run(ZpField((uint32_t)q), MQ, loops, seed0, gpu, tryDirect, tryKernel, tryLU, tryAB, mostCSE, allkernels, kfi, verbose, (uint32_t)q, argv[0]);
+            return run(ZpField((uint32_t)q), MQ, loops, seed0, gpu, tryDirect, tryKernel, tryLU, tryAB, mostCSE, allkernels, kfi, verbose, (uint32_t)q);
         }
-        return run(QField(), MQ, loops, seed0, 0, tryDirect, tryKernel, tryLU, tryAB, mostCSE, allkernels, kfi, verbose, 0, argv[0]);
+        return run(QField(), MQ, loops, seed0, 0, tryDirect, tryKernel, tryLU, tryAB, mostCSE, allkernels, kfi, verbose, 0);
     } catch (const std::exception &e) {
         ++g_failures, std::cerr << "# \033[1;31mERROR: " << e.what() << "\033[0m" << std::endl;
         return -1;

@@ -15,43 +15,18 @@
 // ==========================================================================
 #include "plo_orbit.hpp"
 #include "plo_dl.hpp"
-#include "../../../include/plinopt_hip.h"
 #include <chrono>
 #include <filesystem>
-#include <omp.h>
 
 using namespace plo;
 
 namespace {
 struct HipOrbit {
-    void *h = nullptr;
-    decltype(&plo_init) init = nullptr; decltype(&plo_last_error) last_error = nullptr;
-    decltype(&plo_orbit_plan_create_q) create = nullptr; decltype(&plo_orbit_plan_destroy) destroy = nullptr;
-    decltype(&plo_orbit_search) search = nullptr; decltype(&plo_orbit_search_multi) search_multi = nullptr;
-    bool load() {
-        h = open_hip_lib();
-        if (!h) return false;
-        init = (decltype(init))dlsym(h, "plo_init"); last_error = (decltype(last_error))dlsym(h, "plo_last_error");
-        create = (decltype(create))dlsym(h, "plo_orbit_plan_create_q"); destroy = (decltype(destroy))dlsym(h, "plo_orbit_plan_destroy");
-        search = (decltype(search))dlsym(h, "plo_orbit_search"); search_multi = (decltype(search_multi))dlsym(h, "plo_orbit_search_multi");
-        return init && last_error && create && destroy && search && search_multi;
-    }
+    void *h = open_hip_lib(); bool ok = h != nullptr;
+    PLO_SYM(init, plo_init); PLO_SYM(last_error, plo_last_error);
+    PLO_SYM(create, plo_orbit_plan_create_q); PLO_SYM(destroy, plo_orbit_plan_destroy);
+    PLO_SYM(search, plo_orbit_search); PLO_SYM(search_multi, plo_orbit_search_multi);
 };
-
-// rational CSR for plo_orbit_plan_create_q; wide: a coefficient that does not fit the C-ABI's 64-bit numerators and denominators
-struct QCsr { std::vector<uint32_t> rp{0}, col; std::vector<int64_t> num, den; bool wide = false; };
-QCsr qcsr(const QMat &M) {
-    QCsr c;
-    for (const auto &row : M.rows) {
-        for (const auto &e : row) {
-            c.col.push_back((uint32_t)e.first);
-            if (e.second.n > (__int128)INT64_MAX || e.second.n < -(__int128)INT64_MAX || e.second.d > (__int128)INT64_MAX) c.wide = true;
-            c.num.push_back((int64_t)e.second.n); c.den.push_back((int64_t)e.second.d);
-        }
-        c.rp.push_back((uint32_t)c.col.size());
-    }
-    return c;
-}
 
 struct Opts {
     size_t loops = 100; uint64_t seed0 = 0; int gpu = 1; int measure = ORBIT_DENSITY; bool cse = false;
@@ -111,10 +86,8 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
             refused = cl.wide || cr.wide || cp.wide; why = "a coefficient wider than 64 bits";
             if (!refused) {
                 HipOrbit H;
-                if (!H.load()) { std::cerr << "# \033[1;31mERROR: libplinopt_hip.so cannot be loaded or lacks plo_orbit_search\033[0m\n"; return 2; }   // no silent fallback
-                const plo_qcsr_t l{(uint32_t)QL.rowdim(), (uint32_t)QL.coldim(), cl.rp.data(), cl.col.data(), cl.num.data(), cl.den.data()};
-                const plo_qcsr_t r{(uint32_t)QR.rowdim(), (uint32_t)QR.coldim(), cr.rp.data(), cr.col.data(), cr.num.data(), cr.den.data()};
-                const plo_qcsr_t p{(uint32_t)QP.rowdim(), (uint32_t)QP.coldim(), cp.rp.data(), cp.col.data(), cp.num.data(), cp.den.data()};
+                if (!H.ok) { std::cerr << "# \033[1;31mERROR: libplinopt_hip.so cannot be loaded or lacks plo_orbit_search\033[0m\n"; return 2; }   // no silent fallback
+                const plo_qcsr_t l = cl.view(), r = cr.view(), p = cp.view();
                 plo_orbit_best_t b{}; plo_stats_t st{};
                 int rc;
                 if (o.gpu >= 2) {
@@ -217,9 +190,7 @@ int usage(const char *prg, const Opts &o) {
 } // namespace
 
 int main(int argc, char **argv) {
-#ifdef _OPENMP
-    if (!getenv("OMP_NUM_THREADS")) omp_set_num_threads(std::min(omp_get_max_threads(), 64));   // cgroup-limited boxes report all host cores
-#endif
+    cap_omp_threads();
     Opts o; std::vector<std::string> files;
     auto num = [](const char *s, unsigned __int128 &v) {                                   // a natural number, false above 2^127
         v = 0; if (!*s) return false;

@@ -33,8 +33,18 @@
 #include <tuple>
 #include <utility>
 #include <vector>
+#ifdef _OPENMP
+#include <omp.h>
+#endif
 
 namespace plo {
+
+// first line of a tool's main: at most 64 OpenMP threads unless OMP_NUM_THREADS says otherwise (cgroup-limited boxes report all host cores)
+inline void cap_omp_threads() {
+#ifdef _OPENMP
+    if (!getenv("OMP_NUM_THREADS")) omp_set_num_threads(std::min(omp_get_max_threads(), 64));
+#endif
+}
 
 // ------------------------------------------------------------------ rationals
 // 128-bit numerator and denominator, overflow-checked (round 3; rounds 1-2: 64 bits).  The reference's Givaro::Rational is arbitrary

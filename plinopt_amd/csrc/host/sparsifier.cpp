@@ -10,37 +10,18 @@
 // no silent fallback; --gpu 0 / --host-q keep the host loops.
 // ===========================================================================
 #include "plo_sparsify.hpp"
-#include "../../../include/plinopt_hip.h"
+#include "plo_dl.hpp"
 
 #include <chrono>
-#include <dlfcn.h>
-#include <omp.h>
-#include <libgen.h>
-#include <unistd.h>
 
 using namespace plo;
 
 namespace {
 
 struct HipCob {
-    void *h = nullptr;
-    decltype(&plo_init) init = nullptr;
-    decltype(&plo_last_error) last_error = nullptr;
-    decltype(&plo_cob_search) cob_search = nullptr;
-    decltype(&plo_cob_search_batch) cob_search_batch = nullptr;
-    bool load() {
-        std::vector<std::string> cand;
-        for (const char *v : {"PLO_HIP_LIB", "PLINOPT_HIP_LIB"}) if (const char *e = getenv(v)) cand.emplace_back(e);   // (one name for the tools and plinopt_amd/capi.py; the older one still works)
-        char buf[4096]; ssize_t k = readlink("/proc/self/exe", buf, sizeof buf - 1);
-        if (k > 0) { buf[k] = 0; std::string d = dirname(buf); cand.push_back(d + "/../plinopt_amd/libplinopt_hip.so"); cand.push_back(d + "/libplinopt_hip.so"); }
-        cand.emplace_back("libplinopt_hip.so");
-        for (auto &c : cand) { h = dlopen(c.c_str(), RTLD_NOW | RTLD_GLOBAL); if (h) break; }
-        if (!h) { std::cerr << "# \033[1;31mERROR: cannot load libplinopt_hip.so: " << dlerror() << "\033[0m\n"; return false; }
-        init = (decltype(init))dlsym(h, "plo_init"); last_error = (decltype(last_error))dlsym(h, "plo_last_error");
-        cob_search = (decltype(cob_search))dlsym(h, "plo_cob_search");
-        cob_search_batch = (decltype(cob_search_batch))dlsym(h, "plo_cob_search_batch");
-        return init && last_error && cob_search;
-    }
+    void *h = open_hip_lib(); bool ok = h != nullptr;
+    PLO_SYM(init, plo_init); PLO_SYM(last_error, plo_last_error);
+    PLO_SYM(cob_search, plo_cob_search); PLO_SYM_OPT(cob_search_batch, plo_cob_search_batch);
 };
 
 // An enumeration of fewer candidate rows than this is walked on the host even with --gpu 1: the (block, row) enumerations of a run
@@ -206,7 +187,7 @@ template <class F> int tsparsifier(const F &f, const SparseMat<typename F::Elt> 
 
 int main(int argc, char **argv)
 {
-    if (!getenv("OMP_NUM_THREADS")) omp_set_num_threads(std::min(omp_get_max_threads(), 64));   // cgroup-limited boxes report all host cores
+    cap_omp_threads();
     Fmt fmt = PRETTY; std::string filename; size_t maxnumcoeff = 11, blocksize = 4; bool initialElimination = true; uint64_t q = 0; int gpu = 1; bool gpu_q = true;
     for (int i = 1; i < argc; ++i) {
         std::string a(argv[i]);
@@ -247,7 +228,7 @@ int main(int argc, char **argv)
             ZpField f((uint32_t)q);
             if (gpu > 0) {
                 HipCob L;
-                if (!L.load() || L.init(0) != PLO_OK) { std::cerr << "# \033[1;31mERROR: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return 2; }
+                if (!L.ok || L.init(0) != PLO_OK) { std::cerr << "# \033[1;31mERROR: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return 2; }
                 CobGpuBackend B(L);
                 int rc = tsparsifier(f, rebind(MQ, f), B, fmt, blocksize, maxnumcoeff, initialElimination);
                 std::clog << "# GPU: " << B.launches << " launches, enumeration kernels " << B.kernel_ms << " ms, " << (B.kernel_ms > 0 ? B.candidates / (B.kernel_ms * 1e-3) : 0.0) << " candidate rows/s"
@@ -261,7 +242,7 @@ int main(int argc, char **argv)
         if (gpu > 0 && gpu_q) {
             // over the rationals, as the reference runs it (src/sparsifier.cpp:66-83): the enumeration on the GPU modulo two primes, winners checked over Q
             HipCob L;
-            if (!L.load() || L.init(0) != PLO_OK) { std::cerr << "# \033[1;31mERROR: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return 2; }
+            if (!L.ok || L.init(0) != PLO_OK) { std::cerr << "# \033[1;31mERROR: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return 2; }
             CobGpuQBackend B(L);
             int rc = tsparsifier(f, rebind(MQ, f), B, fmt, blocksize, maxnumcoeff, initialElimination);
             std::clog << "# GPU (Q, two 31-bit primes + check over Q): " << B.gpu_calls << " enumerations in " << B.launches << " launches (both moduli of an enumeration in one), kernels " << B.kernel_ms << " ms, " << B.fallbacks << " on the host; "

@@ -11,7 +11,6 @@
 // ==========================================================================
 #include "plo_inplace.hpp"
 #include "plo_dl.hpp"
-#include "../../../include/plinopt_hip.h"
 #include <unistd.h>
 #include <chrono>
 #include <fstream>
@@ -22,45 +21,23 @@ using namespace plo;
 
 namespace {
 struct HipTril {
-    void *h = nullptr;
-    decltype(&plo_init) init = nullptr; decltype(&plo_last_error) last_error = nullptr;
-    decltype(&plo_tril_plan_create_q) create = nullptr; decltype(&plo_tril_plan_destroy) destroy = nullptr; decltype(&plo_tril_search) search = nullptr;
-    decltype(&plo_tril_search_multi) search_multi = nullptr;
-    bool load() {
-        h = open_hip_lib();
-        if (!h) return false;
-        init = (decltype(init))dlsym(h, "plo_init"); last_error = (decltype(last_error))dlsym(h, "plo_last_error");
-        create = (decltype(create))dlsym(h, "plo_tril_plan_create_q"); destroy = (decltype(destroy))dlsym(h, "plo_tril_plan_destroy");
-        search = (decltype(search))dlsym(h, "plo_tril_search"); search_multi = (decltype(search_multi))dlsym(h, "plo_tril_search_multi");
-        return init && last_error && create && destroy && search;
-    }
+    void *h = open_hip_lib(); bool ok = h != nullptr;
+    PLO_SYM(init, plo_init); PLO_SYM(last_error, plo_last_error);
+    PLO_SYM(create, plo_tril_plan_create_q); PLO_SYM(destroy, plo_tril_plan_destroy);
+    PLO_SYM(search, plo_tril_search); PLO_SYM_OPT(search_multi, plo_tril_search_multi);
 };
 
 bool better(const Tricount &l, const Tricount &r) { return l[0] < r[0] || (l[0] == r[0] && l[1] < r[1]); }   // :893-897
 
-// rational CSR for plo_tril_plan_create_q (round 3: the device programs carry the coefficients modulo a 31-bit prime)
-struct ICsr { std::vector<uint32_t> rp{0}, col; std::vector<int64_t> num, den; bool unit = true, full = true; };
-ICsr icsr(const QMat &M) {
-    ICsr c;
-    for (const auto &row : M.rows) {
-        if (row.empty() || row.size() > 64) c.full = false;
-        for (const auto &e : row) {
-            c.col.push_back((uint32_t)e.first);
-            if (!(e.second.d == 1 && (e.second.n == 1 || e.second.n == -1))) c.unit = false;
-            // (Rat is 128 bits wide; the C-ABI takes 64-bit numerators and denominators: a wider coefficient keeps the matrix on the host)
-            if (e.second.n > (__int128)INT64_MAX || e.second.n < -(__int128)INT64_MAX || e.second.d > (__int128)INT64_MAX || e.second.d < -(__int128)INT64_MAX) c.full = false;
-            c.num.push_back((int64_t)e.second.n); c.den.push_back((int64_t)e.second.d);
-        }
-        c.rp.push_back((uint32_t)c.col.size());
-    }
-    return c;
+// what the device takes (plo_tril_plan_create_q; -e included): coefficients that fit 64 bits, no empty row, rows of at most 64 entries
+bool full(const QCsr &c) {
+    for (size_t i = 0; i + 1 < c.rp.size(); ++i) if (c.rp[i + 1] == c.rp[i] || c.rp[i + 1] - c.rp[i] > 64) return false;
+    return !c.wide;
 }
 } // namespace
 
 int main(int argc, char **argv) {
-#ifdef _OPENMP
-    if (!getenv("OMP_NUM_THREADS")) omp_set_num_threads(std::min(omp_get_max_threads(), 64));   // cgroup-limited boxes report all host cores
-#endif
+    cap_omp_threads();
     size_t loops = 30; uint64_t seed0 = 0; int gpu = 1; bool expanded = false, fork_shards = false; std::vector<std::string> files;
     for (int i = 1; i < argc; ++i) {
         std::string a(argv[i]);
@@ -85,18 +62,15 @@ int main(int argc, char **argv) {
         std::clog << "# Oriented number of operations: " << best[0] << '|' << best[1] << '|' << best[2] << std::endl;
         bool on_gpu = false; double kms = 0;
         if (loops > 0) {
-            ICsr ca = icsr(A), cb = icsr(B), ct = icsr(T);
-            // device path: no empty row, rows of at most 64 entries, coefficients that fit 64 bits (-e included: round 4)
-            const bool device_ok = ca.full && cb.full && ct.full;
+            const QCsr ca = qcsr(A), cb = qcsr(B), ct = qcsr(T);
+            const plo_qcsr_t a = ca.view(), b = cb.view(), t = ct.view();
+            const bool device_ok = full(ca) && full(cb) && full(ct);
             using Key = std::tuple<size_t, size_t, uint64_t, int>;      // (ADD, SCA, seed, variant): the order of :893-897 made total
             // restarts s0 .. s0+cnt-1 on one device (plo_tril_search); throws on failure
             auto gpu_search = [&](int device, uint64_t s0, uint64_t cnt, plo_tril_best_t &r, plo_stats_t &st) {
                 HipTril L;
-                if (!L.load()) throw std::runtime_error("cannot load libplinopt_hip.so");        // no silent fallback: --gpu 0 selects the host loop
+                if (!L.ok) throw std::runtime_error("cannot load libplinopt_hip.so");        // no silent fallback: --gpu 0 selects the host loop
                 if (L.init(device) != PLO_OK) throw std::runtime_error(L.last_error());
-                plo_qcsr_t a{(uint32_t)A.rowdim(), (uint32_t)A.coldim(), ca.rp.data(), ca.col.data(), ca.num.data(), ca.den.data()};
-                plo_qcsr_t b{(uint32_t)B.rowdim(), (uint32_t)B.coldim(), cb.rp.data(), cb.col.data(), cb.num.data(), cb.den.data()};
-                plo_qcsr_t t{(uint32_t)T.rowdim(), (uint32_t)T.coldim(), ct.rp.data(), ct.col.data(), ct.num.data(), ct.den.data()};
                 plo_tril_plan_t *plan = nullptr;
                 if (L.create(&a, &b, &t, expanded ? 1 : 0, &plan) != PLO_OK) throw std::runtime_error(L.last_error());
                 const int rc = L.search(plan, s0, cnt, &r, &st);
@@ -126,10 +100,7 @@ int main(int argc, char **argv) {
                     // --gpu N (BASELINE configs[3]): N contiguous seed shards over N devices from THIS process -- one host thread, one
                     // device and one plan per shard inside the library, the minimum under Key by RCCL MIN all-reduces (plo_tril_search_multi)
                     HipTril L;
-                    if (!L.load() || !L.search_multi) throw std::runtime_error("libplinopt_hip.so cannot be loaded or lacks plo_tril_search_multi");
-                    plo_qcsr_t a{(uint32_t)A.rowdim(), (uint32_t)A.coldim(), ca.rp.data(), ca.col.data(), ca.num.data(), ca.den.data()};
-                    plo_qcsr_t b{(uint32_t)B.rowdim(), (uint32_t)B.coldim(), cb.rp.data(), cb.col.data(), cb.num.data(), cb.den.data()};
-                    plo_qcsr_t t{(uint32_t)T.rowdim(), (uint32_t)T.coldim(), ct.rp.data(), ct.col.data(), ct.num.data(), ct.den.data()};
+                    if (!L.ok || !L.search_multi) throw std::runtime_error("libplinopt_hip.so cannot be loaded or lacks plo_tril_search_multi");
                     std::vector<int> devs((size_t)gpu); for (int r = 0; r < gpu; ++r) devs[(size_t)r] = shard_device(r);
                     plo_tril_best_t r{}; plo_stats_t st{};
                     if (L.search_multi(&a, &b, &t, expanded ? 1 : 0, seed0, loops, gpu, devs.data(), &r, &st) != PLO_OK) throw std::runtime_error(L.last_error());

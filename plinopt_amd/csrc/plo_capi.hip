@@ -1117,10 +1117,10 @@ int multi_run(int ndev, const int *devices, uint64_t seed0, uint64_t nseeds, std
     return PLO_OK;
 }
 
-// The minimum of the shards' words: on the host, and -- with two or more DISTINCT devices (PLO_MULTI_REDUCE=rccl: also for one;
-// =host: never) -- by rccl_min_pair over the devices.  The all-reduce result is the one used; the host minimum is its check, and
-// a difference is a diagnostic on stderr with the host minimum kept (never an error: the host value is right by construction).
-// Returns the winning shard (-1: no shard has a candidate); agg gets the summed statistics, `reduce` and the all-reduce time.
+// The minimum of the shards' words, taken on the host: that is the result.  With two or more DISTINCT devices (PLO_MULTI_REDUCE=rccl:
+// also for one; =host: never) rccl_min_pair over the devices cross-checks it; a difference is a diagnostic on stderr and clears
+// agg.reduce (never an error: the host value is right by construction).
+// `winner` gets the winning shard (-1: no shard has a candidate); agg the summed statistics, `reduce` and the all-reduce time.
 int multi_min(const std::vector<MultiShard> &sh, int ndev, const int *devices, plo_stats_t &agg, int &winner)
 {
     winner = -1;
@@ -1192,18 +1192,13 @@ int sharded_search(uint64_t seed0, uint64_t nseeds, int ndev, const int *devices
     if (stats) *stats = agg;
     return PLO_OK;
 }
-} // namespace
 
-extern "C" {
-
-uint64_t plo_multi_comm_inits(void) { return g_comm_inits; }
-
-int plo_cse_search_multi(const plo_csr_t *A, uint32_t p, uint64_t seed0, uint64_t nseeds, int cost_mode, int ndev, const int *devices,
-                         plo_best_t *out, plo_stats_t *stats)
+// The same for the searches without a plan (plo_cse_search_multi, plo_kernel_search_multi): shard(first seed, count, best, stats) is
+// the single-device entry on a shard's block; the winner is the minimum under (cmpOpCount key of `cost_mode`, seed).  No candidate
+// at all is no error here: *out then holds all ones.
+template <class Shard>
+int planless_search_multi(uint64_t seed0, uint64_t nseeds, int cost_mode, int ndev, const int *devices, plo_best_t *out, plo_stats_t *stats, Shard shard)
 {
-    if (!A || !out) return fail(PLO_E_ARG, "null argument");
-    if (ndev < 1 || ndev > 64) return fail(PLO_E_ARG, "device count outside [1,64]");
-    if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
     DeviceGuard guard;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<MultiShard> sh; std::vector<plo_best_t> bests((size_t)ndev);
@@ -1211,7 +1206,7 @@ int plo_cse_search_multi(const plo_csr_t *A, uint32_t p, uint64_t seed0, uint64_
         switch (cost_mode) { case PLO_COST_ADD_THEN_MUL: return ((unsigned long long)b.adds << 32) | b.muls; case PLO_COST_SUM: return ((unsigned long long)b.adds + b.muls) << 32; default: return (((unsigned long long)b.adds + b.muls) << 32) | b.adds; } };
     int rc = multi_run(ndev, devices, seed0, nseeds, sh, [&](MultiShard &S, int) {
         plo_best_t &b = bests[(size_t)(&S - sh.data())];
-        const int r_ = plo_cse_search(A, p, S.s0, S.cnt, cost_mode, &b, &S.st);
+        const int r_ = shard(S.s0, S.cnt, &b, &S.st);
         if (r_ == PLO_OK && b.seed != ~0ull) { S.hi = key(b); S.lo = b.seed - seed0; }
         return r_;
     });
@@ -1224,6 +1219,21 @@ int plo_cse_search_multi(const plo_csr_t *A, uint32_t p, uint64_t seed0, uint64_
     agg.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = agg;
     return PLO_OK;
+}
+} // namespace
+
+extern "C" {
+
+uint64_t plo_multi_comm_inits(void) { return g_comm_inits; }
+
+int plo_cse_search_multi(const plo_csr_t *A, uint32_t p, uint64_t seed0, uint64_t nseeds, int cost_mode, int ndev, const int *devices,
+                         plo_best_t *out, plo_stats_t *stats)
+{
+    if (!A || !out) return fail(PLO_E_ARG, "null argument");
+    if (ndev < 1 || ndev > 64) return fail(PLO_E_ARG, "device count outside [1,64]");
+    if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
+    return planless_search_multi(seed0, nseeds, cost_mode, ndev, devices, out, stats,
+        [&](uint64_t s0, uint64_t cnt, plo_best_t *b, plo_stats_t *st) { return plo_cse_search(A, p, s0, cnt, cost_mode, b, st); });
 }
 
 int plo_cse_chain_destroy(plo_chain_t *ch)
@@ -1804,13 +1814,15 @@ int plo_cob_search_range(uint32_t n, uint32_t m, const uint32_t *TM, const uint3
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------- trilplacer
-struct plo_tril_plan {
-    plo::TrilPlan P{};
+// what the plans of the atom kernels (trilplacer, inplacer) share
+struct AtomsPlan {
     void *d_img = nullptr; uint32_t *d_err = nullptr; unsigned long long *d_best = nullptr;
     uint32_t waves_per_wg = 4, lds_bytes = 0, blocks_per_cu = 1;
     uint64_t algo_bytes = 0;
-    bool rational = false;           // coefficients other than +-1: residues modulo a 31-bit prime, tril_kernel<true>
+    bool rational = false;           // coefficients other than +-1: residues modulo a 31-bit prime (PLO_TRIL_PRIME), the kernel's <true> instantiation
 };
+struct plo_tril_plan : AtomsPlan { plo::TrilPlan P{}; };
+struct plo_lin_plan : AtomsPlan { plo::LinPlan P{}; };
 
 namespace {
 // One timed launch of a search kernel (trilplacer, inplacer, orbiter) and its statistics
@@ -1864,15 +1876,110 @@ int tril_launch(plo_tril_plan *pl, plo::TrilJob J, plo_stats_t *st) {
 #endif
     return rc;
 }
+int lin_launch(plo_lin_plan *pl, plo::TrilJob J, plo_stats_t *st) {
+    return atoms_launch(pl, pl->rational ? plo::lin_kernel<true> : plo::lin_kernel<false>, "inplacer", J, st);
+}
+
+template <class Plan> void atoms_destroy(Plan *pl) {
+    if (!pl) return;
+    if (pl->d_img) (void)hipFree(pl->d_img);
+    if (pl->d_err) (void)hipFree(pl->d_err);
+    if (pl->d_best) (void)hipFree(pl->d_best);
+    delete pl;
+}
+
+// ---- the plo::TrilMat image of a rational CSR matrix.  Entries num/den: all +-1 gives the unit kernel (small signed values);
+// otherwise the residues modulo PLO_TRIL_PRIME and the rational instantiation of the kernel (plo_tril.hip, plo_lin.hip).
+#define PLO_TRIL_PRIME 2147483629u
+// the rows of M as the device takes them, or the refusal; `unit` is cleared by an entry other than +-1
+int trilmat_check(const plo_qcsr_t *M, bool empty_row_ok, bool &unit) {
+    for (uint32_t i = 0; i < M->m; ++i) {
+        const uint32_t len = M->rowptr[i + 1] - M->rowptr[i];
+        if (len == 0 && !empty_row_ok) return fail(PLO_E_UNSUPPORTED, "empty row: host path only");
+        if (len > 64) return fail(PLO_E_UNSUPPORTED, "row with more than 64 entries: host path only");
+        for (uint32_t e = M->rowptr[i]; e < M->rowptr[i + 1]; ++e) {
+            const int64_t nu = M->num[e], de = M->den ? M->den[e] : 1;
+            if (nu == 0 || de == 0) return fail(PLO_E_ARG, "zero entry or zero denominator");
+            if (!(de == 1 && (nu == 1 || nu == -1))) unit = false;
+            if (de % (int64_t)PLO_TRIL_PRIME == 0 || nu % (int64_t)PLO_TRIL_PRIME == 0) return fail(PLO_E_UNSUPPORTED, "entry not a unit modulo the device's prime: host path only");
+            if (M->col[e] >= M->n || (e > M->rowptr[i] && M->col[e] <= M->col[e - 1])) return fail(PLO_E_ARG, "columns must be sorted and in range");
+        }
+    }
+    return PLO_OK;
+}
+// bytes of its image: rp, col, val, valp, each rounded to 16
+size_t trilmat_bytes(const plo_qcsr_t *M) {
+    const uint32_t nnz = M->rowptr[M->m];
+    return round_up((M->m + 1) * 2, 16) + round_up(nnz * 2, 16) + round_up(nnz, 16) + round_up(nnz * 4, 16);
+}
+// writes that image at img + off (and advances off); D gets the shape and the pointers into the device copy at d_img
+void trilmat_fill(const plo_qcsr_t *M, bool unit, uint8_t *img, const void *d_img, size_t &off, plo::TrilMat &D) {
+    const uint32_t nnz = M->rowptr[M->m];
+    D.m = M->m; D.n = M->n; D.nnz = nnz;
+    uint16_t *rp = (uint16_t *)(img + off); D.rp = (const uint16_t *)((const uint8_t *)d_img + off); off += round_up((M->m + 1) * 2, 16);
+    uint16_t *cl = (uint16_t *)(img + off); D.col = (const uint16_t *)((const uint8_t *)d_img + off); off += round_up(nnz * 2, 16);
+    int8_t *vl = (int8_t *)(img + off); D.val = (const int8_t *)((const uint8_t *)d_img + off); off += round_up(nnz, 16);
+    uint32_t *vp = (uint32_t *)(img + off); D.valp = (const uint32_t *)((const uint8_t *)d_img + off); off += round_up(nnz * 4, 16);
+    for (uint32_t i = 0; i <= M->m; ++i) rp[i] = (uint16_t)M->rowptr[i];
+    for (uint32_t e = 0; e < nnz; ++e) {
+        cl[e] = (uint16_t)M->col[e];
+        const int64_t nu = M->num[e], de = M->den ? M->den[e] : 1;
+        vl[e] = unit ? (int8_t)nu : 0;
+        int64_t a = nu % (int64_t)PLO_TRIL_PRIME, d = de % (int64_t)PLO_TRIL_PRIME; if (a < 0) a += PLO_TRIL_PRIME; if (d < 0) d += PLO_TRIL_PRIME;
+        vp[e] = (uint32_t)((uint64_t)a * inv_mod((uint32_t)d, PLO_TRIL_PRIME) % PLO_TRIL_PRIME);
+    }
+}
+
+// workgroups of `waves` waves and `lds` bytes that the 160 KiB of LDS and the 32 waves of a CU admit
+uint32_t blocks_per_cu(uint32_t waves, uint32_t lds) { return std::max<uint32_t>(1, std::min<uint32_t>(32u / waves, (uint32_t)(g_lds_max / lds))); }
+
+// A new plan with the device buffer of an image of `bytes` bytes (the TrilMat pointers point into it before it is filled), or null
+template <class Plan> Plan *atoms_new(size_t bytes, bool unit) {
+    Plan *pl = new Plan();
+    pl->rational = !unit;
+    if (hipMalloc(&pl->d_img, bytes) != hipSuccess) { delete pl; fail(PLO_E_HIP, "hipMalloc"); return nullptr; }
+    return pl;
+}
+
+// The end of both create functions: four waves (256 threads) per workgroup, one when four do not fit 64 KiB, as many workgroups per CU
+// as LDS and waves admit; then the image, the error and best words and the kernel's dynamic-LDS limit.  A failure destroys the plan.
+template <class Plan> int atoms_finish(Plan *pl, uint32_t lds_per_wave, const std::vector<uint8_t> &img, const void *kernel, const char *tool, Plan **plan) {
+    pl->waves_per_wg = 4;
+    pl->lds_bytes = lds_per_wave * pl->waves_per_wg;
+    if (pl->lds_bytes > 64u * 1024u) { pl->waves_per_wg = 1; pl->lds_bytes = lds_per_wave; }
+    if (pl->lds_bytes > g_lds_max) { atoms_destroy(pl); return fail(PLO_E_CAPACITY, "program does not fit LDS"); }
+    pl->blocks_per_cu = blocks_per_cu(pl->waves_per_wg, pl->lds_bytes);
+    if (hipMemcpy(pl->d_img, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess || hipMalloc((void **)&pl->d_err, 4) != hipSuccess ||
+        hipMalloc((void **)&pl->d_best, 8) != hipSuccess || hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes) != hipSuccess) {
+        atoms_destroy(pl); return fail(PLO_E_HIP, std::string("device setup of the ") + tool + " plan failed");
+    }
+    *plan = pl;
+    return PLO_OK;
+}
+
+// Body of plo_tril_search and plo_lin_search: *w gets the packed word of the best candidate, (ADD << 48 | SCA << 32 | (seed - seed0) << 1 | variant)
+template <class Plan> int atoms_search(Plan *pl, const void *best, int (*launch)(Plan *, plo::TrilJob, plo_stats_t *), uint64_t seed0, uint64_t nseeds, unsigned long long *w, plo_stats_t *stats) {
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!pl || !best) return fail(PLO_E_ARG, "null argument");
+    if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
+    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
+    const auto t0 = std::chrono::steady_clock::now();
+    const unsigned long long init = ~0ull;
+    HIPCHK(hipMemcpy(pl->d_best, &init, 8, hipMemcpyHostToDevice));
+    plo::TrilJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.ops = nullptr; J.best = pl->d_best;
+    int rc = launch(pl, J, st);
+    if (rc != PLO_OK) return rc;
+    HIPCHK(hipMemcpy(w, pl->d_best, 8, hipMemcpyDeviceToHost));
+    if (*w == init) return fail(PLO_E_INTERNAL, "no candidate reported");
+    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return PLO_OK;
+}
 } // namespace
 
 extern "C" {
 
 int plo_tril_plan_create(const plo_icsr_t *A, const plo_icsr_t *B, const plo_icsr_t *T, plo_tril_plan_t **plan) { return plo_tril_plan_create_x(A, B, T, 0, plan); }
 
-// Common builder: entries as rationals num/den.  All entries +-1: the unit kernel (small signed values); otherwise the residues
-// modulo PLO_TRIL_PRIME and the rational instantiation of the kernel (plo_tril.hip).
-#define PLO_TRIL_PRIME 2147483629u
 int plo_tril_plan_create_q(const plo_qcsr_t *A, const plo_qcsr_t *B, const plo_qcsr_t *T, int expanded, plo_tril_plan_t **plan)
 {
     if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
@@ -1885,62 +1992,23 @@ int plo_tril_plan_create_q(const plo_qcsr_t *A, const plo_qcsr_t *B, const plo_q
         if (!M->rowptr || !M->col || !M->num || M->n == 0 || M->n > 16382u) return fail(PLO_E_ARG, "bad matrix (at most 16382 variables)");
         const uint32_t nnz = M->rowptr[M->m];
         if (nnz > 65535u) return fail(PLO_E_CAPACITY, "more than 65535 non-zeros");
-        for (uint32_t i = 0; i < M->m; ++i) {
-            const uint32_t len = M->rowptr[i + 1] - M->rowptr[i];
-            if (len == 0) return fail(PLO_E_UNSUPPORTED, "empty row: host path only");
-            if (len > 64) return fail(PLO_E_UNSUPPORTED, "row with more than 64 entries: host path only");
-            for (uint32_t e = M->rowptr[i]; e < M->rowptr[i + 1]; ++e) {
-                const int64_t nu = M->num[e], de = M->den ? M->den[e] : 1;
-                if (nu == 0 || de == 0) return fail(PLO_E_ARG, "zero entry or zero denominator");
-                if (!(de == 1 && (nu == 1 || nu == -1))) unit = false;
-                if (de % (int64_t)PLO_TRIL_PRIME == 0 || nu % (int64_t)PLO_TRIL_PRIME == 0) return fail(PLO_E_UNSUPPORTED, "entry not a unit modulo the device's prime: host path only");
-                if (M->col[e] >= M->n || (e > M->rowptr[i] && M->col[e] <= M->col[e - 1])) return fail(PLO_E_ARG, "columns must be sorted and in range");
-            }
-        }
+        if (const int rc = trilmat_check(M, false, unit)) return rc;
         cap = std::max(cap, 2u * nnz + 3u * M->m);
         if (expanded && M == T) cap = std::max(cap, 4u * nnz + 6u * M->m);        // TransposedDoubleAlgorithm: 4(len-1)+2 atoms per row, and 4 scaling atoms when the pivot is not +-1
         if (expanded && M == T && M->n >= 16382u) return fail(PLO_E_CAPACITY, "one more variable of c than the atom holds");
-        bytes += round_up((M->m + 1) * 2, 16) + round_up(nnz * 2, 16) + round_up(nnz, 16) + round_up(nnz * 4, 16);
+        bytes += trilmat_bytes(M);
         algo += 2ull * (M->m + 1) + 3ull * nnz;                 // the CSR image of the three matrices, once per candidate
     }
     cap = round_up(cap + 2, 64);
-    plo_tril_plan *pl = new plo_tril_plan();
-    pl->rational = !unit;
+    plo_tril_plan *pl = atoms_new<plo_tril_plan>(bytes, unit);
+    if (!pl) return PLO_E_HIP;
     std::vector<uint8_t> img(bytes, 0);
-    if (hipMalloc(&pl->d_img, bytes) != hipSuccess) { delete pl; return fail(PLO_E_HIP, "hipMalloc"); }
     size_t off = 0;
-    for (int w = 0; w < 3; ++w) {
-        const plo_qcsr_t *M = Ms[w]; const uint32_t nnz = M->rowptr[M->m];
-        plo::TrilMat &D = pl->P.M[w];
-        D.m = M->m; D.n = M->n; D.nnz = nnz;
-        uint16_t *rp = (uint16_t *)(img.data() + off); D.rp = (const uint16_t *)((uint8_t *)pl->d_img + off); off += round_up((M->m + 1) * 2, 16);
-        uint16_t *cl = (uint16_t *)(img.data() + off); D.col = (const uint16_t *)((uint8_t *)pl->d_img + off); off += round_up(nnz * 2, 16);
-        int8_t *vl = (int8_t *)(img.data() + off); D.val = (const int8_t *)((uint8_t *)pl->d_img + off); off += round_up(nnz, 16);
-        uint32_t *vp = (uint32_t *)(img.data() + off); D.valp = (const uint32_t *)((uint8_t *)pl->d_img + off); off += round_up(nnz * 4, 16);
-        for (uint32_t i = 0; i <= M->m; ++i) rp[i] = (uint16_t)M->rowptr[i];
-        for (uint32_t e = 0; e < nnz; ++e) {
-            cl[e] = (uint16_t)M->col[e];
-            const int64_t nu = M->num[e], de = M->den ? M->den[e] : 1;
-            vl[e] = unit ? (int8_t)nu : 0;
-            int64_t a = nu % (int64_t)PLO_TRIL_PRIME, d = de % (int64_t)PLO_TRIL_PRIME; if (a < 0) a += PLO_TRIL_PRIME; if (d < 0) d += PLO_TRIL_PRIME;
-            vp[e] = (uint32_t)((uint64_t)a * inv_mod((uint32_t)d, PLO_TRIL_PRIME) % PLO_TRIL_PRIME);
-        }
-    }
+    for (int w = 0; w < 3; ++w) trilmat_fill(Ms[w], unit, img.data(), pl->d_img, off, pl->P.M[w]);
     pl->P.cap = cap; pl->P.expanded = expanded ? 1u : 0u; pl->P.p = unit ? 0u : PLO_TRIL_PRIME;
     pl->P.lds_per_wave = round_up(8u * cap + 2u * ((A->m + 1u) & ~1u) + A->m, 16) + 16u * ((cap + 63u) / 64u);   // atoms, permutation, signs; masks of a pushvariables pass
     pl->algo_bytes = algo;
-    pl->waves_per_wg = 4;
-    pl->lds_bytes = pl->P.lds_per_wave * pl->waves_per_wg;
-    if (pl->lds_bytes > 64u * 1024u) { pl->waves_per_wg = 1; pl->lds_bytes = pl->P.lds_per_wave; }
-    if (pl->lds_bytes > g_lds_max) { (void)hipFree(pl->d_img); delete pl; return fail(PLO_E_CAPACITY, "program does not fit LDS"); }
-    pl->blocks_per_cu = std::max<uint32_t>(1, std::min<uint32_t>(32u / pl->waves_per_wg, (uint32_t)(g_lds_max / pl->lds_bytes)));
-    const void *fn = pl->rational ? (const void *)plo::tril_kernel<true> : (const void *)plo::tril_kernel<false>;
-    if (hipMemcpy(pl->d_img, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess || hipMalloc((void **)&pl->d_err, 4) != hipSuccess ||
-        hipMalloc((void **)&pl->d_best, 8) != hipSuccess || hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes) != hipSuccess) {
-        plo_tril_plan_destroy(pl); return fail(PLO_E_HIP, "device setup of the trilplacer plan failed");
-    }
-    *plan = pl;
-    return PLO_OK;
+    return atoms_finish(pl, pl->P.lds_per_wave, img, pl->rational ? (const void *)plo::tril_kernel<true> : (const void *)plo::tril_kernel<false>, "trilplacer", plan);
 }
 
 // integer entries (the interface of rounds 1-2): the same builder with denominators 1
@@ -1958,14 +2026,7 @@ int plo_tril_plan_create_x(const plo_icsr_t *A, const plo_icsr_t *B, const plo_i
     return plo_tril_plan_create_q(&Q[0], &Q[1], &Q[2], expanded, plan);
 }
 
-void plo_tril_plan_destroy(plo_tril_plan_t *pl)
-{
-    if (!pl) return;
-    if (pl->d_img) (void)hipFree(pl->d_img);
-    if (pl->d_err) (void)hipFree(pl->d_err);
-    if (pl->d_best) (void)hipFree(pl->d_best);
-    delete pl;
-}
+void plo_tril_plan_destroy(plo_tril_plan_t *pl) { atoms_destroy(pl); }
 
 int plo_tril_cost_many(plo_tril_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats)
 {
@@ -1977,21 +2038,10 @@ int plo_tril_cost_many(plo_tril_plan_t *pl, const uint64_t *seeds, uint64_t seed
 
 int plo_tril_search(plo_tril_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_tril_best_t *best, plo_stats_t *stats)
 {
-    if (!pl || !best) return fail(PLO_E_ARG, "null argument");
-    if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
-    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
-    const unsigned long long init = ~0ull;
-    HIPCHK(hipMemcpy(pl->d_best, &init, 8, hipMemcpyHostToDevice));
-    plo::TrilJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.ops = nullptr; J.best = pl->d_best;
-    int rc = tril_launch(pl, J, st);
-    if (rc != PLO_OK) return rc;
     unsigned long long w = 0;
-    HIPCHK(hipMemcpy(&w, pl->d_best, 8, hipMemcpyDeviceToHost));
-    if (w == init) return fail(PLO_E_INTERNAL, "no candidate reported");
+    if (const int rc = atoms_search(pl, best, tril_launch, seed0, nseeds, &w, stats)) return rc;
     best->add = (uint32_t)(w >> 48); best->sca = (uint32_t)(w >> 32) & 0xFFFFu; best->mul = pl->P.M[0].m;
     best->variant = (uint32_t)(w & 1ull); best->seed = seed0 + ((w & 0xFFFFFFFFull) >> 1);
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return PLO_OK;
 }
 
@@ -2002,26 +2052,8 @@ int plo_kernel_search_multi(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint
     if (ndev < 1 || ndev > 64) return fail(PLO_E_ARG, "device count outside [1,64]");
     if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
     if (per_block != 1u && ndev > 1) return fail(PLO_E_ARG, "shards of the kernel method take one decomposition per restart (per_block = 1)");
-    DeviceGuard guard;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<MultiShard> sh; std::vector<plo_best_t> bests((size_t)ndev);
-    auto key = [&](const plo_best_t &b) -> unsigned long long {
-        switch (cost_mode) { case PLO_COST_ADD_THEN_MUL: return ((unsigned long long)b.adds << 32) | b.muls; case PLO_COST_SUM: return ((unsigned long long)b.adds + b.muls) << 32; default: return (((unsigned long long)b.adds + b.muls) << 32) | b.adds; } };
-    int rc = multi_run(ndev, devices, seed0, nrestarts, sh, [&](MultiShard &S, int) {
-        plo_best_t &b = bests[(size_t)(&S - sh.data())];
-        const int r_ = plo_kernel_search(M, p, S.s0, S.cnt, per_block, cost_mode, nullptr, nullptr, nullptr, &b, &S.st);
-        if (r_ == PLO_OK && b.seed != ~0ull) { S.hi = key(b); S.lo = b.seed - seed0; }
-        return r_;
-    });
-    if (rc != PLO_OK) return rc;
-    plo_stats_t agg{}; int win = -1;
-    rc = multi_min(sh, ndev, devices, agg, win);
-    if (rc != PLO_OK) return rc;
-    out->adds = out->muls = 0xFFFFFFFFu; out->seed = ~0ull;
-    if (win >= 0) *out = bests[(size_t)win];
-    agg.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (stats) *stats = agg;
-    return PLO_OK;
+    return planless_search_multi(seed0, nrestarts, cost_mode, ndev, devices, out, stats,
+        [&](uint64_t s0, uint64_t cnt, plo_best_t *b, plo_stats_t *st) { return plo_kernel_search(M, p, s0, cnt, per_block, cost_mode, nullptr, nullptr, nullptr, b, st); });
 }
 
 int plo_tril_search_multi(const plo_qcsr_t *A, const plo_qcsr_t *B, const plo_qcsr_t *T, int expanded, uint64_t seed0, uint64_t nseeds,
@@ -2036,20 +2068,6 @@ int plo_tril_search_multi(const plo_qcsr_t *A, const plo_qcsr_t *B, const plo_qc
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------- inplacer
-struct plo_lin_plan {
-    plo::LinPlan P{};
-    void *d_img = nullptr; uint32_t *d_err = nullptr; unsigned long long *d_best = nullptr;
-    uint32_t waves_per_wg = 4, lds_bytes = 0, blocks_per_cu = 1;
-    uint64_t algo_bytes = 0;
-    bool rational = false;           // coefficients other than +-1: residues modulo PLO_TRIL_PRIME, lin_kernel<true>
-};
-
-namespace {
-int lin_launch(plo_lin_plan *pl, plo::TrilJob J, plo_stats_t *st) {
-    return atoms_launch(pl, pl->rational ? plo::lin_kernel<true> : plo::lin_kernel<false>, "inplacer", J, st);
-}
-} // namespace
-
 extern "C" {
 
 int plo_lin_plan_create_q(const plo_qcsr_t *A, plo_lin_plan_t **plan)
@@ -2060,68 +2078,25 @@ int plo_lin_plan_create_q(const plo_qcsr_t *A, plo_lin_plan_t **plan)
     if (A->m > 16382u || A->n > 16382u) return fail(PLO_E_CAPACITY, "more than 16382 rows or columns (an atom holds 14-bit variables)");
     const uint32_t m = A->m, nnz = A->rowptr[m];
     bool unit = true;
-    for (uint32_t i = 0; i < m; ++i) {
-        const uint32_t len = A->rowptr[i + 1] - A->rowptr[i];
-        if (len > 64) return fail(PLO_E_UNSUPPORTED, "row with more than 64 entries: host path only");
-        for (uint32_t e = A->rowptr[i]; e < A->rowptr[i + 1]; ++e) {
-            const int64_t nu = A->num[e], de = A->den ? A->den[e] : 1;
-            if (nu == 0 || de == 0) return fail(PLO_E_ARG, "zero entry or zero denominator");
-            if (!(de == 1 && (nu == 1 || nu == -1))) unit = false;
-            if (de % (int64_t)PLO_TRIL_PRIME == 0 || nu % (int64_t)PLO_TRIL_PRIME == 0) return fail(PLO_E_UNSUPPORTED, "entry not a unit modulo the device's prime: host path only");
-            if (A->col[e] >= A->n || (e > A->rowptr[i] && A->col[e] <= A->col[e - 1])) return fail(PLO_E_ARG, "columns must be sorted and in range");
-        }
-    }
+    if (const int rc = trilmat_check(A, true, unit)) return rc;
     // the concatenation of variant 1: the simplified program of variant 0 (at most 2 nnz + m atoms) and the oriented one,
     // checked row by row against 2 len + 2 more atoms (t_linear)
     // (nnz <= 64 m <= 64 * 16382 here: no overflow)
     const uint32_t cap = round_up(4u * nnz + 3u * m + 2u, 64);
     if (cap > 65535u) return fail(PLO_E_CAPACITY, "program does not fit LDS (and counts of 16 bits in the packed key)");
-    const size_t bytes = round_up((m + 1) * 2, 16) + round_up(nnz * 2, 16) + round_up(nnz, 16) + round_up(nnz * 4, 16) + 16;
-    plo_lin_plan *pl = new plo_lin_plan();
-    pl->rational = !unit;
+    const size_t bytes = trilmat_bytes(A) + 16;
+    plo_lin_plan *pl = atoms_new<plo_lin_plan>(bytes, unit);
+    if (!pl) return PLO_E_HIP;
     std::vector<uint8_t> img(bytes, 0);
-    if (hipMalloc(&pl->d_img, bytes) != hipSuccess) { delete pl; return fail(PLO_E_HIP, "hipMalloc"); }
     size_t off = 0;
-    plo::TrilMat &D = pl->P.M;
-    D.m = m; D.n = A->n; D.nnz = nnz;
-    uint16_t *rp = (uint16_t *)(img.data() + off); D.rp = (const uint16_t *)((uint8_t *)pl->d_img + off); off += round_up((m + 1) * 2, 16);
-    uint16_t *cl = (uint16_t *)(img.data() + off); D.col = (const uint16_t *)((uint8_t *)pl->d_img + off); off += round_up(nnz * 2, 16);
-    int8_t *vl = (int8_t *)(img.data() + off); D.val = (const int8_t *)((uint8_t *)pl->d_img + off); off += round_up(nnz, 16);
-    uint32_t *vp = (uint32_t *)(img.data() + off); D.valp = (const uint32_t *)((uint8_t *)pl->d_img + off);
-    for (uint32_t i = 0; i <= m; ++i) rp[i] = (uint16_t)A->rowptr[i];
-    for (uint32_t e = 0; e < nnz; ++e) {
-        cl[e] = (uint16_t)A->col[e];
-        const int64_t nu = A->num[e], de = A->den ? A->den[e] : 1;
-        vl[e] = unit ? (int8_t)nu : 0;
-        int64_t a = nu % (int64_t)PLO_TRIL_PRIME, d = de % (int64_t)PLO_TRIL_PRIME; if (a < 0) a += PLO_TRIL_PRIME; if (d < 0) d += PLO_TRIL_PRIME;
-        vp[e] = (uint32_t)((uint64_t)a * inv_mod((uint32_t)d, PLO_TRIL_PRIME) % PLO_TRIL_PRIME);
-    }
+    trilmat_fill(A, unit, img.data(), pl->d_img, off, pl->P.M);
     pl->P.cap = cap; pl->P.p = unit ? 0u : PLO_TRIL_PRIME;
     pl->P.lds_per_wave = round_up(8u * cap + 2u * ((m + 1u) & ~1u), 16);      // atoms, permutation
     pl->algo_bytes = 8 + 2ull * (m + 1) + 3ull * nnz;                           // the CSR image, once per candidate
-    // four waves (256 threads) per workgroup, as many workgroups per CU as the 160 KiB of LDS and the 32 waves per CU admit
-    pl->waves_per_wg = 4;
-    pl->lds_bytes = pl->P.lds_per_wave * pl->waves_per_wg;
-    if (pl->lds_bytes > 64u * 1024u) { pl->waves_per_wg = 1; pl->lds_bytes = pl->P.lds_per_wave; }
-    if (pl->lds_bytes > g_lds_max) { (void)hipFree(pl->d_img); delete pl; return fail(PLO_E_CAPACITY, "program does not fit LDS"); }
-    pl->blocks_per_cu = std::max<uint32_t>(1, std::min<uint32_t>(32u / pl->waves_per_wg, (uint32_t)(g_lds_max / pl->lds_bytes)));
-    const void *fn = pl->rational ? (const void *)plo::lin_kernel<true> : (const void *)plo::lin_kernel<false>;
-    if (hipMemcpy(pl->d_img, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess || hipMalloc((void **)&pl->d_err, 4) != hipSuccess ||
-        hipMalloc((void **)&pl->d_best, 8) != hipSuccess || hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes) != hipSuccess) {
-        plo_lin_plan_destroy(pl); return fail(PLO_E_HIP, "device setup of the inplacer plan failed");
-    }
-    *plan = pl;
-    return PLO_OK;
+    return atoms_finish(pl, pl->P.lds_per_wave, img, pl->rational ? (const void *)plo::lin_kernel<true> : (const void *)plo::lin_kernel<false>, "inplacer", plan);
 }
 
-void plo_lin_plan_destroy(plo_lin_plan_t *pl)
-{
-    if (!pl) return;
-    if (pl->d_img) (void)hipFree(pl->d_img);
-    if (pl->d_err) (void)hipFree(pl->d_err);
-    if (pl->d_best) (void)hipFree(pl->d_best);
-    delete pl;
-}
+void plo_lin_plan_destroy(plo_lin_plan_t *pl) { atoms_destroy(pl); }
 
 int plo_lin_cost_many(plo_lin_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats)
 {
@@ -2133,23 +2108,11 @@ int plo_lin_cost_many(plo_lin_plan_t *pl, const uint64_t *seeds, uint64_t seed0,
 
 int plo_lin_search(plo_lin_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_lin_best_t *best, plo_stats_t *stats)
 {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
-    if (!pl || !best) return fail(PLO_E_ARG, "null argument");
-    if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
-    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
-    const unsigned long long init = ~0ull;
-    HIPCHK(hipMemcpy(pl->d_best, &init, 8, hipMemcpyHostToDevice));
-    plo::TrilJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.ops = nullptr; J.best = pl->d_best;
-    int rc = lin_launch(pl, J, st);
-    if (rc != PLO_OK) return rc;
     unsigned long long w = 0;
-    HIPCHK(hipMemcpy(&w, pl->d_best, 8, hipMemcpyDeviceToHost));
-    if (w == init) return fail(PLO_E_INTERNAL, "no candidate reported");
+    if (const int rc = atoms_search(pl, best, lin_launch, seed0, nseeds, &w, stats)) return rc;
     best->add = (uint32_t)(w >> 48); best->sca = (uint32_t)(w >> 32) & 0xFFFFu;
     best->variant = (uint32_t)(w & 1ull); best->rows = pl->P.M.m * (best->variant + 1u);       // one barrier per row, twice in variant 1
     best->seed = seed0 + ((w & 0xFFFFFFFFull) >> 1);
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return PLO_OK;
 }
 
@@ -2283,7 +2246,7 @@ int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
     pl->lds_bytes = 0;
     for (uint32_t w : {4u, 2u, 1u}) { const uint32_t b = Q.shared_bytes + w * Q.lds_per_wave; if (b <= g_lds_max && b <= 64u * 1024u) { pl->waves_per_wg = w; pl->lds_bytes = b; break; } }
     if (!pl->lds_bytes) { delete pl; return fail(PLO_E_CAPACITY, "input does not fit LDS"); }
-    pl->blocks_per_cu = std::max<uint32_t>(1, std::min<uint32_t>(32u / pl->waves_per_wg, (uint32_t)(g_lds_max / pl->lds_bytes)));
+    pl->blocks_per_cu = blocks_per_cu(pl->waves_per_wg, pl->lds_bytes);
     pl->grid_max = (uint32_t)g_cus * pl->blocks_per_cu;
     // the device image: values, scales, row pointers, positions
     const size_t bytes = (size_t)Q.shared_bytes;

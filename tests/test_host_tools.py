@@ -203,6 +203,45 @@ def test_sparsifier_over_q_needs_the_gpu_unless_told_otherwise():
         assert rc == 0 and "SUCCESS" in err
 
 
+def _gpu_invocations(tmp_path):
+    """the tools that search on the device, five restarts on the 2x2x2 Winograd files (orbiter writes next to its inputs: copies)"""
+    import shutil
+    lrp = [os.path.join(DATA, "2x2x2_7_Winograd_%s.sms" % x) for x in "LRP"]
+    own = [shutil.copy(f, str(tmp_path)) for f in lrp]
+    return {"inplacer": ["inplacer", "-O", "5", lrp[0]], "trilplacer": ["trilplacer", "-O", "5"] + lrp,
+            "orbiter": ["orbiter", "-O", "5"] + own, "optimizer": ["optimizer", "-q", str(P), "-D", "--gpu", "1", "-O", "5", lrp[0]],
+            "sparsifier": ["sparsifier", "-c", "4", "-S", lrp[0]]}
+
+
+@pytest.mark.parametrize("tool", ["inplacer", "trilplacer", "orbiter", "optimizer"])
+def test_no_silent_fallback_without_a_device(tool, tmp_path):
+    """without a device a tool that was not told `--gpu 0` stops with status 2 and says why; it prints no program"""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    cmd = _gpu_invocations(tmp_path)[tool]
+    rc, out, err = run([os.path.join(ROOT, "bin", cmd[0])] + cmd[1:])
+    assert rc == 2 and out == "", (rc, out, err)
+    assert "ERROR" in err and "no HIP device" in err, err
+
+
+@pytest.mark.parametrize("tool", ["inplacer", "trilplacer", "orbiter", "optimizer", "sparsifier"])
+def test_library_search_order(tool, tmp_path):
+    """a copy of the tool away from the tree (no ../plinopt_amd/, no library beside it, nothing on the loader's path) cannot load the
+    library and says so; PLO_HIP_LIB, and the older name PLINOPT_HIP_LIB alone, point it at the built one"""
+    import shutil
+    cmd = _gpu_invocations(tmp_path)[tool]
+    exe = shutil.copy(os.path.join(ROOT, "bin", cmd[0]), str(tmp_path / ("copy_of_" + cmd[0])))
+    env = {k: v for k, v in os.environ.items() if k not in ("PLO_HIP_LIB", "PLINOPT_HIP_LIB")}
+    env["LD_LIBRARY_PATH"] = ""
+    r = subprocess.run([exe] + cmd[1:], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode != 0 and "cannot load libplinopt_hip.so" in r.stderr, (r.returncode, r.stderr)
+    for name in ("PLO_HIP_LIB", "PLINOPT_HIP_LIB"):
+        r = subprocess.run([exe] + cmd[1:], capture_output=True, text=True, timeout=300,
+                           env=dict(env, **{name: os.path.join(ROOT, "plinopt_amd", "libplinopt_hip.so")}))
+        assert "cannot load" not in r.stderr, (name, r.stderr)
+
+
 def test_sparsifier_finds_the_known_sparse_basis_of_winograd():
     """Winograd's L matrix (14 non-zeros) has an alternative basis with 10 (data/2x2x2_7_DPS-accurate-ALT_L.sms)."""
     rc, out, err = run([SPS, "-c", "4", "-S", "--gpu", "0", os.path.join(DATA, "2x2x2_7_Winograd_L.sms")])
