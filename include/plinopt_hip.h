@@ -317,6 +317,39 @@ int  plo_orbit_search(plo_orbit_plan_t *plan, uint64_t seed0, uint64_t nseeds, p
 int  plo_orbit_search_multi(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure,
                             uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats);
 
+/* ---- Row-dependency enumeration: the search of the reference's `dependency` (src/dependency.cpp:74-101, 158-165).  M (m x n) as
+ * rational CSR, `ncoef` coefficients cnum[v]/cden[v] (the caller's FCoeffs, in order), `level` the largest number of rows in a
+ * combination (1 .. PLO_DEP_MAX_LEVEL).  A combination is a top row i with coefficient 1 and rows i < q1 < q2 < ... with
+ * coefficients of the list; every combination of 2 .. level rows is formed, and a hit is one that vanishes (PLO_DEP_ZERO) or
+ * has exactly one non-zero entry (PLO_DEP_ONE: `col` is its column, `residue` its value).
+ * modulus p (2 <= p < 2^31): values are residues in [0, p) and the hit list is final.  modulus 0 is Q: the device works
+ * modulo the prime PLO_DEP_PRIME, and since reduction modulo it is a ring map, every combination that is a hit over Q is
+ * reported; the list is a superset, `kind`, `col` and `residue` are those of the residues, and the caller recomputes each
+ * reported combination over Q to drop the false ones and classify the others (bin/dependency does).
+ * plo_dep_search enumerates the top rows [row0, row1) and returns the hits in the reference's depth-first order: by top row,
+ * then lexicographic on (q1, v1), (q2, v2), ..., a prefix before its extensions.  *nhits is always the full count; when it
+ * exceeds `cap` the call returns PLO_E_CAPACITY, hits[0 .. cap) holds hits in no particular order, and the caller repeats with
+ * cap = *nhits.  More than 2^24 hits in one call are PLO_E_CAPACITY whatever `cap` is: take fewer top rows per call.
+ * PLO_E_UNSUPPORTED: level above PLO_DEP_MAX_LEVEL, a modulus of 2^31 or more, a denominator (of M or of a coefficient) that is no
+ * unit modulo the modulus (the prime, over Q).  PLO_E_CAPACITY: more than 4096 rows, 1024 columns or 255 coefficients, or a
+ * level whose vectors do not fit LDS (512 x 128, level 6, 64 coefficients is within every limit).  One device per call. */
+#define PLO_DEP_MAX_LEVEL 8
+#define PLO_DEP_PRIME     2147483629u
+#define PLO_DEP_ZERO      0
+#define PLO_DEP_ONE       1
+typedef struct {
+    uint32_t size;                        /* rows in the combination, 2 .. level */
+    uint32_t kind;                        /* PLO_DEP_ZERO or PLO_DEP_ONE */
+    uint32_t col, residue;                /* PLO_DEP_ONE: the column of the non-zero entry and its value, in [1, p) */
+    uint16_t rows[PLO_DEP_MAX_LEVEL];     /* rows[0] the top row; increasing; 0 beyond `size` */
+    uint8_t  coef[PLO_DEP_MAX_LEVEL];     /* coef[k]: index of row k's coefficient in the list, k >= 1; coef[0] = 0 (the top row has 1) */
+} plo_dep_hit_t;
+typedef struct plo_dep_plan plo_dep_plan_t;
+int  plo_dep_plan_create_q(const plo_qcsr_t *M, const int64_t *cnum, const int64_t *cden, uint32_t ncoef,
+                           uint64_t modulus /* 0 = Q */, uint32_t level, plo_dep_plan_t **plan);
+void plo_dep_plan_destroy(plo_dep_plan_t *plan);
+int  plo_dep_search(plo_dep_plan_t *plan, uint32_t row0, uint32_t row1, plo_dep_hit_t *hits, uint64_t cap, uint64_t *nhits, plo_stats_t *stats);
+
 /* Pack / unpack the (cost, seed) word used by the grid reduction and by the
  * single 8-byte MIN all-reduce across ranks (the `#pragma omp critical`
  * best-so-far of include/plinopt_optimize.inl:1214-1237).  seed_off is the

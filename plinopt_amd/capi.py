@@ -26,6 +26,7 @@ EXPORTS = [
     "plo_tril_plan_create", "plo_tril_plan_create_x", "plo_tril_plan_create_q", "plo_tril_plan_destroy", "plo_tril_cost_many", "plo_tril_search",
     "plo_lin_plan_create_q", "plo_lin_plan_destroy", "plo_lin_cost_many", "plo_lin_search", "plo_lin_search_multi",
     "plo_orbit_plan_create_q", "plo_orbit_plan_destroy", "plo_orbit_cost_many", "plo_orbit_search", "plo_orbit_search_multi",
+    "plo_dep_plan_create_q", "plo_dep_plan_destroy", "plo_dep_search",
     "plo_pack_cost",
 ]
 
@@ -82,6 +83,15 @@ class LinBest(ctypes.Structure):
 
 class OrbitBest(ctypes.Structure):
     _fields_ = [("cost", ctypes.c_uint32), ("nnz", ctypes.c_uint32), ("nno", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
+
+
+DEP_MAX_LEVEL = 8
+
+
+class DepHit(ctypes.Structure):
+    """plo_dep_hit_t of include/plinopt_hip.h"""
+    _fields_ = [("size", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("col", ctypes.c_uint32), ("residue", ctypes.c_uint32),
+                ("rows", ctypes.c_uint16 * DEP_MAX_LEVEL), ("coef", ctypes.c_uint8 * DEP_MAX_LEVEL)]
 
 
 class PloError(RuntimeError):
@@ -171,6 +181,11 @@ def lib():
         L.plo_orbit_search.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(OrbitBest), ctypes.POINTER(Stats)]
         L.plo_orbit_search_multi.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                              ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(OrbitBest), ctypes.POINTER(Stats)]
+        L.plo_dep_plan_create_q.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+                                            ctypes.POINTER(ctypes.c_void_p)]
+        L.plo_dep_plan_destroy.argtypes = [ctypes.c_void_p]
+        L.plo_dep_plan_destroy.restype = None
+        L.plo_dep_search.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(DepHit), ctypes.c_uint64, u64p, ctypes.POINTER(Stats)]
         L.plo_multi_comm_inits.restype = ctypes.c_uint64
         L.plo_pack_cost.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32]
         L.plo_pack_cost.restype = ctypes.c_uint64

@@ -15,6 +15,7 @@
 #include "plo_tril.hip"
 #include "plo_lin.hip"
 #include "plo_orbit.hip"
+#include "plo_dep.hip"
 #include "../../include/plinopt_hip.h"
 
 #include <algorithm>
@@ -2311,6 +2312,142 @@ int plo_orbit_search_multi(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_q
     return sharded_search(seed0, nseeds, ndev, devices, best, stats,
         [&](plo_orbit_plan_t **plan) { return plo_orbit_plan_create_q(L, R, P, modulus, measure, plan); }, plo_orbit_search, plo_orbit_plan_destroy,
         [&](const plo_orbit_best_t &pb) { return std::make_pair(((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, pb.seed - seed0); });   // (cost, nnz, nno), then seed
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------- dependency
+struct plo_dep_plan {
+    plo::DepPlan P{};
+    void *d_img = nullptr; unsigned long long *d_ctr = nullptr;      // d_ctr: the task counter, then the hit counter
+    uint32_t waves_per_wg = 4, lds_bytes = 0, blocks_per_cu = 1, grid_max = 1, level = 0;
+    uint64_t algo_bytes = 0; bool m_in_lds = false;
+};
+
+namespace {
+#define PLO_DEP_MAX_HITS (1ull << 24)
+// the residue of num/den modulo p, false when den is no unit
+bool dep_residue(int64_t num, int64_t den, uint32_t p, uint32_t &out) {
+    int64_t d = den % (int64_t)p, a = num % (int64_t)p;
+    if (d < 0) d += p;
+    if (a < 0) a += p;
+    if (gcd64(d, p) != 1) return false;
+    out = (uint32_t)((uint64_t)a * inv_mod((uint32_t)d, p) % p);
+    return true;
+}
+// the reference's order: by top row, then (q1, v1), (q2, v2), ..., a prefix before its extensions
+bool dep_before(const plo_dep_hit_t &a, const plo_dep_hit_t &b) {
+    if (a.rows[0] != b.rows[0]) return a.rows[0] < b.rows[0];
+    for (uint32_t k = 1; k < a.size && k < b.size; ++k) {
+        if (a.rows[k] != b.rows[k]) return a.rows[k] < b.rows[k];
+        if (a.coef[k] != b.coef[k]) return a.coef[k] < b.coef[k];
+    }
+    return a.size < b.size;
+}
+} // namespace
+
+extern "C" {
+
+int plo_dep_plan_create_q(const plo_qcsr_t *M, const int64_t *cnum, const int64_t *cden, uint32_t ncoef, uint64_t modulus, uint32_t level, plo_dep_plan_t **plan)
+{
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!M || !plan || (ncoef && (!cnum || !cden))) return fail(PLO_E_ARG, "null argument");
+    if (modulus == 1) return fail(PLO_E_ARG, "modulus 1");
+    if (level == 0 || ncoef == 0) return fail(PLO_E_ARG, "level and the number of coefficients must be positive");
+    if (const char *d = qcsr_defect(M)) return fail(PLO_E_ARG, d);
+    for (uint32_t v = 0; v < ncoef; ++v) if (cden[v] <= 0) return fail(PLO_E_ARG, "non-positive denominator of a coefficient");
+    if (level > PLO_DEP_MAX_LEVEL) return fail(PLO_E_UNSUPPORTED, "level above " + std::to_string(PLO_DEP_MAX_LEVEL) + ": host path only");
+    if (modulus >= (1ull << 31)) return fail(PLO_E_UNSUPPORTED, "modulus of 2^31 or more: host path only");
+    if (M->m > 4096) return fail(PLO_E_CAPACITY, "more than 4096 rows");
+    if (M->n > 1024) return fail(PLO_E_CAPACITY, "more than 1024 columns");
+    if (ncoef > 255) return fail(PLO_E_CAPACITY, "more than 255 coefficients");
+    const uint32_t p = modulus ? (uint32_t)modulus : PLO_DEP_PRIME, m = M->m, n = M->n, ld = n | 1u;
+    std::vector<uint32_t> dense((size_t)m * ld, 0u), coef(ncoef);
+    for (uint32_t i = 0; i < m; ++i)
+        for (uint32_t e = M->rowptr[i]; e < M->rowptr[i + 1]; ++e)
+            if (!dep_residue(M->num[e], M->den ? M->den[e] : 1, p, dense[(size_t)i * ld + M->col[e]])) return fail(PLO_E_UNSUPPORTED, "a denominator of the matrix is no unit modulo " + std::to_string(p));
+    for (uint32_t v = 0; v < ncoef; ++v)
+        if (!dep_residue(cnum[v], cden[v], p, coef[v])) return fail(PLO_E_UNSUPPORTED, "a denominator of a coefficient is no unit modulo " + std::to_string(p));
+    plo_dep_plan *pl = new plo_dep_plan();
+    plo::DepPlan &Q = pl->P;
+    pl->level = level;
+    Q.m = m; Q.n = n; Q.ld = ld; Q.C = ncoef; Q.p = p; Q.mu = (~0ull) / p;
+    Q.L = std::max(2u, std::min(level, m));                   // no combination has more rows than the matrix
+    Q.nvec = Q.L < 3u ? 1u : Q.L - 2u;
+    Q.lds_per_wave = round_up(4u * (Q.nvec * n + 2u * PLO_DEP_MAX_LEVEL), 16);
+    // M in LDS when it and four waves fit in 64 KiB; otherwise it is read through L2
+    const uint32_t m_bytes = round_up(4u * m * ld, 16), c_bytes = round_up(4u * ncoef, 16);
+    const uint32_t cap = (uint32_t)std::min<size_t>(g_lds_max, 64u * 1024u);
+    pl->m_in_lds = (uint64_t)m_bytes + c_bytes + 4u * Q.lds_per_wave <= cap;
+    Q.off_coef = pl->m_in_lds ? m_bytes : 0u; Q.off_wave = Q.off_coef + c_bytes;
+    pl->lds_bytes = 0;
+    for (uint32_t w : {4u, 2u, 1u}) { const uint64_t b = (uint64_t)Q.off_wave + (uint64_t)w * Q.lds_per_wave; if (b <= cap) { pl->waves_per_wg = w; pl->lds_bytes = (uint32_t)b; break; } }
+    if (!pl->lds_bytes) { delete pl; return fail(PLO_E_CAPACITY, "the vectors of this level do not fit LDS"); }
+    pl->blocks_per_cu = blocks_per_cu(pl->waves_per_wg, pl->lds_bytes);
+    pl->grid_max = (uint32_t)g_cus * pl->blocks_per_cu;
+    pl->algo_bytes = 4ull * m * ld + 4ull * ncoef;
+    const size_t bytes = (size_t)m_bytes + c_bytes;
+    std::vector<uint8_t> img(bytes, 0);
+    if (m) memcpy(img.data(), dense.data(), 4ull * m * ld);
+    memcpy(img.data() + m_bytes, coef.data(), 4ull * ncoef);
+    const void *fn = pl->m_in_lds ? (const void *)plo::dep_kernel<true> : (const void *)plo::dep_kernel<false>;
+    if (hipMalloc(&pl->d_img, bytes) != hipSuccess || hipMemcpy(pl->d_img, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc((void **)&pl->d_ctr, 16) != hipSuccess ||
+        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes) != hipSuccess) {
+        plo_dep_plan_destroy(pl); return fail(PLO_E_HIP, "device setup of the dependency plan failed");
+    }
+    Q.M = (const uint32_t *)pl->d_img; Q.coef = (const uint32_t *)((const uint8_t *)pl->d_img + m_bytes);
+    *plan = pl;
+    return PLO_OK;
+}
+
+void plo_dep_plan_destroy(plo_dep_plan_t *pl)
+{
+    if (!pl) return;
+    if (pl->d_img) (void)hipFree(pl->d_img);
+    if (pl->d_ctr) (void)hipFree(pl->d_ctr);
+    delete pl;
+}
+
+int plo_dep_search(plo_dep_plan_t *pl, uint32_t row0, uint32_t row1, plo_dep_hit_t *hits, uint64_t cap, uint64_t *nhits, plo_stats_t *stats)
+{
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!pl || !nhits || (cap && !hits)) return fail(PLO_E_ARG, "null argument");
+    if (row0 > row1 || row1 > pl->P.m) return fail(PLO_E_ARG, "top rows out of range");
+    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
+    const auto t0 = std::chrono::steady_clock::now();
+    *nhits = 0;
+    const uint32_t m = pl->P.m, C = pl->P.C, nrows = row1 - row0;
+    std::vector<uint64_t> toff(nrows + 1u, 0);
+    for (uint32_t r = 0; r < nrows; ++r) toff[r + 1u] = toff[r] + (uint64_t)(m - 1u - (row0 + r)) * C;
+    const uint64_t ntasks = toff[nrows];
+    if (pl->level < 2u || ntasks == 0) return PLO_OK;
+    const uint64_t dcap = std::min<uint64_t>(cap, PLO_DEP_MAX_HITS);
+    uint64_t *d_toff = nullptr; plo_dep_hit_t *d_hits = nullptr;
+    auto release = [&] { if (d_toff) (void)hipFree(d_toff); if (d_hits) (void)hipFree(d_hits); };
+    if (hipMalloc((void **)&d_toff, 8ull * (nrows + 1u)) != hipSuccess || hipMemcpy(d_toff, toff.data(), 8ull * (nrows + 1u), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc((void **)&d_hits, std::max<uint64_t>(1, dcap) * sizeof(plo_dep_hit_t)) != hipSuccess ||
+        hipMemsetAsync(pl->d_ctr, 0, 16, g_stream) != hipSuccess) { release(); return fail(PLO_E_HIP, "device buffers of the dependency search"); }
+    plo::DepJob J{}; J.row0 = row0; J.nrows = nrows; J.toff = d_toff; J.ntasks = ntasks; J.next = pl->d_ctr; J.count = pl->d_ctr + 1; J.hits = d_hits; J.cap = dcap;
+    const uint64_t need = (ntasks + pl->waves_per_wg - 1) / pl->waves_per_wg;
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(pl->grid_max, need));
+    int rc = timed_launch(pl, grid, ntasks, st, [&] {
+        if (pl->m_in_lds) hipLaunchKernelGGL((plo::dep_kernel<true>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+        else hipLaunchKernelGGL((plo::dep_kernel<false>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+    });
+    unsigned long long found = 0;
+    if (rc == PLO_OK && hipMemcpy(&found, pl->d_ctr + 1, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back of the hit count");
+    if (rc == PLO_OK) {
+        *nhits = found;
+        const uint64_t have = std::min<uint64_t>(found, dcap);
+        if (have && hipMemcpy(hits, d_hits, have * sizeof(plo_dep_hit_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back of the hits");
+        else if (found > PLO_DEP_MAX_HITS) rc = fail(PLO_E_CAPACITY, std::to_string(found) + " hits, more than 2^24 in one call: take fewer top rows");
+        else if (found > cap) rc = fail(PLO_E_CAPACITY, std::to_string(found) + " hits for a buffer of " + std::to_string(cap));
+        else std::sort(hits, hits + found, dep_before);
+    }
+    release();
+    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
 }
 
 } // extern "C"

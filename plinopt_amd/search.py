@@ -435,3 +435,49 @@ def orbit_search_multi(L, R, P, modulus, measure, seed0, nseeds, devices):
     capi.check(lib.plo_orbit_search_multi(*[ctypes.byref(c) for c, _ in csr], modulus, measure, seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
     del csr
     return ((b.cost, b.nnz, b.nno), b.seed), st.as_dict()
+
+
+DEP_ZERO, DEP_ONE = 0, 1
+DEP_PRIME = 2147483629
+
+
+class DepPlan:
+    """Mirror of the enumeration of the reference's `dependency` (src/dependency.cpp:74-101, 158-165, bin/dependency): M (m x n)
+    as a rational CSR (rowptr, col, num[, den]), the coefficient list as (numerator, denominator) pairs, over Q (modulus 0) or
+    Z_modulus (< 2^31), combinations of at most `level` rows (1 .. 8).  `search` returns the hits of the top rows
+    [row0, row1) in the reference's depth-first order, each (rows, coefficient indices, kind, column, residue): the top row has
+    coefficient 1 and index None.  Over Q the device works modulo DEP_PRIME and the list is a superset of the true hits: the
+    caller recomputes every combination over Q.  More hits than `cap` raise PloError(PLO_E_CAPACITY) with the full count in
+    `last_nhits`."""
+
+    def __init__(self, m, n, rowptr, col, num, den=None, coeffs=((1, 1), (-1, 1)), modulus=0, level=4, device=None):
+        L = capi.lib()
+        if device is not None:
+            capi.check(L.plo_init(device))
+        self._h = None
+        self._csr, self._keep = _qcsr(m, n, rowptr, col, num, den)
+        cn = (ctypes.c_int64 * max(len(coeffs), 1))(*[int(c[0]) for c in coeffs])
+        cd = (ctypes.c_int64 * max(len(coeffs), 1))(*[int(c[1]) for c in coeffs])
+        h = ctypes.c_void_p()
+        capi.check(L.plo_dep_plan_create_q(ctypes.byref(self._csr), cn, cd, len(coeffs), modulus, level, ctypes.byref(h)))
+        self._h = h
+        self.m = m
+        self.last_stats = None
+        self.last_nhits = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                capi.lib().plo_dep_plan_destroy(self._h); self._h = None
+        except Exception:
+            pass
+
+    def search(self, row0=0, row1=None, cap=1 << 16):
+        row1 = self.m if row1 is None else row1
+        hits = (capi.DepHit * max(cap, 1))()
+        nh, st = ctypes.c_uint64(0), capi.Stats()
+        rc = capi.lib().plo_dep_search(self._h, row0, row1, hits, cap, ctypes.byref(nh), ctypes.byref(st))
+        self.last_nhits = nh.value
+        capi.check(rc)
+        self.last_stats = st.as_dict()
+        return [(tuple(h.rows[:h.size]), (None,) + tuple(h.coef[1:h.size]), h.kind, h.col, h.residue) for h in hits[:nh.value]]
