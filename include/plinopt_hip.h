@@ -165,7 +165,11 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
  * per_block > 1: the restarts of a block of per_block consecutive seeds share the decomposition of the block's first seed.
  * adds/muls (nrestarts entries), info (3 per restart: rank, NotIndep, number of dependent rows computed through Dep) and best may each be NULL.
  * M needs at most 128 rows, 64 columns, 64 dependent rows and a kernel of positive dimension (PLO_E_UNSUPPORTED otherwise: the caller
- * falls back to host decompositions + plo_cse_chain_batch). */
+ * falls back to host decompositions + plo_cse_chain_batch).  PLO_E_CAPACITY: more than 64 rows with an entry other than +-1, or a Dep
+ * whose pair table outgrows the LDS (sized from a sample of the decompositions: 128x64 with three random entries per row is one).
+ * Empty rows of M are admitted: an empty row is a dependent row whose combination is empty, i.e. a row of Dep without entry (a matrix
+ * of empty rows only is refused: PLO_E_UNSUPPORTED, "zero matrix").  With PLO_COST_SUM best->adds holds the sum and best->muls 0, as
+ * plo_cse_chain_batch. */
 int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t nrestarts, uint32_t per_block, int cost_mode,
                       uint32_t *adds, uint32_t *muls, uint32_t *info, plo_best_t *best, plo_stats_t *stats);
 /* The restart loop of KernelOptimiser (include/plinopt_optimize.inl:1299-1340) over `ndev` devices from one process: contiguous

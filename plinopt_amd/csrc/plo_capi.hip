@@ -1347,7 +1347,7 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
             uint32_t a = 0, mu = 0;
             if (cost_mode == PLO_COST_SUM_THEN_ADD) { a = (uint32_t)(key & 0xFFFFu); mu = (uint32_t)(key >> 16) - a; }
             else if (cost_mode == PLO_COST_ADD_THEN_MUL) { a = (uint32_t)(key >> 16); mu = (uint32_t)(key & 0xFFFFu); }
-            else { a = (uint32_t)key; mu = 0; }                                     // sum only: reported in .adds
+            else { a = (uint32_t)(key >> 16); mu = 0; }                             // sum only (cost_key32: the sum above 16 zero bits): reported in .adds
             best->adds = a; best->muls = mu; best->seed = seed0 + off;
         }
 #undef BCHK
@@ -1558,7 +1558,7 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
             uint32_t a = 0, mu = 0;
             if (cost_mode == PLO_COST_SUM_THEN_ADD) { a = (uint32_t)(key & 0xFFFFu); mu = (uint32_t)(key >> 16) - a; }
             else if (cost_mode == PLO_COST_ADD_THEN_MUL) { a = (uint32_t)(key >> 16); mu = (uint32_t)(key & 0xFFFFu); }
-            else { a = (uint32_t)key; mu = 0; }
+            else { a = (uint32_t)(key >> 16); mu = 0; }                             // sum only: reported in .adds, as plo_cse_chain_batch
             best->adds = a; best->muls = mu; best->seed = seed0 + o;
         }
         cleanup();

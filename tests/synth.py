@@ -425,3 +425,333 @@ def orbit_tie_cases():
     _orbit_case(out, "1x2x2_Q", "tie", (1, 2, 2), 3, _triple(rng, (1, 2, 2), 3, UNIT, hi=2))
     _orbit_case(out, "2x1x2_Q_canon", "tie", (2, 1, 2), 4, _triple(rng, (2, 1, 2), 4, UNIT, hi=2), measure=CANONICAL)
     return out
+
+
+# ======================================================================================================================
+# Edge-shape cases for the kernel method (plo_kmethod.hip, plo_kernel_search) and the trilinear kernel (plo_tril.hip,
+# plo_tril_*): tests/golden/make_kmethod_synth_costs.py and make_tril_synth_costs.py score them with the C oracle
+# (oracle/plo_oracle.c plo_oracle_kernel_restart, oracle/plo_tril_oracle.c); tests/test_gpu_kmethod_tril_synth.py holds the
+# kernels to those goldens and tests/test_synth_golden.py recomputes them.
+# ======================================================================================================================
+KM_PRIME = 131071
+KM_MODULI = [3, 5, 7, 101, 8191, 524287, 2147483629, 2147483647]
+KM_R = [4, 5, 8, 9, 16, 17, 32, 33, 64]
+KM_PER_BLOCK = (1000, 50, 16)                                    # seed0, restarts and per_block of the shared-decomposition check
+
+
+def _clog2(x):
+    return max(x - 1, 0).bit_length()
+
+
+def rank_mod(rows, p):
+    """rank modulo p of rows given as {column: value}"""
+    piv, r = {}, 0
+    for row in rows:
+        row = {j: v % p for j, v in row.items() if v % p}
+        while row:
+            j = min(row)
+            if j not in piv:
+                iv = pow(row[j], -1, p)
+                piv[j] = {k: v * iv % p for k, v in row.items()}
+                r += 1
+                break
+            x = row[j]
+            for k, v in piv[j].items():
+                w = (row.get(k, 0) - x * v) % p
+                if w:
+                    row[k] = w
+                else:
+                    row.pop(k, None)
+    return r
+
+
+def km_refusal(m, n, rows, p):
+    """None when plo_kernel_search takes the matrix as far as the host can tell without a device (Dep's pair table is sized
+    from a sample of the decompositions on the device: a dense Dep is refused for capacity there), else the name of the
+    header's code, in the order plo_kernel_search checks"""
+    if m == 0 or m > 128 or n == 0 or n > 64:
+        return "PLO_E_UNSUPPORTED"
+    R = rank_mod(rows, p)
+    nd = m - R
+    if nd == 0 or nd > 64 or R == 0:
+        return "PLO_E_UNSUPPORTED"
+    unit = all(v % p in (1, p - 1) for r in rows for v in r.values())
+    if m > 64 and not unit:
+        return "PLO_E_CAPACITY"
+    naive = sum(max(len(r) - 1, 0) for r in rows)
+    for cols, nv in ((n, naive), (m, nd * R)):                   # the pair keys of M's image and, at its hard bound, of Dep's
+        nc = cols + nv // 2 + 2
+        if nc >= 0xFFFF or 2 * _clog2(nc) + _clog2(p) > 51:
+            return "PLO_E_CAPACITY"
+    if 2 * sum(len(r) for r in rows) >= 65535 or 2 * nd * R >= 65535:
+        return "PLO_E_CAPACITY"
+    return None
+
+
+def km_text(m, n, p, rows):
+    return "%d %d %d\n" % (m, n, p) + "".join("%d %d %d\n" % (i, j, v) for i, r in enumerate(rows) for j, v in sorted(r.items()))
+
+
+def _km_case(out, name, family, n, rows, p=KM_PRIME, refusal=None):
+    """rows: one {column: signed value} per row; the case holds the residues"""
+    m = len(rows)
+    assert all(0 <= j < n and v % p for r in rows for j, v in r.items()), name
+    rows = [{j: v % p for j, v in r.items()} for r in rows]
+    got = km_refusal(m, n, rows, p)
+    assert got == refusal, (name, got)
+    unit = all(v in (1, p - 1) for r in rows for v in r.values())
+    assert m <= 64 or unit or refusal, name                      # more than 64 rows: +-1 only
+    rank = rank_mod(rows, p) if n <= 64 and m <= 128 else None
+    c = SimpleNamespace(name="km_%s_%s" % (family, name), family=family, m=m, n=n, p=p, rows=rows, csr=(m, n) + to_csr(rows, p), refusal=refusal,
+                        mode="runs", seeds=list(SEEDS_RUNS), unit=unit, rank=rank, quick=not refusal, sha256=_sha(km_text(m, n, p, rows)))
+    assert c.name not in [x.name for x in out], c.name
+    out.append(c)
+    return c
+
+
+def _km_blocks(k, vals=None, rng=None):
+    """k diagonal blocks of 2 columns x 4 rows: e0, e1, e0 + e1, e0 - e1 (or those supports with values drawn from vals)"""
+    rows = []
+    for b in range(k):
+        rows += [{2 * b: 1}, {2 * b + 1: 1}, {2 * b: 1, 2 * b + 1: 1}, {2 * b: 1, 2 * b + 1: -1}]
+    if vals:
+        rows = [{j: _pick(rng, vals) for j in r} for r in rows]
+    return rows
+
+
+def kmethod_cases():
+    """About 50 matrices at the limits of plo_kernel_search (128 rows, 64 columns, 64 dependent rows, rank 64, rows of 64
+    entries, empty rows, eight moduli, 4 / 2 / 1 waves per workgroup) and seven it refuses.  Every case is scored as the
+    (seed0, n) runs of SEED_RUNS with per_block = 1: plo_kernel_search takes a seed range only."""
+    rng = random.Random(0x4B3E7)
+    out = []
+    # (a) the size limits on block-diagonal matrices: 4x2, 64x32, 68x34, 128x64 (rank 64 and 64 dependent rows), one row less,
+    # and 64x32 with other values than +-1 (ProgramGen with one row per lane)
+    for k in (1, 16, 17, 32):
+        c = _km_case(out, "%dx%d" % (4 * k, 2 * k), "a", 2 * k, _km_blocks(k))
+        assert (c.rank, c.m - c.rank) == (2 * k, 2 * k)
+    c = _km_case(out, "127x64", "a", 64, _km_blocks(32)[:-1])
+    assert (c.rank, c.m - c.rank) == (64, 63)
+    c = _km_case(out, "64x32_vals", "a", 32, _km_blocks(16, [1, -1, 2, 3], rng))
+    assert not c.unit and c.rank == 32
+    # (b) few columns, many dependent rows
+    c = _km_case(out, "65x1", "b", 1, [{0: _pick(rng, [1, -1])} for _ in range(65)])
+    assert c.m - c.rank == 64
+    c = _km_case(out, "66x2", "b", 2, [{0: 1}, {1: 1}] + [{0: 1, 1: _pick(rng, [1, -1])} for _ in range(64)])
+    assert c.m - c.rank == 64
+    vecs = [t for t in ((a, b, cc, d) for a in (0, 1, -1) for b in (0, 1, -1) for cc in (0, 1, -1) for d in (0, 1, -1)) if any(t)]
+    c = _km_case(out, "68x4", "b", 4, [{j: v for j, v in enumerate(t) if v} for t in _sample(rng, vecs, 68)])
+    assert (c.rank, c.m - c.rank) == (4, 64)
+    c = _km_case(out, "40x3_rank1", "b", 3, [{0: k, 1: -k, 2: 2 * k} for k in (1 + rng.randrange(5) for _ in range(40))])
+    assert c.rank == 1 and not c.unit
+    # (c) long rows, and rows of Dep of every group width: the identity of size R and one row of R entries (its combination
+    # has R entries and the rank is R: Dep's lpr_log2 = ceil(log2 R) goes from 2 to 6); R = 64 is a row of 64 entries
+    for R in KM_R:
+        eye = [{j: 1} for j in range(R)]
+        _km_case(out, "R%d_ones" % R, "c", R, eye + [{j: 1 for j in range(R)}])
+        if R + 1 <= 64:
+            _km_case(out, "R%d_1toR" % R, "c", R, eye + [{j: j + 1 for j in range(R)}])
+    c = _km_case(out, "64x16_dense", "c", 16, [{j: 1} for j in range(16)] + [{j: _pick(rng, [1, -1, 2]) for j in range(16)} for _ in range(48)])
+    assert (c.m, c.rank) == (64, 16)
+    # (d) degenerate rows and columns
+    while True:
+        rows = _rows(rng, 8, [2 + rng.randrange(2) for _ in range(12)], [1, -1, 2])
+        if rank_mod(rows, KM_PRIME) == 8:
+            break
+    _km_case(out, "15x8_3empty", "d", 8, rows + [{}, {}, {}])
+    _km_case(out, "3x2_empty", "d", 2, [{0: 1}, {1: 1}, {}])       # its only dependent row has an empty combination
+    basis = [{0: 1, 1: -1}, {1: 1, 2: 1}, {2: -1, 3: 1}, {0: 1, 3: 1}]
+    _km_case(out, "dup_unit", "d", 4, basis + [dict(basis[0]), dict(basis[2]), {j: -v for j, v in basis[1].items()}, dict(basis[0])])
+    _km_case(out, "dup_twice", "d", 4, basis + [dict(basis[1]), {j: 2 * v for j, v in basis[2].items()}, {j: -2 * v for j, v in basis[0].items()}])
+    while True:
+        rows = [{2 * j: v for j, v in r.items()} for r in _rows(rng, 8, [2 + rng.randrange(2) for _ in range(12)], [1, -1, 2])]
+        if rank_mod(rows, KM_PRIME) == 8:
+            break
+    _km_case(out, "12x16_even", "d", 16, rows)
+    c = _km_case(out, "64x64_col63", "d", 64, _rows(rng, 64, [3] * 64, [1, -1, 2, 3], pool=list(range(63))), p=2147483629)
+    assert c.rank < 64 and not c.unit
+    # (e) moduli: both branches of kmul, p - 2 of every bit length in kinv, Barrett at 31 bits, on one 30x12 pattern
+    pattern = _rows(rng, 12, [3] * 30, [1, -1, 2, 3, 6])
+    for p in KM_MODULI:
+        _km_case(out, "mod%d" % p, "e", 12, [{j: (v if v % p else 1) for j, v in r.items()} for r in pattern], p=p)
+    # (f) the LDS choices: 112x56 block diagonal (the elimination arrays of 112 x 114 words and the combinations put a wave's
+    # state between a third and a half of the LDS: two waves per workgroup); 4x2 has four, 128x64 one
+    c = _km_case(out, "112x56", "f", 56, _km_blocks(28))
+    assert (c.rank, c.m - c.rank) == (56, 56)
+    # refusals, with the code include/plinopt_hip.h documents
+    U = "PLO_E_UNSUPPORTED"
+    _km_case(out, "67x2_65dep", "refuse", 2, [{0: 1}, {1: 1}] + [{0: 1, 1: _pick(rng, [1, -1])} for _ in range(65)], refusal=U)
+    for s in range(1000):                                         # two +-1 entries per row: the seed that leaves rank 62, i.e. 66 dependent rows
+        r2 = random.Random(0x4B3E7000 + s)
+        rows = _rows(r2, 64, [2] * 128, [1, -1])
+        if rank_mod(rows, KM_PRIME) == 62:
+            break
+    assert rank_mod(rows, KM_PRIME) == 62
+    _km_case(out, "128x64_rank62", "refuse", 64, rows, refusal=U)
+    _km_case(out, "129x2", "refuse", 2, [{0: 1}, {1: 1}] + [{0: 1, 1: _pick(rng, [1, -1])} for _ in range(127)], refusal=U)
+    _km_case(out, "3x65", "refuse", 65, [{0: 1}, {64: 1}, {0: 1, 64: 1}], refusal=U)
+    _km_case(out, "4x7_fullrank", "refuse", 7, [{0: 1, 4: 1}, {1: 1, 5: -1}, {2: 1, 6: 1}, {3: 1, 0: -1}], refusal=U)
+    _km_case(out, "3x2_allempty", "refuse", 2, [{}, {}, {}], refusal=U)
+    _km_case(out, "65x3_a2", "refuse", 3, [{0: 1}, {1: 1}, {2: 1}, {0: 1, 1: 2}] + _rows(rng, 3, [2] * 61, [1, -1]), refusal="PLO_E_CAPACITY")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- trilinear
+TRIL_RATS = [F(1), F(-1), F(1, 2), F(-2), F(3), F(-2, 3), F(1000003, 7)]
+TRIL_VARIANTS = [("unit", UNIT, False), ("rat", TRIL_RATS, False), ("unit_e", UNIT, True), ("rat_e", TRIL_RATS, True)]
+TRIL_SEEDS3 = [BASE_SEED, 0, (1 << 64) - 2]                      # the two programs near the 160 KiB of LDS
+TRIL_TIE_N = 1000
+
+
+def tril_layout(m, nnz, expanded):
+    """(cap, lds_per_wave, waves per workgroup, LDS bytes of a workgroup) as plo_tril_plan_create_q sizes them; nnz of A, B, T"""
+    cap = max(2 * z + 3 * m for z in nnz)
+    if expanded:
+        cap = max(cap, 4 * nnz[2] + 6 * m)
+    cap = _ru(cap + 2, 64)
+    per_wave = _ru(8 * cap + 2 * ((m + 1) & ~1) + m, 16) + 16 * ((cap + 63) // 64)
+    waves = 4 if 4 * per_wave <= WG_LDS else 1
+    return cap, per_wave, waves, waves * per_wave
+
+
+def tril_refusal(m, mats, expanded):
+    """None when the device takes the triple, else the name of the header's code (include/plinopt_hip.h, plo_tril_*), in the
+    order plo_tril_plan_create_q checks; mats: three (n, entries)"""
+    if m > 16382:
+        return "PLO_E_CAPACITY"
+    for w, (n, ent) in enumerate(mats):
+        assert 0 < n <= 16382
+        if len(ent) > 65535:
+            return "PLO_E_CAPACITY"
+        lens = [0] * m
+        for (i, _), v in sorted(ent.items()):
+            lens[i] += 1
+        for i in range(m):
+            if lens[i] == 0 or lens[i] > 64:
+                return "PLO_E_UNSUPPORTED"
+            if any(v.numerator % LIN_PRIME == 0 or v.denominator % LIN_PRIME == 0 for (r, _), v in ent.items() if r == i):
+                return "PLO_E_UNSUPPORTED"
+        if expanded and w == 2 and n >= 16382:
+            return "PLO_E_CAPACITY"
+    if tril_layout(m, [len(e) for _, e in mats], expanded)[3] > LDS_MAX:
+        return "PLO_E_CAPACITY"
+    return None
+
+
+def tril_text(c):
+    return "expanded %d\n" % c.expanded + "".join(sms_text(c.m, n, e) for n, e in c.mats)
+
+
+def tril_quick(cap, unit):
+    """The cases whose goldens tests/test_synth_golden.py recomputes, by a fixed rule on the program's capacity (the
+    oracle's time follows the length of the longest of the three programs; rationals cost about twice as much)"""
+    return cap * (1 if unit else 2) <= 6000
+
+
+def _tril_case(out, name, family, m, mats, expanded, refusal=None, quick=None, seeds=None):
+    """mats: three (n, rows) for A, B and T (the transposed product matrix), rows as {column: value}"""
+    assert len(mats) == 3 and all(len(rows) == m and all(0 <= j < n for r in rows for j in r) for n, rows in mats), name
+    ents = [(n, {(i, j): F(v) for i, r in enumerate(rows) for j, v in r.items()}) for n, rows in mats]
+    got = tril_refusal(m, ents, expanded)
+    assert got == refusal, (name, got)
+    by_list = len(out) % 2 == 0 or seeds is not None
+    unit = all(v in (1, -1) for _, e in ents for v in e.values())
+    cap, per_wave, waves, lds = tril_layout(m, [len(e) for _, e in ents], expanded)
+    c = SimpleNamespace(name="tril_%s_%s" % (family, name), family=family, m=m, mats=ents, expanded=bool(expanded), refusal=refusal,
+                        mode="list" if by_list else "runs", seeds=list(seeds or (SEEDS_LIST if by_list else SEEDS_RUNS)), unit=unit,
+                        cap=cap, lds_per_wave=per_wave, waves=waves, lds=lds, quick=(tril_quick(cap, unit) if quick is None else quick) and not refusal)
+    c.sha256 = _sha(tril_text(c))
+    assert c.name not in [x.name for x in out], c.name
+    out.append(c)
+    return c
+
+
+def tril_args(c):
+    """the three (n, rowptr, col, num, den) of plinopt_amd.TrilPlan"""
+    return [qcsr(c.m, n, e)[1:] for n, e in c.mats]
+
+
+def _spread(m, total):
+    """row lengths that sum to total, as even as possible"""
+    return [total // m + (1 if i < total % m else 0) for i in range(m)]
+
+
+def tril_cases():
+    """About 80 triples (A, B, T) at the edges of tril_kernel, t_linear with permutation and signs, t_double and
+    t_pushvariables_ref, and six the device refuses.  Every row is non-empty."""
+    rng = random.Random(0x7A11)
+    out = []
+    short = lambda m, n, vals: _rows(rng, n, [1 + rng.randrange(min(3, n)) for _ in range(m)], vals)  # noqa: E731
+    # (a) row-count edges with 3..9 variables per matrix, the three counts different
+    for m in (1, 2, 63, 64, 65, 129):
+        for fl, vals, ex in TRIL_VARIANTS:
+            ns = _sample(rng, range(3, 10), 3)
+            _tril_case(out, "m%d_%s" % (m, fl), "a", m, [(n, short(m, n, vals)) for n in ns], ex)
+    # (b) row lengths: a row of 64 entries in A only, in B only, in T only and in all three (20 rows, 64 variables), every row
+    # of length 1, and a single row of 64 entries under -e
+    for where in ("A", "B", "T", "ABT"):
+        for fl, vals, ex in TRIL_VARIANTS:
+            mats = []
+            for x in "ABT":
+                lens = [1 + rng.randrange(4) for _ in range(20)]
+                if x in where:
+                    lens[rng.randrange(20)] = 64
+                mats.append((64, _rows(rng, 64, lens, vals)))
+            _tril_case(out, "row64_%s_%s" % (where, fl), "b", 20, mats, ex)
+    for fl, vals, ex in TRIL_VARIANTS:
+        _tril_case(out, "len1_%s" % fl, "b", 12, [(n, _rows(rng, n, [1] * 12, vals)) for n in (5, 7, 4)], ex)
+    for fl, vals, ex in TRIL_VARIANTS[2:]:
+        _tril_case(out, "m1_T64_%s" % fl, "b", 1, [(3, _rows(rng, 3, [2], vals)), (4, _rows(rng, 4, [3], vals)), (64, _rows(rng, 64, [64], vals))], ex)
+    # (c) the row forms of t_double (expanded only): the row's first column i with column i + 1 present and absent, pivot +-1,
+    # 3 and 1/2, the first entry in the last column, single-entry rows of each kind
+    for fl, vals, piv in (("unit_e", UNIT, [F(1), F(-1), F(-1), F(1)]), ("rat_e", TRIL_RATS, [F(1), F(-1), F(3), F(1, 2)])):
+        v = lambda: _pick(rng, vals)  # noqa: E731
+        T = []
+        for a in piv:
+            T += [{2: a, 3: v(), 5: v()}, {1: a, 4: v(), 6: v()}, {5: a, 6: v()}, {0: a, 7: v()}, {7: a}, {3: a}, {6: a, 7: v()}]
+        m = len(T)
+        _tril_case(out, "forms_%s" % fl, "c", m, [(5, short(m, 5, vals)), (6, short(m, 6, vals)), (8, T)], True)
+    # (d) variable indices: the 14-bit src/des fields of the rational atom next to the "none" code 0x3FFF
+    for fl, vals, ex in TRIL_VARIANTS:
+        mats = []
+        for n in (16382, 16382, 16381 if ex else 16382):
+            pool = [0, 1, n // 2, n - 3, n - 2, n - 1]
+            rows = [{0: vals[0], n - 1: vals[1], n - 2: vals[0]}, {n - 1: vals[1], 1: vals[0], 0: vals[1]}] + _rows(rng, n, [3] * 10, vals, pool)
+            mats.append((n, rows))
+        _tril_case(out, "n16382_%s" % fl, "d", 12, mats, ex)
+    # (e) LDS: four waves of a workgroup just under and just over 64 KiB (the switch to one wave per workgroup), 300x64 and
+    # 200x64, and two programs near the 160 KiB of a CU
+    for fl, vals, ex in TRIL_VARIANTS:
+        for side, tot in (("under", 320 if ex else 800), ("over", 336 if ex else 832)):
+            lens = {"A": _spread(100, 300), "B": _spread(100, 300), "T": _spread(100, 300)}
+            lens["T" if ex else "A"] = _spread(100, tot)
+            c = _tril_case(out, "%s64k_%s" % (side, fl), "e", 100, [(40, _rows(rng, 40, lens[x], vals)) for x in "ABT"], ex)
+            assert c.waves == (4 if side == "under" else 1) and abs(4 * c.lds_per_wave - WG_LDS) < 1200, (c.name, c.lds_per_wave)
+    c = _tril_case(out, "300x64_unit", "e", 300, [(64, _rows(rng, 64, [1 + rng.randrange(4) for _ in range(300)], UNIT)) for _ in range(3)], False)
+    assert c.waves == 1
+    c = _tril_case(out, "200x64_rat_e", "e", 200, [(64, _rows(rng, 64, [1 + rng.randrange(4) for _ in range(200)], TRIL_RATS)) for _ in range(3)], True)
+    assert c.waves == 1
+    c = _tril_case(out, "1200x200_unit", "e", 1200, [(200, _rows(rng, 200, [5] * 1200, UNIT)) for _ in range(3)], False, quick=False, seeds=TRIL_SEEDS3)
+    assert c.waves == 1 and 128 * 1024 < c.lds <= LDS_MAX
+    c = _tril_case(out, "600x200_rat_e", "e", 600, [(200, _rows(rng, 200, [5] * 600, TRIL_RATS)) for _ in range(3)], True, quick=False, seeds=TRIL_SEEDS3)
+    assert c.waves == 1 and 127 * 1024 < c.lds <= LDS_MAX
+    assert all(c.waves == 4 for c in out if c.family in "abcd")
+    # refusals
+    ok = lambda m, n: _rows(rng, n, [2] * m, UNIT)  # noqa: E731
+    U, C = "PLO_E_UNSUPPORTED", "PLO_E_CAPACITY"
+    _tril_case(out, "empty_row", "refuse", 4, [(5, ok(4, 5)), (5, _rows(rng, 5, [2, 0, 1, 2], UNIT)), (5, ok(4, 5))], False, refusal=U)
+    _tril_case(out, "row65", "refuse", 3, [(70, ok(3, 70)), (70, ok(3, 70)), (70, _rows(rng, 70, [2, 65, 3], UNIT))], False, refusal=U)
+    _tril_case(out, "T16382_e", "refuse", 3, [(5, ok(3, 5)), (5, ok(3, 5)), (16382, [{0: 1, 16381: -1}, {1: 1}, {16380: 1, 16381: 1}])], True, refusal=C)
+    _tril_case(out, "num_prime", "refuse", 3, [(5, [{0: 1, 1: F(LIN_PRIME, 3)}, {2: 1}, {3: -1}]), (5, ok(3, 5)), (5, ok(3, 5))], False, refusal=U)
+    _tril_case(out, "den_prime", "refuse", 3, [(5, ok(3, 5)), (5, ok(3, 5)), (5, [{0: 1}, {2: F(2, LIN_PRIME)}, {3: -1}])], True, refusal=U)
+    _tril_case(out, "m16383", "refuse", 16383, [(5, _rows(rng, 5, [1] * 16383, UNIT)) for _ in range(3)], False, refusal=C)
+    return out
+
+
+def tril_tie_cases():
+    """two tiny triples whose candidates tie all the time: the argmin under (ADD, SCA, seed, variant)"""
+    rng = random.Random(0x71E7)
+    out = []
+    _tril_case(out, "2x2_unit", "tie", 2, [(2, _rows(rng, 2, [2, 1], UNIT)), (2, _rows(rng, 2, [1, 2], UNIT)), (2, _rows(rng, 2, [2, 2], UNIT))], False)
+    _tril_case(out, "3x3_rat_e", "tie", 3, [(3, _rows(rng, 3, [2, 1, 2], TRIL_RATS)), (2, _rows(rng, 2, [1, 2, 1], TRIL_RATS)), (3, _rows(rng, 3, [2, 2, 1], TRIL_RATS))], True)
+    return out

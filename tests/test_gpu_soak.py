@@ -14,6 +14,10 @@ against the product's host engines.
                         workgroup, 160 KiB of LDS) x 11 seeds, against tests/lin_oracle.py                  (test_gpu_lin_orbit_synth.py)
   orbit                45 edge-shape triples (dimensions 1 to 16, 1/2/4 waves per workgroup, composite and 31-bit
                         moduli, Q next to the int64 bound) x 11 seeds, against tests/orbit_oracle.py        (test_gpu_lin_orbit_synth.py)
+  kernel method        43 edge-shape matrices (128 x 64 with rank 64 and 64 dependent rows, rows of 64 entries, empty
+                        rows, moduli 3 to 2^31 - 1, 4/2/1 waves per workgroup) x 11 restarts, against the C oracle  (test_gpu_kmethod_tril_synth.py)
+  in-place trilinear   64 edge-shape triples (1 to 1200 rows, 64-entry rows, the row forms of `-e`, variable 16381,
+                        the 64 KiB switch, 130 KiB of LDS) x 11 seeds (3 near 160 KiB), against the C oracle  (test_gpu_kmethod_tril_synth.py)
 
 A refusal the header documents (PLO_E_CAPACITY / PLO_E_UNSUPPORTED) is counted and bounded, anything else fails."""
 import os
