@@ -296,21 +296,43 @@ int  plo_lin_search_multi(const plo_qcsr_t *A, uint64_t seed0, uint64_t nseeds, 
  * CandRng of the seed (splitmix64, then x <- 950706376 x mod 2^31-1); U (m x m), then V (k x k), then W (n x n), each of size
  * s drawn as: P by Fisher-Yates (for i = s down to 2, swap P[i-1] and P[next() % i]), Q the same way, D[i] = next() & 1 for
  * i = 0..s-1, then row-major for i < j: M[P[i]][Q[j]] = next() % 3 - 1; the diagonal M[P[i]][Q[i]] = D[i] ? 1 : -1.
- * seed == PLO_ORBIT_BASE_SEED is U = V = W = identity: the input itself.
+ * That is the action PLO_ORBIT_ACT_TRIANGULAR (0), the default.  The reference offers two other distributions at compile
+ * time (ACTION_FULL_PLUQ :77-96, ACTION_HOUSEHOLDER :98-123); here the action is a run-time choice of the plan.  For every
+ * action a matrix of size s starts alike: P, then Q, then D as above.  Then:
+ *   PLO_ORBIT_ACT_PLUQ (1): Lambda lower triangular, Lambda[i][i] = D[i] ? 1 : -1, then row-major for j < i
+ *     Lambda[i][j] = next() % 3 - 1; then for i = 0..s-1 a vector u_i with u_i[Q[i]] = 1, u_i[j] = next() % 3 - 1 for
+ *     j = 0..Q[i]-1 in that order and zeros behind; row P[i] of M is Lambda.u_i: M[P[i]][c] = sum_j Lambda[c][j] u_i[j].
+ *     M = Pi_P Um Lambda^T (Um: the rows u_i, unit lower triangular once sorted by Q[i]): det +-1 and an integral inverse.
+ *   PLO_ORBIT_ACT_HOUSEHOLDER (2): u[i] = next() % 3 - 1 for i = 0..s-1, d = sum u[i]^2.  When d is a unit of the run's field
+ *     (d != 0 over Q; gcd(d, modulus) = 1 modulo a number) M[P[i]][Q[j]] = +-(delta_ij - 2 u[i] u[j] / d) with the sign of
+ *     D[i] (an orthogonal matrix over Q), otherwise M is the signed permutation M[P[i]][Q[i]] = +-1.  (The reference tests
+ *     d == 0 only and would divide by a non-unit of a composite modulus; the permutation branch there is this build's reading.)
+ * U is drawn first, then V, then W, for every action.
+ * seed == PLO_ORBIT_BASE_SEED is U = V = W = identity, for every action: the input itself.
  * Order: the lexicographic minimum of (cost, nnz, nno, seed); the tool's winner improves on the input iff its (cost, nnz, nno)
  * is smaller than the input's.
  * modulus 0 is Q: the rows of L and R and the columns of P are scaled to integers on the host, and the counts are exact.
  * PLO_E_UNSUPPORTED: a modulus of 2^31 or more, a denominator that is no unit modulo the modulus, or a Q input whose
- * transformed entries are not provably below 2^62 (row L1 norm times 2^(s-2)).  PLO_E_CAPACITY: m, k or n above 16, more
+ * transformed entries are not provably below 2^62: the row's L1 norm (after scaling) times the entry bounds of the part's two
+ * factors, a direct one of size sd and an inverse of size si ((sd, si) = (k, m) for L, (n, k) for R, (m, n) for P), must stay
+ * below 2^62.  TRIANGULAR: 1 x 2^(si-2).  PLUQ: sd x si 4^(si-2) (1 for si = 1).  HOUSEHOLDER: sd x si (numerators over d), and
+ * the row's scale times sd si as well.  PLO_E_CAPACITY: m, k or n above 16, more
  * than 4096 rows, 2^21 transformed entries or more, or an input that does not fit LDS.  PLO_E_ARG: shapes that are not
- * m k, k n, m n. */
+ * m k, k n, m n, or an unknown action. */
 #define PLO_ORBIT_BASE_SEED 0xFFFFFFFFFFFFFFFFull     /* U = V = W = identity: the input itself */
 #define PLO_ORBIT_DENSITY   0                          /* -s */
 #define PLO_ORBIT_CANONICAL 2                          /* -c */
+#define PLO_ORBIT_ACT_TRIANGULAR  0                    /* signed permutation times one triangle (the default) */
+#define PLO_ORBIT_ACT_PLUQ        1                    /* a product of two triangles */
+#define PLO_ORBIT_ACT_HOUSEHOLDER 2                    /* an orthogonal reflection, or a signed permutation */
 typedef struct { uint32_t cost, nnz, nno, reserved; uint64_t seed; } plo_orbit_best_t;
 typedef struct plo_orbit_plan plo_orbit_plan_t;
 int  plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P,
                              uint64_t modulus /* 0 = Q */, int measure, plo_orbit_plan_t **plan);
+/* the same with the action (PLO_ORBIT_ACT_*); plo_orbit_plan_create_q is action PLO_ORBIT_ACT_TRIANGULAR.  The functions
+ * below serve the plans of every action. */
+int  plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P,
+                               uint64_t modulus /* 0 = Q */, int measure, int action, plo_orbit_plan_t **plan);
 void plo_orbit_plan_destroy(plo_orbit_plan_t *plan);
 /* out3[3k..3k+2] = cost, nnz, nno of candidate k (seeds[k], or seed0+k when seeds==NULL) */
 int  plo_orbit_cost_many(plo_orbit_plan_t *plan, const uint64_t *seeds, uint64_t seed0, uint64_t n,
@@ -320,6 +342,8 @@ int  plo_orbit_search(plo_orbit_plan_t *plan, uint64_t seed0, uint64_t nseeds, p
  * and plan each, the minimum under (cost, nnz, nno, seed).  Same conventions for devices, stats and PLO_MULTI_REDUCE. */
 int  plo_orbit_search_multi(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure,
                             uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats);
+int  plo_orbit_search_multi_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action,
+                                uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats);
 
 /* ---- Row-dependency enumeration: the search of the reference's `dependency` (src/dependency.cpp:74-101, 158-165).  M (m x n) as
  * rational CSR, `ncoef` coefficients cnum[v]/cden[v] (the caller's FCoeffs, in order), `level` the largest number of rows in a

@@ -1,6 +1,6 @@
 // ==========================================================================
 // bin/orbiter -- the De Groote orbit search of a matrix-multiplication triple (reference src/orbiter.cpp):
-//   orbiter [-b bits] [-m|-q mod] [-r r e s] [-s|-c] [-O loops] [--seed s] [--gpu 0|1|N] L.sms R.sms P.sms
+//   orbiter [-b bits] [-m|-q mod] [-r r e s] [-s|-c] [-O loops] [--seed s] [--gpu 0|1|N] [--action a] L.sms R.sms P.sms
 // Searches the candidates (U, V, W) s .. s+O-1 (plo_orbit_*, include/plinopt_hip.h) for an equivalent triple with a smaller
 // (cost, nnz, nno); when the best one improves on the input, writes <L>.nnz.sms, <R>.nnz.sms, <P>.nnz.sms next to the inputs.
 // clog: the reference's '#' lines (Init. ops, Search(N), Rdcd. opt) and the exact matrix-multiplication checks of the input
@@ -9,6 +9,8 @@
 // The restarts run on the GPU through plo_orbit_search[_multi] of libplinopt_hip.so; --gpu 0, or an input the device refuses
 // (a modulus of 2^31 or more, a Q input outside its int64 bound, sizes beyond its limits), uses the host loop (OpenMP) and
 // says so.  -b is accepted for the reference's command lines: the checks here are exact.
+// --action triangular|pluq|householder chooses how U, V and W are drawn (PLO_ORBIT_ACT_*; the reference's compile-time
+// ACTION_FULL_PLUQ and ACTION_HOUSEHOLDER, src/orbiter.cpp:77-123), for the search, --costs and --candidate alike.
 // Refused with status 2: -z over Q, -P/-I, shapes that are not mk, kn, mn, a denominator that is no unit modulo the modulus, a
 // modulus above 2^63.  Testing aids: --costs prints `cost nnz nno` of the base candidate, then of seeds s .. s+O-1 (host);
 // --candidate s|base DIR writes the three matrices of one candidate to DIR/{L,R,P}.sms.
@@ -24,12 +26,12 @@ namespace {
 struct HipOrbit {
     void *h = open_hip_lib(); bool ok = h != nullptr;
     PLO_SYM(init, plo_init); PLO_SYM(last_error, plo_last_error);
-    PLO_SYM(create, plo_orbit_plan_create_q); PLO_SYM(destroy, plo_orbit_plan_destroy);
-    PLO_SYM(search, plo_orbit_search); PLO_SYM(search_multi, plo_orbit_search_multi);
+    PLO_SYM(create, plo_orbit_plan_create_act); PLO_SYM(destroy, plo_orbit_plan_destroy);
+    PLO_SYM(search, plo_orbit_search); PLO_SYM(search_multi, plo_orbit_search_multi_act);
 };
 
 struct Opts {
-    size_t loops = 100; uint64_t seed0 = 0; int gpu = 1; int measure = ORBIT_DENSITY; bool cse = false;
+    size_t loops = 100; uint64_t seed0 = 0; int gpu = 1; int measure = ORBIT_DENSITY; int action = ORBIT_ACT_TRIANGULAR; bool cse = false;
     unsigned __int128 modulus = 0; bool costs = false, cand = false; uint64_t cseed = 0; std::string cdir;
 };
 
@@ -46,7 +48,7 @@ template <class F> int mm_report(const F &f, const OrbitTriple<F> &T) {
     try { ok = orbit_mm_check(f, T); } catch (const std::exception &e) { why = e.what(); }
     const std::string shape = std::to_string(T.m) + 'x' + std::to_string(T.k) + 'x' + std::to_string(T.n);
     if (ok) {
-        OrbitCount c = orbit_candidate(f, T, ORBIT_BASE, ORBIT_DENSITY);
+        OrbitCount c = orbit_candidate(f, T, ORBIT_BASE, ORBIT_DENSITY, ORBIT_ACT_TRIANGULAR);
         std::clog << "# \033[1;32mSUCCESS: correct " << shape << " (" << c.nnz << ',' << c.nno << ") Matrix-Multiplication over " << f.name() << " \033[0m" << std::endl;
         return 0;
     }
@@ -60,20 +62,20 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
     T.L = rebind(QL, f); T.R = rebind(QR, f); T.PT = rebind(transpose(QP), f); T.m = m; T.k = k; T.n = n;
     const int measure = modulus ? ORBIT_DENSITY : o.measure;
     if (o.costs) {
-        auto line = [&](uint64_t s) { const OrbitCount c = orbit_candidate(f, T, s, measure); std::cout << c.cost << ' ' << c.nnz << ' ' << c.nno << '\n'; };
+        auto line = [&](uint64_t s) { const OrbitCount c = orbit_candidate(f, T, s, measure, o.action); std::cout << c.cost << ' ' << c.nnz << ' ' << c.nno << '\n'; };
         line(ORBIT_BASE);
         for (uint64_t j = 0; j < o.loops; ++j) line(o.seed0 + j);
         return 0;
     }
     if (o.cand) {
-        OrbitTriple<F> C; const OrbitCount c = orbit_candidate(f, T, o.cseed, measure, &C);
+        OrbitTriple<F> C; const OrbitCount c = orbit_candidate(f, T, o.cseed, measure, o.action, &C);
         std::filesystem::create_directories(o.cdir);
         write_triple(f, C, o.cdir + "/L.sms", o.cdir + "/R.sms", o.cdir + "/P.sms", modulus ? 'M' : 'R');
         std::clog << "# candidate " << (o.cseed == ORBIT_BASE ? std::string("base") : std::to_string(o.cseed)) << ": " << c.cost << ' ' << c.nnz << ' ' << c.nno << std::endl;
         return 0;
     }
     const int input_bad = mm_report(f, T);                                               // :263, printed then ignored
-    const OrbitCount init = orbit_candidate(f, T, ORBIT_BASE, measure);
+    const OrbitCount init = orbit_candidate(f, T, ORBIT_BASE, measure, o.action);
     std::clog << "# Init. ops: " << init.cost << ", (" << init.nnz << ',' << init.nno << ')' << std::endl;
     const auto t0 = std::chrono::steady_clock::now();
     using Key = std::tuple<size_t, size_t, size_t, uint64_t>;                             // (cost, nnz, nno, seed)
@@ -92,11 +94,11 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
                 int rc;
                 if (o.gpu >= 2) {
                     std::vector<int> devs((size_t)o.gpu); for (int j = 0; j < o.gpu; ++j) devs[(size_t)j] = shard_device(j);
-                    rc = H.search_multi(&l, &r, &p, modulus, measure, o.seed0, o.loops, o.gpu, devs.data(), &b, &st);
+                    rc = H.search_multi(&l, &r, &p, modulus, measure, o.action, o.seed0, o.loops, o.gpu, devs.data(), &b, &st);
                 } else {
                     rc = H.init(0);
                     plo_orbit_plan_t *plan = nullptr;
-                    if (rc == PLO_OK) rc = H.create(&l, &r, &p, modulus, measure, &plan);
+                    if (rc == PLO_OK) rc = H.create(&l, &r, &p, modulus, measure, o.action, &plan);
                     // (a launch takes at most 2^31-1 candidates: longer runs go in pieces, minimum under the same order)
                     for (uint64_t done = 0; rc == PLO_OK && done < o.loops;) {
                         const uint64_t piece = std::min<uint64_t>(o.loops - done, (1ull << 31) - 1ull);
@@ -128,7 +130,7 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
                 #pragma omp for schedule(dynamic, 16)
                 for (long long j = 0; j < (long long)o.loops; ++j) {
                     try {
-                        const OrbitCount c = orbit_candidate(f, T, o.seed0 + (uint64_t)j, measure);
+                        const OrbitCount c = orbit_candidate(f, T, o.seed0 + (uint64_t)j, measure, o.action);
                         tb = std::min(tb, Key{c.cost, c.nnz, c.nno, o.seed0 + (uint64_t)j});
                     } catch (const std::exception &e) {
                         #pragma omp critical
@@ -149,7 +151,7 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
     if (improved) {
         const uint64_t seed = std::get<3>(best);
         OrbitTriple<F> W;
-        const OrbitCount rc = orbit_candidate(f, T, seed, measure, &W);
+        const OrbitCount rc = orbit_candidate(f, T, seed, measure, o.action, &W);
         if (!(rc == bc)) {
             std::cerr << "# \033[1;31mERROR: replay of seed " << seed << " gives " << rc.cost << ' ' << rc.nnz << ' ' << rc.nno << ", search said " << bc.cost << ' ' << bc.nnz << ' ' << bc.nno << "\033[0m\n";
             return 3;
@@ -177,13 +179,14 @@ QMat read_file(const std::string &f) {
 }
 
 int usage(const char *prg, const Opts &o) {
-    std::clog << "Usage: " << prg << " [-b #] [-m|-q #] [-r # # #] [-s|-c] [-O #] [--seed s] [--gpu 0|1|N] L.sms R.sms P.sms\n"
+    std::clog << "Usage: " << prg << " [-b #] [-m|-q #] [-r # # #] [-s|-c] [-O #] [--seed s] [--gpu 0|1|N] [--action a] L.sms R.sms P.sms\n"
               << "  [-b b]: accepted (the matrix-multiplication checks are exact)\n"
               << "  [-m/-q m]: search modulo m without its factors 2 (default Q)\n"
               << "  [-r r e s]: search modulo (r^e-s) without its factors 2\n"
               << "  [-s|-c]: search sparser|canonical (default sparser; always sparser modulo a number)\n"
               << "  [-O #]: randomized search with that many loops (default " << o.loops << " loops)\n"
               << "  [--seed s]: candidates s .. s+O-1 (default 0); [--gpu 0|1|N]: host loop, one GPU, N GPU shards (default 1)\n"
+              << "  [--action triangular|pluq|householder]: how U, V and W are drawn (default triangular)\n"
               << "  testing aids: --costs (per-seed counts on the host), --candidate s|base DIR (one candidate's matrices)\n";
     return -1;
 }
@@ -221,6 +224,11 @@ int main(int argc, char **argv) {
             else if (a == "-z") o.cse = true;
             else if (a == "--seed") { need(1); o.seed0 = strtoull(argv[++i], nullptr, 10); }
             else if (a == "--gpu") { need(1); o.gpu = atoi(argv[++i]); }
+            else if (a == "--action") {
+                need(1); const std::string w(argv[++i]);
+                if (w == "triangular") o.action = ORBIT_ACT_TRIANGULAR; else if (w == "pluq") o.action = ORBIT_ACT_PLUQ;
+                else if (w == "householder") o.action = ORBIT_ACT_HOUSEHOLDER; else return refuse("unknown action " + w + " (triangular, pluq or householder)");
+            }
             else if (a == "--costs") o.costs = true;
             else if (a == "--candidate") { need(2); const std::string s(argv[++i]); o.cand = true; o.cseed = s == "base" ? ORBIT_BASE : strtoull(s.c_str(), nullptr, 10); o.cdir = argv[++i]; }
             else if (!a.empty() && a[0] == '-') return refuse("unknown option " + a);

@@ -5,7 +5,9 @@
 // matrices, row i of L (m x k) becomes U^-T X V, row i of R (k x n) becomes V^-1 Y W and column j of P (m x n) becomes
 // U Z W^-T: the "sandwich" form, without the Kronecker products.  U = Pi_P T Pi_Q^T with T upper triangular, +-1 on
 // its diagonal and {-1, 0, 1} above, so U^-1 = Pi_Q T^-1 Pi_P^T is integral (back-substitution, entries of size at most
-// 2^(s-2)).  The same function scores a candidate in the host loop and replays the winner.
+// 2^(s-2)).  That is the default action; ORBIT_ACT_PLUQ draws a product of two triangles (integral inverse by two
+// substitutions) and ORBIT_ACT_HOUSEHOLDER an orthogonal matrix, kept as integer numerators over one denominator d.
+// The same function scores a candidate in the host loop and replays the winner.
 // ==========================================================================
 #pragma once
 #include "plo_host.hpp"
@@ -13,10 +15,75 @@
 namespace plo {
 
 enum { ORBIT_DENSITY = 0, ORBIT_CANONICAL = 2 };
+enum { ORBIT_ACT_TRIANGULAR = 0, ORBIT_ACT_PLUQ = 1, ORBIT_ACT_HOUSEHOLDER = 2 };
 constexpr uint64_t ORBIT_BASE = ~0ull;
 
-// M (s x s, row-major) and its inverse, integers
-struct Zoi { size_t s = 0; std::vector<int64_t> M, Mi; };
+// M (s x s, row-major) and its inverse: integer numerators over the denominator den (1 but for a Householder matrix)
+struct Zoi { size_t s = 0; std::vector<int64_t> M, Mi; int64_t den = 1; };
+
+// d is a unit of the run's field: d != 0 over Q, gcd(d, modulus) = 1 modulo a number
+inline bool orbit_unit(const QField &, int64_t d) { return d != 0; }
+inline bool orbit_unit(const ZpField &f, int64_t d) { return std::gcd((uint64_t)d, (uint64_t)f.p) == 1; }
+inline bool orbit_unit(const Zp64Field &f, int64_t d) { return std::gcd((uint64_t)d, f.p) == 1; }
+
+// what every action draws first: Fisher-Yates P, then Q, then the s sign bits
+struct ZoiStart { std::vector<size_t> P, Q; std::vector<int64_t> D; };
+inline ZoiStart zoi_start(CandRng &rng, size_t s) {
+    ZoiStart z; z.P.resize(s); z.Q.resize(s); z.D.resize(s);
+    std::iota(z.P.begin(), z.P.end(), 0); std::iota(z.Q.begin(), z.Q.end(), 0);
+    for (auto *perm : {&z.P, &z.Q})
+        for (size_t i = s; i > 1; --i) std::swap((*perm)[i - 1], (*perm)[rng.next() % i]);
+    for (size_t i = 0; i < s; ++i) z.D[i] = (rng.next() & 1u) ? 1 : -1;
+    return z;
+}
+
+// ORBIT_ACT_PLUQ (reference src/orbiter.cpp:78-96): Lambda lower triangular (D on the diagonal, then the strict lower part
+// row-major), then s vectors u_i (1 at Q[i], draws before, zeros behind); row P[i] of M is Lambda.u_i.  M = Pi_P Um Lambda^T
+// with Um[i] = u_i = row Q[i] of the unit lower triangular Lu, so M^-1[a][P[i]] = sum_b Lambda^-1[b][a] Lu^-1[b][Q[i]].
+inline Zoi zoi_pluq(CandRng &rng, size_t s) {
+    const ZoiStart z = zoi_start(rng, s);
+    std::vector<int64_t> La(s * s, 0), Lu(s * s, 0), Lai(s * s, 0), Lui(s * s, 0);
+    for (size_t i = 0; i < s; ++i) La[i * s + i] = z.D[i];
+    for (size_t i = 0; i < s; ++i) for (size_t j = 0; j < i; ++j) La[i * s + j] = (int64_t)(rng.next() % 3u) - 1;
+    for (size_t i = 0; i < s; ++i) {
+        const size_t q = z.Q[i];
+        Lu[q * s + q] = 1;
+        for (size_t j = 0; j < q; ++j) Lu[q * s + j] = (int64_t)(rng.next() % 3u) - 1;
+    }
+    // inverses of the lower triangles by forward substitution, column by column
+    for (const auto &pr : {std::make_pair(&La, &Lai), std::make_pair(&Lu, &Lui)}) {
+        const std::vector<int64_t> &T = *pr.first; std::vector<int64_t> &Ti = *pr.second;
+        for (size_t j = 0; j < s; ++j)
+            for (size_t i = j; i < s; ++i) {
+                int64_t acc = i == j ? 1 : 0;
+                for (size_t l = j; l < i; ++l) acc -= T[i * s + l] * Ti[l * s + j];
+                Ti[i * s + j] = T[i * s + i] * acc;
+            }
+    }
+    Zoi r; r.s = s; r.M.assign(s * s, 0); r.Mi.assign(s * s, 0);
+    for (size_t i = 0; i < s; ++i) for (size_t c = 0; c < s; ++c) {
+        int64_t a = 0, b = 0;
+        for (size_t j = 0; j < s; ++j) { a += La[c * s + j] * Lu[z.Q[i] * s + j]; b += Lai[j * s + c] * Lui[j * s + z.Q[i]]; }
+        r.M[z.P[i] * s + c] = a; r.Mi[c * s + z.P[i]] = b;
+    }
+    return r;
+}
+
+// ORBIT_ACT_HOUSEHOLDER (reference :99-123): u in {-1, 0, 1}^s, d = u.u; N = diag(D) (I - 2 u u^T / d) when d is a unit, else
+// diag(D); N^-1 = (I - 2 u u^T / d) diag(D).  M[P[i]][Q[j]] = N[i][j], M^-1[Q[i]][P[j]] = N^-1[i][j]; numerators over d.
+template <class F> Zoi zoi_householder(const F &f, CandRng &rng, size_t s) {
+    const ZoiStart z = zoi_start(rng, s);
+    std::vector<int64_t> u(s);
+    int64_t d = 0;
+    for (size_t i = 0; i < s; ++i) { u[i] = (int64_t)(rng.next() % 3u) - 1; d += u[i] * u[i]; }
+    const bool refl = orbit_unit(f, d);
+    Zoi r; r.s = s; r.M.assign(s * s, 0); r.Mi.assign(s * s, 0); r.den = refl ? d : 1;
+    for (size_t i = 0; i < s; ++i) for (size_t j = 0; j < s; ++j) {
+        const int64_t h = refl ? (i == j ? d : 0) - 2 * u[i] * u[j] : (i == j ? 1 : 0);
+        r.M[z.P[i] * s + z.Q[j]] = z.D[i] * h; r.Mi[z.Q[i] * s + z.P[j]] = h * z.D[j];
+    }
+    return r;
+}
 
 // the stream's matrix: Fisher-Yates P, then Q, then the s sign bits, then the strict upper part row-major
 inline Zoi zoi_matrix(CandRng &rng, size_t s) {
@@ -41,11 +108,16 @@ inline Zoi zoi_matrix(CandRng &rng, size_t s) {
 inline Zoi zoi_identity(size_t s) { Zoi z; z.s = s; z.M.assign(s * s, 0); for (size_t i = 0; i < s; ++i) z.M[i * s + i] = 1; z.Mi = z.M; return z; }
 
 struct OrbitUVW { Zoi U, V, W; };
-inline OrbitUVW orbit_uvw(size_t m, size_t k, size_t n, uint64_t seed) {
+template <class F> OrbitUVW orbit_uvw(const F &f, size_t m, size_t k, size_t n, uint64_t seed, int action) {
     if (seed == ORBIT_BASE) return {zoi_identity(m), zoi_identity(k), zoi_identity(n)};
     CandRng rng(seed);
+    auto draw = [&](size_t s) {
+        if (action == ORBIT_ACT_PLUQ) return zoi_pluq(rng, s);
+        if (action == ORBIT_ACT_HOUSEHOLDER) return zoi_householder(f, rng, s);
+        return zoi_matrix(rng, s);
+    };
     OrbitUVW c;
-    c.U = zoi_matrix(rng, m); c.V = zoi_matrix(rng, k); c.W = zoi_matrix(rng, n);
+    c.U = draw(m); c.V = draw(k); c.W = draw(n);
     return c;
 }
 
@@ -70,14 +142,15 @@ inline bool operator==(const OrbitCount &a, const OrbitCount &b) { return std::t
 template <class F> struct OrbitTriple { SparseMat<typename F::Elt> L, R, PT; size_t m = 0, k = 0, n = 0; };
 
 // one part of the sandwich: out_i(p, q) = sum over the entries (a, b, x) of row i of A[a][p] x B[b][q], for the rows of X
-// (columns a * cb + b; output pr x qc); A is sa x sa, B is sb x sb (row-major); Out gets the rows when asked
-template <class F> void orbit_part(const F &f, const SparseMat<typename F::Elt> &X, size_t cb, const std::vector<int64_t> &A, size_t sa,
-                                   const std::vector<int64_t> &B, size_t sb, OrbitCount &c, size_t &canon, SparseMat<typename F::Elt> *Out) {
+// (columns a * cb + b; output pr x qc); A is sa x sa over the denominator da, B is sb x sb over db (row-major); Out gets the
+// rows when asked
+template <class F> void orbit_part(const F &f, const SparseMat<typename F::Elt> &X, size_t cb, const std::vector<int64_t> &A, int64_t da, size_t sa,
+                                   const std::vector<int64_t> &B, int64_t db, size_t sb, OrbitCount &c, size_t &canon, SparseMat<typename F::Elt> *Out) {
     using E = typename F::Elt;
     std::vector<E> acc(sa * sb);
     std::vector<E> Af(A.size()), Bf(B.size());
-    for (size_t t = 0; t < A.size(); ++t) Af[t] = f.fromInt(A[t]);
-    for (size_t t = 0; t < B.size(); ++t) Bf[t] = f.fromInt(B[t]);
+    for (size_t t = 0; t < A.size(); ++t) Af[t] = da == 1 ? f.fromInt(A[t]) : f.div(f.fromInt(A[t]), f.fromInt(da));
+    for (size_t t = 0; t < B.size(); ++t) Bf[t] = db == 1 ? f.fromInt(B[t]) : f.div(f.fromInt(B[t]), f.fromInt(db));
     if (Out) *Out = SparseMat<E>(X.rowdim(), sa * sb);
     for (size_t i = 0; i < X.rowdim(); ++i) {
         std::fill(acc.begin(), acc.end(), f.zero());
@@ -101,14 +174,14 @@ template <class F> void orbit_part(const F &f, const SparseMat<typename F::Elt> 
 
 // counts of candidate `seed` (cost = nnz, or L.m + R.m + P.n - the rows with one non-zero for ORBIT_CANONICAL); the three
 // transformed matrices (P transposed back) when out is given
-template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &T, uint64_t seed, int measure, OrbitTriple<F> *out = nullptr) {
-    const OrbitUVW c = orbit_uvw(T.m, T.k, T.n, seed);
+template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &T, uint64_t seed, int measure, int action, OrbitTriple<F> *out = nullptr) {
+    const OrbitUVW c = orbit_uvw(f, T.m, T.k, T.n, seed, action);
     const size_t m = T.m, k = T.k, n = T.n;
     auto tr = [](const std::vector<int64_t> &M, size_t s) { std::vector<int64_t> R(s * s); for (size_t i = 0; i < s; ++i) for (size_t j = 0; j < s; ++j) R[j * s + i] = M[i * s + j]; return R; };
     OrbitCount r; size_t canon = 0;
-    orbit_part(f, T.L, k, c.U.Mi, m, c.V.M, k, r, canon, out ? &out->L : nullptr);                  // U^-T X V: A[a][p] = U^-1[a][p]
-    orbit_part(f, T.R, n, tr(c.V.Mi, k), k, c.W.M, n, r, canon, out ? &out->R : nullptr);           // V^-1 Y W: A[b][p] = V^-1[p][b]
-    orbit_part(f, T.PT, n, tr(c.U.M, m), m, tr(c.W.Mi, n), n, r, canon, out ? &out->PT : nullptr);  // U Z W^-T: A[a][p] = U[p][a], B[c][q] = W^-1[q][c]
+    orbit_part(f, T.L, k, c.U.Mi, c.U.den, m, c.V.M, c.V.den, k, r, canon, out ? &out->L : nullptr);                  // U^-T X V: A[a][p] = U^-1[a][p]
+    orbit_part(f, T.R, n, tr(c.V.Mi, k), c.V.den, k, c.W.M, c.W.den, n, r, canon, out ? &out->R : nullptr);           // V^-1 Y W: A[b][p] = V^-1[p][b]
+    orbit_part(f, T.PT, n, tr(c.U.M, m), c.U.den, m, tr(c.W.Mi, n), c.W.den, n, r, canon, out ? &out->PT : nullptr);  // U Z W^-T: A[a][p] = U[p][a], B[c][q] = W^-1[q][c]
     r.cost = measure == ORBIT_CANONICAL ? T.L.rowdim() + T.R.rowdim() + T.PT.rowdim() - canon : r.nnz;
     if (out) { out->m = m; out->k = k; out->n = n; }
     return r;

@@ -2133,6 +2133,7 @@ struct plo_orbit_plan {
     void *d_img = nullptr; uint64_t *d_best = nullptr;
     uint32_t waves_per_wg = 4, lds_bytes = 0, blocks_per_cu = 1, grid_max = 1;
     uint64_t algo_bytes = 0;
+    int action = PLO_ORBIT_ACT_TRIANGULAR;
 };
 
 namespace {
@@ -2161,13 +2162,29 @@ const char *qcsr_defect(const plo_qcsr_t *A) {
 }
 int64_t gcd64(int64_t a, int64_t b) { if (a < 0) a = -a; if (b < 0) b = -b; while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
 
+using orbit_fn_t = void (*)(plo::OrbitPlan, plo::OrbitJob);
+orbit_fn_t orbit_fn(bool mod, int action) {
+    switch (action) {
+    case PLO_ORBIT_ACT_PLUQ: return mod ? plo::orbit_kernel<true, 1> : plo::orbit_kernel<false, 1>;
+    case PLO_ORBIT_ACT_HOUSEHOLDER: return mod ? plo::orbit_kernel<true, 2> : plo::orbit_kernel<false, 2>;
+    default: return mod ? plo::orbit_kernel<true> : plo::orbit_kernel<false>;
+    }
+}
+
 int orbit_launch(plo_orbit_plan *pl, plo::OrbitJob J, plo_stats_t *st) {
     const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
     const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(pl->grid_max, need));
     return timed_launch(pl, grid, J.ncand, st, [&] {
-        if (pl->P.p) hipLaunchKernelGGL((plo::orbit_kernel<true>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
-        else hipLaunchKernelGGL((plo::orbit_kernel<false>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+        hipLaunchKernelGGL(orbit_fn(pl->P.p != 0, pl->action), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
     });
+}
+
+// |entries| of the two factors of a part, a direct one of size sd and an inverse of size si, multiplied:
+// triangular 1 x 2^(si-2); PLUQ sd x si 4^(si-2); Householder (numerators over d <= s) sd x si
+__int128 orbit_factor_bound(int action, uint32_t sd, uint32_t si) {
+    if (action == PLO_ORBIT_ACT_PLUQ) return (__int128)sd * (si >= 2 ? (__int128)si << (2 * (si - 2)) : 1);
+    if (action == PLO_ORBIT_ACT_HOUSEHOLDER) return (__int128)sd * si;
+    return (__int128)1 << (si >= 2 ? si - 2 : 0);
 }
 } // namespace
 
@@ -2175,9 +2192,15 @@ extern "C" {
 
 int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, plo_orbit_plan_t **plan)
 {
+    return plo_orbit_plan_create_act(L, R, P, modulus, measure, PLO_ORBIT_ACT_TRIANGULAR, plan);
+}
+
+int plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, plo_orbit_plan_t **plan)
+{
     if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
     if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
     if (measure != PLO_ORBIT_DENSITY && measure != PLO_ORBIT_CANONICAL) return fail(PLO_E_ARG, "measure must be PLO_ORBIT_DENSITY or PLO_ORBIT_CANONICAL");
+    if (action != PLO_ORBIT_ACT_TRIANGULAR && action != PLO_ORBIT_ACT_PLUQ && action != PLO_ORBIT_ACT_HOUSEHOLDER) return fail(PLO_E_ARG, "action must be one of PLO_ORBIT_ACT_*");
     if (modulus == 1) return fail(PLO_E_ARG, "modulus 1");
     uint32_t m = 0, k = 0, n = 0;
     if (!orbit_shape(L, R, P, m, k, n)) return fail(PLO_E_ARG, "shapes are not r x mk, r x kn, mn x r");
@@ -2199,6 +2222,7 @@ int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
     std::vector<uint16_t> pos;
     std::vector<uint32_t> rp{0};
     const uint32_t inv_size[3] = {m, k, n};            // the factor of each part with an inverse: U^-1, V^-1, W^-T
+    const uint32_t dir_size[3] = {k, n, m};            // and the direct one: V, W, U
     for (uint32_t g = 0; g < 3u * r; ++g) {
         if (modulus) {
             for (auto &e : rows[g]) {
@@ -2209,7 +2233,7 @@ int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
                 if (v) { pos.push_back(e.first); val.push_back((int64_t)v); }
             }
         } else {
-            // scale the row to integers by the lcm of its denominators; |sums| <= L1 * 2^(s-2) < 2^62
+            // scale the row to integers by the lcm of its denominators; |sums| <= L1 * (the factors' entry bounds) < 2^62
             __int128 l = 1;
             for (auto &e : rows[g]) { const int64_t d = e.second.second; l = l / gcd64((int64_t)(l % d), d) * d; if (l > ((__int128)1 << 62)) return fail(PLO_E_UNSUPPORTED, "row scale above 2^62 (int64 bound): host path only"); }
             __int128 l1 = 0;
@@ -2220,7 +2244,14 @@ int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
                 pos.push_back(e.first); val.push_back((int64_t)v);
             }
             const uint32_t s = inv_size[g / r];
-            if ((l1 << (s >= 2 ? s - 2 : 0)) >= ((__int128)1 << 62)) return fail(PLO_E_UNSUPPORTED, "row L1 norm times 2^(s-2) reaches 2^62 (int64 bound): host path only");
+            if (action == PLO_ORBIT_ACT_TRIANGULAR) {
+                if ((l1 << (s >= 2 ? s - 2 : 0)) >= ((__int128)1 << 62)) return fail(PLO_E_UNSUPPORTED, "row L1 norm times 2^(s-2) reaches 2^62 (int64 bound): host path only");
+            } else {
+                // (l1 and l are at most 2^62 and the bound below 2^37: no overflow of the 128-bit products)
+                const __int128 fb = orbit_factor_bound(action, dir_size[g / r], s);
+                if (l1 * fb >= ((__int128)1 << 62)) return fail(PLO_E_UNSUPPORTED, "row L1 norm times the entry bounds of the action's factors reaches 2^62 (int64 bound): host path only");
+                if (action == PLO_ORBIT_ACT_HOUSEHOLDER && l * fb >= ((__int128)1 << 62)) return fail(PLO_E_UNSUPPORTED, "row scale times the Householder denominators reaches 2^62 (int64 bound): host path only");
+            }
             scale[g] = (int64_t)l;
         }
         rp.push_back((uint32_t)val.size());
@@ -2234,17 +2265,23 @@ int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
     // shared LDS: values, scales, row pointers, positions
     Q.off_scale = round_up(8u * nnz, 16); Q.off_rp = Q.off_scale + round_up(8u * nrows, 16); Q.off_pos = Q.off_rp + round_up(4u * (nrows + 1u), 16);
     Q.shared_bytes = Q.off_pos + round_up(2u * nnz, 16);
+    const bool table = action == PLO_ORBIT_ACT_HOUSEHOLDER && modulus;             // 1/d modulo the modulus, d = 0..16
+    if (table) { Q.off_dinv = Q.shared_bytes; Q.shared_bytes += round_up(4u * 17u, 16); }
     // a wave: A_L (m x m), B_L (k x k), A_R (k x k), B_R (n x n), A_P (m x m), B_P (n x n), T^-1, T, P and Q, row counters
     const uint32_t sz[6] = {m, k, k, n, m, n};
     uint32_t off = 0;
     for (int f = 0; f < 6; ++f) { Q.off_fac[f] = off; off += round_up(8u * sz[f] * sz[f], 16); }
-    Q.off_ti = off; off += round_up(8u * smax * smax, 16);
-    Q.off_t = off; off += round_up(smax * smax, 16);
+    Q.off_ti = off; if (action != PLO_ORBIT_ACT_HOUSEHOLDER) off += round_up(8u * smax * smax, 16);       // Householder inverts nothing
+    Q.off_t = off; off += action == PLO_ORBIT_ACT_HOUSEHOLDER ? 32u : round_up(smax * smax, 16);      // Householder: u and the signs, 16 bytes each
+    if (action == PLO_ORBIT_ACT_PLUQ) {                                             // the second triangle and its inverse
+        Q.off_ti2 = off; off += round_up(8u * smax * smax, 16);
+        Q.off_t2 = off; off += round_up(smax * smax, 16);
+    }
     Q.off_perm = off; off += 32;
     Q.off_cnt = off; off += round_up(2u * nrows + 2u, 16);
     Q.lds_per_wave = off;
     pl->algo_bytes = 10ull * nnz + 12ull * nrows;
-    pl->lds_bytes = 0;
+    pl->lds_bytes = 0; pl->action = action;
     for (uint32_t w : {4u, 2u, 1u}) { const uint32_t b = Q.shared_bytes + w * Q.lds_per_wave; if (b <= g_lds_max && b <= 64u * 1024u) { pl->waves_per_wg = w; pl->lds_bytes = b; break; } }
     if (!pl->lds_bytes) { delete pl; return fail(PLO_E_CAPACITY, "input does not fit LDS"); }
     pl->blocks_per_cu = blocks_per_cu(pl->waves_per_wg, pl->lds_bytes);
@@ -2252,9 +2289,12 @@ int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
     // the device image: values, scales, row pointers, positions
     const size_t bytes = (size_t)Q.shared_bytes;
     std::vector<uint8_t> img(bytes, 0);
+    if (table)
+        for (uint32_t d = 1; d <= 16; ++d)
+            if (gcd64((int64_t)d, (int64_t)modulus) == 1) { const uint32_t v = inv_mod((uint32_t)(d % modulus), (uint32_t)modulus); memcpy(img.data() + Q.off_dinv + 4u * d, &v, 4); }
     memcpy(img.data(), val.data(), 8u * nnz); memcpy(img.data() + Q.off_scale, scale.data(), 8u * nrows);
     memcpy(img.data() + Q.off_rp, rp.data(), 4u * (nrows + 1u)); memcpy(img.data() + Q.off_pos, pos.data(), 2u * nnz);
-    const void *fn = modulus ? (const void *)plo::orbit_kernel<true> : (const void *)plo::orbit_kernel<false>;
+    const void *fn = (const void *)orbit_fn(modulus != 0, action);
     if (hipMalloc(&pl->d_img, bytes) != hipSuccess || hipMemcpy(pl->d_img, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
         hipMalloc((void **)&pl->d_best, 16ull * pl->grid_max * pl->waves_per_wg) != hipSuccess ||
         hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes) != hipSuccess) {
@@ -2262,6 +2302,7 @@ int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
     }
     uint8_t *d = (uint8_t *)pl->d_img;
     Q.val = (const int64_t *)d; Q.scale = (const int64_t *)(d + Q.off_scale); Q.rp = (const uint32_t *)(d + Q.off_rp); Q.pos = (const uint16_t *)(d + Q.off_pos);
+    if (table) Q.dinv = (const uint32_t *)(d + Q.off_dinv);
     *plan = pl;
     return PLO_OK;
 }
@@ -2308,9 +2349,15 @@ int plo_orbit_search(plo_orbit_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_
 int plo_orbit_search_multi(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure,
                            uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats)
 {
+    return plo_orbit_search_multi_act(L, R, P, modulus, measure, PLO_ORBIT_ACT_TRIANGULAR, seed0, nseeds, ndev, devices, best, stats);
+}
+
+int plo_orbit_search_multi_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action,
+                               uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats)
+{
     if (!L || !R || !P || !best) return fail(PLO_E_ARG, "null argument");
     return sharded_search(seed0, nseeds, ndev, devices, best, stats,
-        [&](plo_orbit_plan_t **plan) { return plo_orbit_plan_create_q(L, R, P, modulus, measure, plan); }, plo_orbit_search, plo_orbit_plan_destroy,
+        [&](plo_orbit_plan_t **plan) { return plo_orbit_plan_create_act(L, R, P, modulus, measure, action, plan); }, plo_orbit_search, plo_orbit_plan_destroy,
         [&](const plo_orbit_best_t &pb) { return std::make_pair(((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, pb.seed - seed0); });   // (cost, nnz, nno), then seed
 }
 

@@ -380,22 +380,24 @@ def lin_search_multi(m, n, rowptr, col, num, den, seed0, nseeds, devices):
 
 ORBIT_BASE_SEED = (1 << 64) - 1
 ORBIT_DENSITY, ORBIT_CANONICAL = 0, 2
+ORBIT_ACT_TRIANGULAR, ORBIT_ACT_PLUQ, ORBIT_ACT_HOUSEHOLDER = 0, 1, 2
 
 
 class OrbitPlan:
     """Mirror of the restart loop of the reference's orbiter (src/orbiter.cpp:272-324, bin/orbiter): the triple L (r x mk),
     R (r x kn), P (mn x r), each as a rational CSR (m, n, rowptr, col, num[, den]), over Q (modulus 0) or Z_modulus
     (< 2^31), scored by `measure` (ORBIT_DENSITY or ORBIT_CANONICAL).  `cost_many` returns (cost, nnz, nno) per seed;
-    `search` the best ((cost, nnz, nno), seed), ties to the smaller seed.  ORBIT_BASE_SEED is the input itself."""
+    `search` the best ((cost, nnz, nno), seed), ties to the smaller seed.  ORBIT_BASE_SEED is the input itself.  `action`
+    (ORBIT_ACT_TRIANGULAR, ORBIT_ACT_PLUQ or ORBIT_ACT_HOUSEHOLDER) is how U, V and W are drawn."""
 
-    def __init__(self, L, R, P, modulus=0, measure=ORBIT_DENSITY, device=None):
+    def __init__(self, L, R, P, modulus=0, measure=ORBIT_DENSITY, device=None, action=ORBIT_ACT_TRIANGULAR):
         lib = capi.lib()
         if device is not None:
             capi.check(lib.plo_init(device))
         self._h = None
         self._csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
         h = ctypes.c_void_p()
-        capi.check(lib.plo_orbit_plan_create_q(*[ctypes.byref(c) for c, _ in self._csr], modulus, measure, ctypes.byref(h)))
+        capi.check(lib.plo_orbit_plan_create_act(*[ctypes.byref(c) for c, _ in self._csr], modulus, measure, action, ctypes.byref(h)))
         self._h = h
         self.last_stats = None
 
@@ -425,14 +427,14 @@ class OrbitPlan:
         return (b.cost, b.nnz, b.nno), b.seed
 
 
-def orbit_search_multi(L, R, P, modulus, measure, seed0, nseeds, devices):
-    """`plo_orbit_search_multi`: the orbit search over the listed devices from this process (L, R, P as for OrbitPlan).
+def orbit_search_multi(L, R, P, modulus, measure, seed0, nseeds, devices, action=ORBIT_ACT_TRIANGULAR):
+    """`plo_orbit_search_multi_act`: the orbit search over the listed devices from this process (L, R, P as for OrbitPlan).
     Returns (((cost, nnz, nno), seed), stats)."""
     lib = capi.lib()
     csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
     dv = (ctypes.c_int * len(devices))(*devices)
     b, st = capi.OrbitBest(), capi.Stats()
-    capi.check(lib.plo_orbit_search_multi(*[ctypes.byref(c) for c, _ in csr], modulus, measure, seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
+    capi.check(lib.plo_orbit_search_multi_act(*[ctypes.byref(c) for c, _ in csr], modulus, measure, action, seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
     del csr
     return ((b.cost, b.nnz, b.nno), b.seed), st.as_dict()
 
