@@ -96,7 +96,9 @@ int plo_cse_plan_is_hbm(const plo_plan_t *plan);
  * table), [5] sweeps whose claimed-slot list overflowed, [6] candidates, [7] how often the plan was rebuilt with the eager
  * pair table because a candidate outgrew the structures of the deferred updates (sized from the input's triples). */
 int plo_cse_plan_hbm_counters(const plo_plan_t *plan, uint32_t out[8]);
-/* the same, the first n <= 10 counters: [8] windows of the flat sweep beyond the first one of a batch of rows (a wave takes the entries
+/* the same, the first n <= 13 counters: [10] merges of the deferred updates forced by log or hot-table pressure, [11] groups of partitions
+ * summed by the merges, [12] records of those groups loaded behind the four prefetched records of a thread, all three summed over the
+ * candidates of the launch; [8] windows of the flat sweep beyond the first one of a batch of rows (a wave takes the entries
  * of its rows 2048 at a time; PLO_BIG_FWIN makes the window smaller in the tests), counted on wave 0; [9] rows walked by the row search
  * (the length of the shorter row list of a step's two columns, summed over steps: reference include/plinopt_optimize.inl:92-94 walks
  * every row). */

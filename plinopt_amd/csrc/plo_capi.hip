@@ -769,13 +769,14 @@ int plo_cse_plan_hbm_counters(const plo_plan_t *pl, uint32_t out[8])
 
 int plo_cse_plan_hbm_counters_ex(const plo_plan_t *pl, uint32_t *out, uint32_t n)
 {
-    if (!pl || !out || n > 10u) return fail(PLO_E_ARG, "bad argument");
-    uint32_t o[10] = {0};
+    if (!pl || !out || n > 13u) return fail(PLO_E_ARG, "bad argument");
+    uint32_t o[13] = {0};
     const int rc = plo_cse_plan_hbm_counters(pl, o);
     if (rc != PLO_OK) return rc;
     uint32_t hs[64];
     HIPCHK(hipMemcpy(hs, pl->d_stats, sizeof hs, hipMemcpyDeviceToHost));
     o[8] = hs[53]; o[9] = hs[54];
+    o[10] = hs[39]; o[11] = hs[13]; o[12] = hs[14];         // the merge: forced by log / hot pressure, groups summed, records loaded behind the prefetch
     for (uint32_t k = 0; k < n; ++k) out[k] = o[k];
     return PLO_OK;
 }

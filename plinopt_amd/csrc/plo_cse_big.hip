@@ -458,7 +458,7 @@ struct BigShared {
     uint32_t a, b, r, aggn, nspill, keepn; uint64_t kprime; uint64_t selkey;
     uint32_t nbisect, spilltot, listover, nwin, nsearched;   // nwin: windows of the flat sweep beyond the first of a batch of rows (thread 0's wave); nsearched: rows walked by the row search   // diagnostics: tie picks by bisection, entries through the spill list, sweeps whose slot list overflowed
     uint32_t logn, hotn, hotbits, nforced, hotops, logtot_lo, logtot_hi;   // DEFER: log fill, claimed hot slots, hot table size; diagnostics: merges forced by log/hot pressure, updates served by the hot table, log entries written
-    uint32_t derr; unsigned long long tmg[4], tmb[4]; uint32_t ngrp; uint32_t outcnt[64];           // DEFER merge: live entries written back per partition of the current group
+    uint32_t derr; unsigned long long tmg[4], tmb[4]; uint32_t ngrp, nloop; uint32_t outcnt[64];           // DEFER merge: live entries written back per partition of the current group
     uint32_t cblk[512];            // level-M triple counts per block of 64 first columns (NCmax <= 32768)
     unsigned long long tph[8];     // phase clocks (100 MHz ticks): level, select, rows, sweep1, flush1, sweep2, flush2, tail
     unsigned long long tpg[7], tld; // ProgramGen: table fill + flags, expand + A1, A2, A3 + B + count, Triangle set-up, Triangle, D; tld: the image load
@@ -494,6 +494,9 @@ struct BigShared {
 //           are small) is summed in an LDS hash table (counts biased by 2^15: records arrive in any order), live
 //           triples (frequency >= 2) are written back compactly and counted per level; the new window [theta', M] is
 //           chosen on the exact histogram and its triples move to the hot table.  All of it is streaming traffic.
+//           A group costs two barriers: its records -- four per thread, counted across the group's partitions -- are
+//           requested while the table of the group before is scanned; the table is cleared once per merge and the
+//           scan empties every slot it reads.
 // Frequencies never rise after the step that creates a triple, so a cold triple stays cold until the next merge and the
 // hot table always holds every triple of frequency >= theta: levels >= theta of hist[] stay exact, lower levels are
 // not maintained between merges (never read: a scan that would go below theta triggers the merge).
@@ -668,62 +671,67 @@ __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigSh
         {
             for (uint32_t f = tid; f <= P.maxf0; f += nth) hist[f] = 0u;
             uint64_t *ltab = (uint64_t *)mreg;
+            for (uint32_t s = tid; s < (1u << PLO_DLB); s += nth) ltab[s] = PLO_LEMPTY;      // once: the scan of a group leaves its slots empty again
+            if (tid < 64u) sh.outcnt[tid] = 0u;
             BSYNC();
             // Counts of 128 partitions ahead live in two registers (lane i: partition W + i, W + 64 + i); the bounds of a group come from
-            // them without a memory round trip.  The first four records of a thread for the NEXT group are requested while the table of
-            // the current group is scanned and written back.
+            // them without a memory round trip: lane j of `inc` = records of the group's partitions 0..j.  The first four records of a
+            // thread for the NEXT group, counted across its partitions, are requested while the table of the current group is scanned
+            // and written back.
             uint32_t W = 0, cW = lane < Pn ? ptail[lane] : 0u, cW2 = 64u + lane < Pn ? ptail[64u + lane] : 0u;
-            auto bounds = [&](uint32_t p_, uint32_t &cT, uint32_t &g, uint32_t &tot) {
+            auto bounds = [&](uint32_t p_, uint32_t &inc_, uint32_t &g, uint32_t &tot) {
                 const uint32_t o = p_ - W + lane;                                  // 0 .. 127
                 const uint32_t x0 = (uint32_t)__shfl((int)cW, (int)(o & 63u)), x1 = (uint32_t)__shfl((int)cW2, (int)(o & 63u));
-                cT = o < 64u ? x0 : x1;
-                const uint32_t inc = wave_incl_scan(cT);
-                const unsigned long long okm = __builtin_amdgcn_ballot_w64(inc <= P.lgrp);
+                inc_ = wave_incl_scan(o < 64u ? x0 : x1);
+                const unsigned long long okm = __builtin_amdgcn_ballot_w64(inc_ <= P.lgrp);
                 g = okm == ~0ull ? 64u : (uint32_t)__builtin_ctzll(~okm);
                 if (g == 0u) g = 1u;
                 if (g > Pn - p_) g = Pn - p_;
-                tot = (uint32_t)__builtin_amdgcn_readlane((int)inc, (int)(g - 1u));
+                tot = (uint32_t)__builtin_amdgcn_readlane((int)inc_, (int)(g - 1u));
             };
-            uint32_t p = 0, cT = 0, g = 0, tot = 0;
-            bounds(0u, cT, g, tot);
-            // records tid, tid + nth, tid + 2 nth, tid + 3 nth of the group's FIRST partition (the others, and anything beyond, are loaded in the loop)
+            uint32_t p = 0, inc = 0, g = 0, tot = 0;
+            bounds(0u, inc, g, tot);
+            // records x, x + nth, x + 2 nth, x + 3 nth of the group (p_, g_, inc_), x = b + tid: a record that lies behind the first j
+            // partitions of the group is found rcap - (records of the partition) further on for each of them
             uint64_t f0 = 0, f1 = 0, f2 = 0, f3 = 0;
-            auto first4 = [&](uint32_t p_, uint32_t n0) {
+            auto flat4 = [&](uint32_t p_, uint32_t g_, uint32_t inc_, uint32_t tot_, uint32_t b) {
+                const uint32_t x0 = b + tid, x1 = x0 + nth, x2 = x1 + nth, x3 = x2 + nth;
+                uint32_t a0 = x0, a1 = x1, a2 = x2, a3 = x3, prev = 0u;
+                for (uint32_t j = 0; j + 1u < g_; ++j) {
+                    const uint32_t s = (uint32_t)__builtin_amdgcn_readlane((int)inc_, (int)j), d = rcap - (s - prev);
+                    prev = s;
+                    a0 += x0 >= s ? d : 0u; a1 += x1 >= s ? d : 0u; a2 += x2 >= s ? d : 0u; a3 += x3 >= s ? d : 0u;
+                }
                 const uint64_t *sp = store + (uint64_t)p_ * rcap;
-                f0 = tid < n0 ? sp[tid] : 0ull; f1 = tid + nth < n0 ? sp[tid + nth] : 0ull; f2 = tid + 2u * nth < n0 ? sp[tid + 2u * nth] : 0ull; f3 = tid + 3u * nth < n0 ? sp[tid + 3u * nth] : 0ull;
+                f0 = x0 < tot_ ? sp[a0] : 0ull; f1 = x1 < tot_ ? sp[a1] : 0ull; f2 = x2 < tot_ ? sp[a2] : 0ull; f3 = x3 < tot_ ? sp[a3] : 0ull;
             };
-            first4(0u, (uint32_t)__builtin_amdgcn_readlane((int)cT, 0));
+            flat4(0u, g, inc, tot, 0u);
 #define PLO_PUT(v_) do { const int32_t d_ = (int32_t)((v_) & 0x7FFFull); if (d_) if (!lt_put(ltab, (v_) >> 16, ((v_) & 0x8000ull) ? d_ : -d_, pbits, lb)) { wg_max(&sh.errflag, (uint32_t)BERR_TABLE); wg_max(&sh.derr, 103u); } } while (0)
             unsigned long long tbl = wall_clock64();
             while (p < Pn) {
                 if (tot > (7u << (PLO_DLB - 3u))) { if (tid == 0) { wg_max(&sh.errflag, (uint32_t)BERR_TABLE); wg_max(&sh.derr, 102u); } break; }       // more than 7/8 of the table
                 uint32_t lb = 6u; while ((1u << lb) < 2u * tot + 64u && lb < PLO_DLB) ++lb;
-                for (uint32_t s = tid; s < (1u << lb); s += nth) ltab[s] = PLO_LEMPTY;
-                if (tid < 64u) sh.outcnt[tid] = 0u;
-                BSYNC();
                 unsigned long long tb0 = wall_clock64();
 #define PLO_BSTAMP(q_) do { if (tid == 0) { const unsigned long long t_ = wall_clock64(); sh.tmb[q_] += t_ - tb0; tb0 = t_; } } while (0)
-                if (tid == 0) { sh.tmb[3] += tb0 - tbl; ++sh.ngrp; }
+                if (tid == 0) { sh.tmb[3] += tb0 - tbl; ++sh.ngrp; if (tot > 4u * nth) sh.nloop += tot - 4u * nth; }
                 PLO_PUT(f0); PLO_PUT(f1); PLO_PUT(f2); PLO_PUT(f3);
-                for (uint32_t j = 0; j < g; ++j) {
-                    const uint32_t nT = (uint32_t)__builtin_amdgcn_readlane((int)cT, (int)j);
-                    const uint64_t *sp = store + (uint64_t)(p + j) * rcap;
-                    for (uint32_t e = tid + (j == 0u ? 4u * nth : 0u); e < nT; e += 4u * nth) {
-                        const uint64_t v0 = sp[e], v1 = e + nth < nT ? sp[e + nth] : 0ull, v2 = e + 2u * nth < nT ? sp[e + 2u * nth] : 0ull, v3 = e + 3u * nth < nT ? sp[e + 3u * nth] : 0ull;
-                        PLO_PUT(v0); PLO_PUT(v1); PLO_PUT(v2); PLO_PUT(v3);
-                    }
+                for (uint32_t b = 4u * nth; b < tot; b += 4u * nth) {             // beyond the prefetch: lgrp above 4 nth, or one oversized partition
+                    flat4(p, g, inc, tot, b);
+                    PLO_PUT(f0); PLO_PUT(f1); PLO_PUT(f2); PLO_PUT(f3);
                 }
                 // the next group: slide the window of counts, bounds, first records
                 const uint32_t pn = p + g;
                 if (pn >= W + 64u) { W += 64u; cW = cW2; const uint32_t q = W + 64u + lane; cW2 = q < Pn ? ptail[q] : 0u; }
-                uint32_t cTn = 0, gn = 1, totn = 0;
-                if (pn < Pn) bounds(pn, cTn, gn, totn);
+                uint32_t incn = 0, gn = 1, totn = 0;
+                if (pn < Pn) bounds(pn, incn, gn, totn);
                 BSYNC();
                 PLO_BSTAMP(0);
-                if (pn < Pn) first4(pn, (uint32_t)__builtin_amdgcn_readlane((int)cTn, 0)); else { f0 = f1 = f2 = f3 = 0ull; }
+                if (pn < Pn) flat4(pn, gn, incn, totn, 0u); else { f0 = f1 = f2 = f3 = 0ull; }
+                // scan: a slot that held a key is emptied for the next group as it is read
                 for (uint32_t s = tid; s < (1u << lb); s += nth) {
                     const uint64_t v = ltab[s];
                     if (v == PLO_LEMPTY) continue;
+                    ltab[s] = PLO_LEMPTY;
                     const uint32_t cb = (uint32_t)(v & 0xFFFFull);
                     if (cb < PLO_DBIAS + 2u) continue;                       // frequency below 2: never chosen, never rises -- dropped
                     const uint32_t c = cb - PLO_DBIAS; const uint64_t k = v >> 16;
@@ -735,9 +743,9 @@ __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigSh
                 }
                 BSYNC();
                 PLO_BSTAMP(1);
-                if (tid < g) { const uint32_t c_ = sh.outcnt[tid] < capp ? sh.outcnt[tid] : capp; pcount[p + tid] = c_; ptail[p + tid] = c_; }
+                if (tid < g) { const uint32_t c_ = sh.outcnt[tid] < capp ? sh.outcnt[tid] : capp; pcount[p + tid] = c_; ptail[p + tid] = c_; sh.outcnt[tid] = 0u; }     // (the next scan starts behind a barrier)
                 tbl = wall_clock64();
-                p = pn; cT = cTn; g = gn; tot = totn;
+                p = pn; inc = incn; g = gn; tot = totn;
             }
 #undef PLO_PUT
         }
@@ -878,7 +886,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
         for (int q = 0; q < 4; ++q) { sh.tb1[q] = sh.tb2[q] = 0; sh.nb[q] = 0; } sh.fb1 = sh.fb2 = sh.fl1 = sh.fl2 = 0; for (int q = 0; q < 16; ++q) sh.pw[q] = 0; for (int c_ = 0; c_ < 4; ++c_) for (int q = 0; q < 8; ++q) sh.tpc[c_][q] = 0;
 #endif
         sh.errflag = 0; sh.fullscans = 0; sh.rebuilds = 0; sh.steps = 0; sh.hlbad = 0; ncrptr[0] = 0; sh.nbisect = 0; sh.spilltot = 0; sh.listover = 0; sh.nwin = 0; sh.nsearched = 0;
-        sh.logn = 0; sh.hotn = 0; sh.hotbits = P.hotbits_min; sh.derr = 0; for (int q = 0; q < 4; ++q) { sh.tmg[q] = 0; sh.tmb[q] = 0; } sh.ngrp = 0; sh.nforced = 0; sh.hotops = 0; sh.logtot_lo = 0; sh.logtot_hi = 0;
+        sh.logn = 0; sh.hotn = 0; sh.hotbits = P.hotbits_min; sh.derr = 0; for (int q = 0; q < 4; ++q) { sh.tmg[q] = 0; sh.tmb[q] = 0; } sh.ngrp = 0; sh.nloop = 0; sh.nforced = 0; sh.hotops = 0; sh.logtot_lo = 0; sh.logtot_hi = 0;
     }
     PLO_BIG_FENCE(); BSYNC();
     if (tid == 0) sh.tld = wall_clock64() - tld0;
@@ -2130,7 +2138,7 @@ template <int MODE, bool DEFER, bool IDK = false> __global__ __launch_bounds__(P
             const uint32_t a = (uint32_t)(res >> 32), mu_ = (uint32_t)res;
             if (J.adds) J.adds[c] = a;
             if (J.muls) J.muls[c] = mu_;
-            if (J.stats) { atomicAdd(&J.stats[32], sh.steps); atomicAdd(&J.stats[33], sh.fullscans); atomicAdd(&J.stats[34], sh.rebuilds); atomicAdd(&J.stats[35], sh.nbisect); atomicAdd(&J.stats[36], sh.spilltot); atomicAdd(&J.stats[37], sh.listover); atomicAdd(&J.stats[38], 1u); atomicAdd(&J.stats[39], sh.nforced); atomicMax(&J.stats[43], sh.derr); for (int q = 0; q < 4; ++q) { J.stats[44 + q] = (uint32_t)(sh.tmg[q] / 100ull); J.stats[48 + q] = (uint32_t)(sh.tmb[q] / 100ull); } J.stats[52] = sh.ngrp; J.stats[55] = (uint32_t)((tk1 - tk0) / 100ull); J.stats[56] = (uint32_t)((tk2 - tk1) / 100ull); J.stats[12] = (uint32_t)(sh.tld / 100ull); for (int q = 0; q < 7; ++q) J.stats[57 + q] = ok ? (uint32_t)(sh.tpg[q] / 100ull) : 0u; atomicAdd(&J.stats[53], sh.nwin); atomicAdd(&J.stats[54], sh.nsearched); atomicAdd(&J.stats[40], sh.hotops); { const uint32_t lo_ = atomicAdd(&J.stats[41], sh.logtot_lo); if (lo_ + sh.logtot_lo < lo_) atomicAdd(&J.stats[42], 1u); atomicAdd(&J.stats[42], sh.logtot_hi); }
+            if (J.stats) { atomicAdd(&J.stats[32], sh.steps); atomicAdd(&J.stats[33], sh.fullscans); atomicAdd(&J.stats[34], sh.rebuilds); atomicAdd(&J.stats[35], sh.nbisect); atomicAdd(&J.stats[36], sh.spilltot); atomicAdd(&J.stats[37], sh.listover); atomicAdd(&J.stats[38], 1u); atomicAdd(&J.stats[39], sh.nforced); atomicMax(&J.stats[43], sh.derr); for (int q = 0; q < 4; ++q) { J.stats[44 + q] = (uint32_t)(sh.tmg[q] / 100ull); J.stats[48 + q] = (uint32_t)(sh.tmb[q] / 100ull); } J.stats[52] = sh.ngrp; atomicAdd(&J.stats[13], sh.ngrp); atomicAdd(&J.stats[14], sh.nloop); J.stats[55] = (uint32_t)((tk1 - tk0) / 100ull); J.stats[56] = (uint32_t)((tk2 - tk1) / 100ull); J.stats[12] = (uint32_t)(sh.tld / 100ull); for (int q = 0; q < 7; ++q) J.stats[57 + q] = ok ? (uint32_t)(sh.tpg[q] / 100ull) : 0u; atomicAdd(&J.stats[53], sh.nwin); atomicAdd(&J.stats[54], sh.nsearched); atomicAdd(&J.stats[40], sh.hotops); { const uint32_t lo_ = atomicAdd(&J.stats[41], sh.logtot_lo); if (lo_ + sh.logtot_lo < lo_) atomicAdd(&J.stats[42], 1u); atomicAdd(&J.stats[42], sh.logtot_hi); }
                 J.stats[0] = sh.steps; J.stats[1] = sh.fullscans; J.stats[2] = sh.rebuilds; for (int q = 0; q < 8; ++q) J.stats[4 + q] = (uint32_t)(sh.tph[q] / 100ull);
 #ifdef PLO_BIG_PROFILE
                 for (int q = 0; q < 4; ++q) { J.stats[16 + q] = (uint32_t)(sh.tb1[q] / 100ull); J.stats[20 + q] = (uint32_t)(sh.tb2[q] / 100ull); J.stats[24 + q] = sh.nb[q]; }
