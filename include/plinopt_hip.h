@@ -94,7 +94,10 @@ int plo_cse_plan_is_hbm(const plo_plan_t *plan);
  * [2] frequency-level rebuilds, [3] tie picks (:260-265) resolved by bisection on the key (more ties in one
  * column than the LDS list holds), [4] pairs that went through the spill list (no room in the LDS aggregation
  * table), [5] sweeps whose claimed-slot list overflowed, [6] candidates, [7] how often the plan was rebuilt with the eager
- * pair table because a candidate outgrew the structures of the deferred updates (sized from the input's triples). */
+ * pair table because a candidate outgrew the structures of the deferred updates (sized from the input's triples).
+ * (On the device these are the words plo::BigStat names in plo_cse_big.hip: [0]..[6] are BS_SUM_STEPS .. BS_SUM_CANDIDATES,
+ * [8] BS_SUM_EXTRA_WINDOWS, [9] BS_SUM_ROWS_SEARCHED, [10] BS_SUM_FORCED_MERGES, [11] BS_SUM_MERGE_GROUPS, [12] BS_SUM_MERGE_LOOP;
+ * [7] is kept by the host.) */
 int plo_cse_plan_hbm_counters(const plo_plan_t *plan, uint32_t out[8]);
 /* the same, the first n <= 13 counters: [10] merges of the deferred updates forced by log or hot-table pressure, [11] groups of partitions
  * summed by the merges, [12] records of those groups loaded behind the four prefetched records of a thread, all three summed over the

@@ -29,6 +29,7 @@
 #include <array>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -69,6 +70,125 @@ uint32_t inv_mod(uint32_t a, uint32_t p) {
 }
 uint32_t ceil_log2(uint32_t x) { uint32_t l = 0; while ((1u << l) < x) ++l; return l; }
 uint32_t round_up(uint32_t x, uint32_t a) { return (x + a - 1) / a * a; }
+double seconds_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+// An integer environment knob: unset, or the number strtol reads from it (a flag counts as soon as it is set, whatever it holds)
+std::optional<long> env_knob(const char *name) { const char *e = getenv(name); if (!e) return std::nullopt; return strtol(e, nullptr, 10); }
+
+// Temporary device memory of one call: freed when its scope ends, whichever return is taken
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }      // (move-only: this also deletes the copies)
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    operator T *() const { return p; }
+};
+
+// The event pair around one launch on g_stream: launch() enqueues the kernel, *ms gets its time
+template <class Launch> int timed(float *ms, Launch launch)
+{
+    struct Events { hipEvent_t e0 = nullptr, e1 = nullptr; ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); } } ev;
+    HIPCHK(hipEventCreate(&ev.e0)); HIPCHK(hipEventCreate(&ev.e1));
+    HIPCHK(hipEventRecord(ev.e0, g_stream));
+    launch();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.e1, g_stream)); HIPCHK(hipEventSynchronize(ev.e1));
+    HIPCHK(hipEventElapsedTime(ms, ev.e0, ev.e1));
+    return PLO_OK;
+}
+
+// One timed launch and its statistics: time and count add up over the launches of a call, the shape is the latest launch's.
+// shape == nullptr: time and count only (the sizing launch of the kernel method).
+struct LaunchShape { uint64_t grid; uint32_t lds_bytes, waves_per_wg; uint64_t algo_bytes; };
+template <class Launch> int timed_launch(plo_stats_t *st, const LaunchShape *shape, Launch launch)
+{
+    float ms = 0;
+    const int rc = timed(&ms, launch);
+    if (rc != PLO_OK) return rc;
+    if (!st) return PLO_OK;
+    st->kernel_ms += ms; st->launches += 1;
+    if (shape) { st->grid = (uint32_t)shape->grid; st->lds_bytes = shape->lds_bytes; st->waves_per_wg = shape->waves_per_wg; st->algo_bytes = shape->algo_bytes; }
+    return PLO_OK;
+}
+// the same for a search kernel whose plan holds the shape (trilplacer, inplacer, orbiter, dependency): its candidates are counted too
+template <class Plan, class Launch> int timed_launch(Plan *pl, uint64_t grid, uint64_t ncand, plo_stats_t *st, Launch launch)
+{
+    const LaunchShape shape{grid, pl->lds_bytes, pl->waves_per_wg, pl->algo_bytes};
+    const int rc = timed_launch(st, &shape, launch);
+    if (rc == PLO_OK && st) st->candidates += ncand;
+    return rc;
+}
+
+// Waves (= candidates) per workgroup, 4, 2 or 1, for a kernel that needs lds(w) bytes with w waves: the first count that fits
+// `limit`, or with most_per_cu the count that puts most waves on a CU (32 at most; the larger workgroup on a tie).
+// 0 when not even one wave fits; *lds_out gets the bytes, *per_cu (optional) the waves on a CU.
+template <class Lds> uint32_t pick_waves(Lds lds, bool most_per_cu, uint64_t limit, uint32_t *lds_out, uint32_t *per_cu = nullptr)
+{
+    uint32_t W = 0, bestw = 0;
+    for (uint32_t w : {4u, 2u, 1u}) {
+        const uint64_t l = lds(w);
+        if (l > limit) continue;
+        const uint32_t waves = std::min<uint32_t>(32u, (uint32_t)(limit / l) * w);
+        if (W && (!most_per_cu || waves <= bestw)) continue;
+        bestw = waves; W = w; *lds_out = (uint32_t)l;
+    }
+    if (per_cu) *per_cu = bestw;
+    return W;
+}
+
+// (adds, muls) of a cost key with two fields of `bits` bits: 16 in the 32-bit key of the wave kernels (plo::cost_key32), 20 in the
+// HBM kernel's.  PLO_COST_SUM_THEN_ADD holds (sum, adds); PLO_COST_ADD_THEN_MUL and PLO_COST_RECSUB (adds, muls).
+// A sum-only key (PLO_COST_SUM) holds the sum above `bits` zero bits and no split: false, with the sum in *adds and 0 in *muls.
+// That is what plo_cse_chain_batch and plo_kernel_search report; the plan and chain searches ask the device for the winner's
+// split instead.
+bool decode_key(uint64_t key, int cost_mode, uint32_t bits, uint32_t *adds, uint32_t *muls)
+{
+    const uint32_t hi = (uint32_t)(key >> bits), lo = (uint32_t)(key & ((1ull << bits) - 1ull));
+    if (cost_mode == PLO_COST_SUM_THEN_ADD) { *adds = lo; *muls = hi - lo; }
+    else if (cost_mode == PLO_COST_SUM) { *adds = hi; *muls = 0; return false; }
+    else { *adds = hi; *muls = lo; }
+    return true;
+}
+
+// The minimum under (cost key, seed) over `count` candidates from `first`, in launches of at most `chunk` candidates:
+// run(first seed, count) launches with *d_best as the job's best word and leaves (key << off_bits | seed offset) there.
+// 2^24 candidates and 24 bits for the HBM kernel, 2^32-1 and 32 bits otherwise.  All ones when count == 0.
+template <class Run> int chunked_min(unsigned long long *d_best, uint64_t first, uint64_t count, uint64_t chunk, uint32_t off_bits, uint64_t *bkey, uint64_t *bseed, Run run)
+{
+    *bkey = *bseed = ~0ull;
+    for (uint64_t done = 0; done < count;) {
+        const uint64_t cnt = std::min<uint64_t>(chunk, count - done);
+        HIPCHK(hipMemsetAsync(d_best, 0xFF, sizeof(unsigned long long), g_stream));
+        const int rc = run(first + done, cnt);
+        if (rc != PLO_OK) return rc;
+        unsigned long long w = 0;
+        HIPCHK(hipMemcpy(&w, d_best, sizeof w, hipMemcpyDeviceToHost));
+        const uint64_t key = w >> off_bits, sd = first + done + (w & ((1ull << off_bits) - 1ull));
+        if (key < *bkey || (key == *bkey && sd < *bseed)) { *bkey = key; *bseed = sd; }
+        done += cnt;
+    }
+    return PLO_OK;
+}
+
+// Body of the cost_many entries of the CSE family: adds and muls of n > 0 candidates, and one optional array of 64-bit words
+// that goes in (`seeds`) or comes out (`prods`).  run(d_adds, d_muls, d_words) fills in the job and launches it.
+template <class Run> int cse_cost_many_run(uint64_t n, const uint64_t *seeds, uint32_t *adds, uint32_t *muls, uint64_t *prods, plo_stats_t *st, Run run)
+{
+    DevBuf<uint32_t> d_adds, d_muls; DevBuf<uint64_t> d_words;
+    HIPCHK(hipMalloc((void **)&d_adds.p, n * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&d_muls.p, n * sizeof(uint32_t)));
+    if (seeds || prods) HIPCHK(hipMalloc((void **)&d_words.p, n * sizeof(uint64_t)));
+    if (seeds) HIPCHK(hipMemcpy(d_words, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    int rc = run(d_adds.p, d_muls.p, d_words.p);
+    if (rc == PLO_OK) {
+        hipError_t e1 = hipMemcpy(adds, d_adds, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        hipError_t e2 = hipMemcpy(muls, d_muls, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        hipError_t e3 = prods ? hipMemcpy(prods, d_words, n * sizeof(uint64_t), hipMemcpyDeviceToHost) : hipSuccess;
+        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) rc = fail(PLO_E_HIP, "copy back failed");
+    }
+    st->candidates = n;
+    return rc;
+}
 
 } // namespace
 
@@ -113,6 +233,39 @@ struct plo_plan {
 };
 
 namespace {
+
+// the host copy of the caller's matrix
+void set_matrix(plo_plan *pl, const plo_csr_t *A, uint32_t p)
+{
+    pl->m = A->m; pl->n = A->n; pl->p = p;
+    pl->rowptr.assign(A->rowptr, A->rowptr + A->m + 1);
+    pl->col.assign(A->col, A->col + A->rowptr[A->m]);
+    pl->val.assign(A->val, A->val + A->rowptr[A->m]);
+}
+
+// The LDS image of a wave-kernel candidate, from the shape fields of P (m, n, nnz, NC, cap, mw, unit, multcap): the template is its
+// first tmpl_bytes, the region all of it; the row starts (rs_bytes) are shared by the waves of a workgroup
+void layout_wave_image(plo::WavePlan &P)
+{
+    const uint32_t mw = P.mw;
+    uint32_t off = 0;
+    P.off_tab = off;   off += P.cap * 8u;
+    P.off_val = off;   off += P.nnz * 4u;
+    P.off_inv = off;   off += P.unit ? 0u : P.nnz * 4u;
+    P.off_col = off;   off += P.nnz * 2u;
+    P.off_len = off;   off += P.m * 2u;
+    off = round_up(off, 8);
+    P.off_cmask = off;                      // interleaved {cmask[mw], umask[mw]} per column
+    P.off_umask = off + mw * 8u;
+    P.tmpl_bytes = off + P.n * 2u * mw * 8u;
+    off += P.NC * 2u * mw * 8u;
+    P.off_aff = off;   off += (2u * mw + 1u) * 8u;
+    P.off_ties = off;  off += P.cap * 2u;
+    off = round_up(off, 8);
+    P.off_mult = off;  off += P.multcap * 8u;
+    P.region_bytes = round_up(off, 16);
+    P.rs_bytes = round_up((P.m + 1) * 2u, 16);
+}
 
 // img_out != nullptr: host part only (the template image and the plan fields; P.tmpl is left for the caller)
 int build_plan(plo_plan *pl, std::vector<uint8_t> *img_out = nullptr)
@@ -160,24 +313,8 @@ int build_plan(plo_plan *pl, std::vector<uint8_t> *img_out = nullptr)
     P.multcap = unit ? 0u : (uint32_t)(naive / 2 + 8); P.maxlen = maxlen; P.rb = rb; P.bb = bb;
     if (cap > 65536u) return fail(PLO_E_CAPACITY, "pair table larger than 65536 slots");
     P.mu = p ? (~0ull) / p : 0;
-    uint32_t off = 0;
-    P.off_tab = off;   off += cap * 8u;
-    P.off_val = off;   off += nnz * 4u;
-    P.off_inv = off;   off += unit ? 0u : nnz * 4u;
-    P.off_col = off;   off += nnz * 2u;
-    P.off_len = off;   off += m * 2u;
-    off = round_up(off, 8);
-    P.off_cmask = off;                      // interleaved {cmask[mw], umask[mw]} per column
-    P.off_umask = off + mw * 8u;
-    const uint32_t tmpl_bytes = off + n * 2u * mw * 8u;
-    off += (uint32_t)NC * 2u * mw * 8u;
-    P.tmpl_bytes = tmpl_bytes;
-    P.off_aff = off;   off += (2u * mw + 1u) * 8u;
-    P.off_ties = off;  off += cap * 2u;
-    off = round_up(off, 8);
-    P.off_mult = off;  off += P.multcap * 8u;
-    P.region_bytes = round_up(off, 16);
-    P.rs_bytes = round_up((m + 1) * 2u, 16);
+    layout_wave_image(P);
+    const uint32_t tmpl_bytes = P.tmpl_bytes;
 
     // template image
     std::vector<uint8_t> img(tmpl_bytes + P.rs_bytes, 0);
@@ -207,14 +344,8 @@ int build_plan(plo_plan *pl, std::vector<uint8_t> *img_out = nullptr)
     // waves (= candidates) per workgroup: the choice that puts most waves on a CU
     if (P.rs_bytes + P.region_bytes > g_lds_max)
         return fail(PLO_E_CAPACITY, "candidate state does not fit the 160 KiB LDS of one CU");
-    uint32_t W = 1, bestw = 0;
-    for (uint32_t w : {4u, 2u, 1u}) {
-        const uint32_t lds = P.rs_bytes + w * P.region_bytes;
-        if (lds > g_lds_max) continue;
-        const uint32_t waves = std::min<uint32_t>(32u, (uint32_t)(g_lds_max / lds) * w);
-        if (waves > bestw) { bestw = waves; W = w; }
-    }
-    pl->waves_per_wg = W; pl->lds_bytes = P.rs_bytes + W * P.region_bytes;
+    const uint32_t W = pick_waves([&](uint32_t w) { return P.rs_bytes + w * P.region_bytes; }, true, g_lds_max, &pl->lds_bytes);
+    pl->waves_per_wg = W;
 
     if (img_out) { *img_out = std::move(img); return PLO_OK; }
     if (pl->d_tmpl) { (void)hipFree(pl->d_tmpl); pl->d_tmpl = nullptr; }
@@ -250,9 +381,111 @@ const void *big_kernel_fn(const plo::BigPlan &B)
     return B.mode == 2u ? (const void *)plo::cse_big_kernel<2, false> : B.mode == 1u ? (const void *)plo::cse_big_kernel<1, false> : (const void *)plo::cse_big_kernel<0, false>;
 }
 
+// The PLO_BIG_* knobs of a plan (tests and experiments).  The first six are flags; the clamps of the others are where they are used.
+struct BigPlanKnobs {
+    std::optional<long> vt_global = env_knob("PLO_BIG_VT_GLOBAL"), norid = env_knob("PLO_BIG_NORID"), idkeys = env_knob("PLO_BIG_IDKEYS"),
+                        noprune = env_knob("PLO_BIG_NOPRUNE"), eager = env_knob("PLO_BIG_EAGER"), nodual = env_knob("PLO_BIG_NODUAL");
+    std::optional<long> fwin = env_knob("PLO_BIG_FWIN"), hbits = env_knob("PLO_BIG_HBITS"), logtrig = env_knob("PLO_BIG_LOGTRIG"), hwin = env_knob("PLO_BIG_HWIN"),
+                        hotbits = env_knob("PLO_BIG_HOTBITS"), lgrp = env_knob("PLO_BIG_LGRP"), aggbits = env_knob("PLO_BIG_AGGBITS"), selcap = env_knob("PLO_BIG_SELCAP");
+};
+// ... and of a launch
+struct BigLaunchKnobs { std::optional<long> wg_per_cu = env_knob("PLO_BIG_WG_PER_CU"), slices = env_knob("PLO_BIG_SLICES"), stats = env_knob("PLO_BIG_STATS"); };
+
+// the distinct pair triples of the input, sorted per first column: keys, frequencies, the largest frequency; pairs0 = the pair instances
+struct BigTriples { std::vector<uint64_t> keys; std::vector<uint32_t> cnts; uint64_t pairs0 = 0; uint32_t maxf = 0; };
+
+// Deferred cold updates (plo_cse_big.hip, "Deferred cold updates"): partitioned store + log + hot table instead of the one big table.
+// Taken whenever its LDS budget allows (a partition and its share of the log are summed in a 2^13-slot LDS table); PLO_BIG_EAGER=1
+// keeps the eager table (the A/B switch of the tests).  Sizes the structures in pl->B; st0 and pc0 get the store's image.
+void size_big_deferred(plo_plan *pl, const BigPlanKnobs &K, const BigTriples &T, std::vector<uint64_t> &st0, std::vector<uint32_t> &pc0)
+{
+    plo::BigPlan &B = pl->B;
+    const auto &keys = T.keys; const auto &cnts = T.cnts;
+    const uint32_t m = pl->m;
+    B.defer = 0u;
+    if (!B.prune || K.eager || pl->big_no_defer) return;
+    uint64_t topsum = 0;                                      // entries of the M0 longest rows: a step rewrites at most M0 rows
+    { std::vector<uint32_t> ls(m); for (uint32_t i = 0; i < m; ++i) ls[i] = pl->rowptr[i + 1] - pl->rowptr[i];
+      std::sort(ls.begin(), ls.end(), std::greater<uint32_t>());
+      for (uint32_t i = 0; i < m && i < T.maxf; ++i) topsum += ls[i]; }
+    uint32_t pbits = 0; while ((keys.size() >> pbits) > 1280u && pbits < 11u) ++pbits;
+    const uint32_t Pn = 1u << pbits;
+    pc0.assign(Pn, 0u);
+    auto part = [&](uint64_t k) { return pbits ? (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> (64u - pbits)) : 0u; };   // == plo::dpart
+    for (uint64_t k : keys) ++pc0[part(k)];
+    const uint32_t maxfill = *std::max_element(pc0.begin(), pc0.end());
+    const uint32_t capp = (maxfill + maxfill / 4u + 64u + 1u) & ~1u;
+    const uint64_t hotmax = std::min<uint64_t>(1ull << 17, T.pairs0);               // triples alive at any time <= pair instances of the input
+    const uint64_t stepmax = 3ull * topsum + 3ull * 8192ull;                        // records one step can write
+    if (capp > 5000u) return;
+    const uint64_t lpp = 6080u - capp;                                              // records of a partition's log that still fit the merge beside its live triples (12 records per thread, an LDS table of 2^13 slots)
+    const uint64_t budget = lpp * Pn * 5ull / 6ull;                                 // (hash imbalance of the partitions' shares)
+    if (budget <= stepmax + hotmax + 4096ull) return;
+    uint64_t trig = std::min<uint64_t>(budget - stepmax - hotmax - 4096ull, (uint64_t)PLO_BIG_LOGTRIG_MAX);
+    if (K.logtrig) trig = std::min<uint64_t>(trig, std::max<uint64_t>(1, (uint64_t)*K.logtrig));   // test knob: merges forced by the log
+    const uint64_t logcap = trig + stepmax + hotmax + 4096ull;
+    B.defer = 1u; B.pbits = pbits; B.capp = capp; B.logtrig = (uint32_t)trig; B.logcap = (uint32_t)logcap;
+    B.plcap = (uint32_t)std::min<uint64_t>((logcap * 6ull / 5ull + Pn - 1) / Pn + 64ull, lpp + 64ull);
+    B.hwin = 8192u; if (K.hwin) B.hwin = (uint32_t)std::max<long>(1, *K.hwin);   // test knob: window size (triples kept hot)
+    B.hotbits_min = std::min(16u, std::max(10u, ceil_log2((uint32_t)(4u * std::min<uint64_t>(T.pairs0, 16384u)))));
+    B.hotbits_max = std::max(B.hotbits_min, std::min(19u, ceil_log2((uint32_t)(4u * hotmax + 1024u))));
+    if (K.hotbits) B.hotbits_min = (uint32_t)std::min<long>(B.hotbits_max, std::max<long>(6, *K.hotbits));   // test knob: a full hot table is reported and the launch repeated with a larger one
+    B.lgrp = 3000u; if (K.lgrp) B.lgrp = (uint32_t)std::min<long>(7000, std::max<long>(64, *K.lgrp));   // experiment knob: records per group of partitions summed together
+    st0.assign((size_t)capp * Pn, 0ull);
+    std::vector<uint32_t> fill(Pn, 0u);
+    for (size_t k = 0; k < keys.size(); ++k) { const uint32_t q = part(keys[k]); st0[(size_t)q * capp + fill[q]++] = (keys[k] << PLO_GVB) | 0x8000ull | cnts[k]; }   // a record: key | insert flag | frequency
+}
+
+// workspace layout of one candidate (the eager table has 2^hbits slots; with deferred updates hbits becomes ProgramGen's)
+void layout_big_workspace(plo::BigPlan &B)
+{
+    const uint64_t nnz = B.nnz, m = B.m, NC = B.NCmax, multcap = B.multcap;
+    uint64_t off = 0;
+    auto take = [&](uint64_t bytes) { uint64_t o = off; off = (off + bytes + 255) & ~255ull; return o; };
+    if (B.defer) {
+        // the table region only serves ProgramGen's (column, |v|) multiset: it shares the partitions' logs, idle by then
+        uint64_t pg = 1024; while (pg < 2ull * nnz + 2ull * multcap + 64ull) pg <<= 1;
+        B.hbits = ceil_log2((uint32_t)pg);
+        B.o_store = take(std::max<uint64_t>(((uint64_t)(B.capp + B.plcap) << B.pbits) * 8, pg * 8)); B.o_tab = B.o_store; B.o_plog = 0;
+        B.o_pcount = take(4ull << B.pbits); B.o_ptail = take(4ull << B.pbits);
+        B.o_log = take((uint64_t)B.logcap * 8); B.o_hot = take(8ull << B.hotbits_max);
+    } else B.o_tab = take(8ull << B.hbits);
+    B.o_ent = take((nnz + 128) * 4); B.o_col = take(nnz * 4); B.o_val = take(nnz * 4); B.o_inv = take(nnz * 4);
+    B.o_len = take(m * 4); B.o_ucount = take(NC * 4); B.o_cntM = take(NC * 4);
+    B.o_dm = take((uint64_t)B.dmcap * 8); B.o_hl = take((uint64_t)B.hlcap * 16); B.o_aff = take(m * 32);
+    B.o_ncrptr = take((NC + 2) * 4); B.o_ncr = take((nnz + 64) * 4);
+    B.o_tl = take((nnz + 64) * 4); B.o_clen = take(NC * 4); B.o_keep = take((m + 64) * 4);
+    B.o_multc = take(multcap * 4); B.o_multv = take(multcap * 4);
+    B.o_tcnt = take(NC * 4); B.o_tptr2 = take((NC + 2) * 4); B.o_tlist = take((nnz + 64) * 4); B.o_cols2 = take(NC * 4); B.o_spill = take((nnz + 64) * 8);
+    B.ws_stride = off;
+}
+
+// dynamic LDS: histogram + max(ProgramGen scratch, aggregation table of 2^aggbits u64)
+int size_big_lds(plo_plan *pl, const BigPlanKnobs &K)
+{
+    plo::BigPlan &B = pl->B;
+    const uint32_t maxlen = B.scr_stride;
+    B.aggbits = std::min(13u, std::max(6u, ceil_log2((uint32_t)std::min<uint64_t>(4 * pl->pairs0 + 64, 1u << 13))));
+    if (K.aggbits) B.aggbits = (uint32_t)std::min(14l, std::max(6l, *K.aggbits));
+    // LDS aggregation entry: key | count.  When column, ratio, inverse ratio and a count up to m fit 64 bits the key carries
+    // both x and 1/x (the flush then needs no inversion); otherwise (column, x) with a 16-bit count.
+    { const uint32_t cb = ceil_log2(B.m + 2u);
+      if (B.bb + 2u * B.rb + cb <= 64u && !K.nodual) { B.agg_dual = 1u; B.agg_cb = 64u - B.bb - 2u * B.rb; if (B.agg_cb > 16u) B.agg_cb = 16u; }
+      else { B.agg_dual = 0u; B.agg_cb = 16u; } }
+    // dynamic LDS, in words: histogram, tables of the mode, then max(ProgramGen scratch, aggregation table: 2^aggbits entries of 8 bytes, 6 in mode 2)
+    const uint32_t agg_words = B.mode == 2u ? (1u << B.aggbits) + (1u << B.aggbits) / 2u : 2u << B.aggbits;
+    uint32_t scr_words = std::max<uint32_t>((PLO_BIG_THREADS / 64) * maxlen, agg_words);
+    uint32_t tab_words = B.mode == 1u ? 2u * ((B.nv + 1u) & ~1u) : B.mode == 2u ? ((B.nr + 1u) & ~1u) + PLO_RSTRIDE * PLO_RSTRIDE / 2u + (B.nr + 3u) / 4u * 2u + (B.defer ? 0u : (1u << B.aggbits) / 2u) : 0u;   // mode 2: ratio values, ratio ids, inverse ids, slot list of the aggregation table (eager flush only)
+    if (B.defer) { tab_words += PLO_DBLOOM_WORDS; scr_words = std::max<uint32_t>(scr_words, PLO_DMREG_WORDS - PLO_DBLOOM_WORDS); }   // Bloom filter, and 64 KB in all for the merge
+    pl->big_lds = (((B.maxf0 + 2u) & ~1u) + tab_words + scr_words) * 4u;
+    if (pl->big_lds + sizeof(plo::BigShared) + 64 > g_lds_max) return fail(PLO_E_CAPACITY, "frequency histogram does not fit LDS");
+    return PLO_OK;
+}
+
 // Plan for the HBM-resident kernel family (plo_cse_big.hip)
 int build_big_plan(plo_plan *pl)
 {
+    const BigPlanKnobs K;
     const uint32_t m = pl->m, n = pl->n, p = pl->p;
     const auto &rowptr = pl->rowptr; const auto &col = pl->col; const auto &val = pl->val;
     const uint32_t nnz = rowptr[m];
@@ -267,7 +500,7 @@ int build_big_plan(plo_plan *pl)
     std::sort(dv.begin(), dv.end()); dv.erase(std::unique(dv.begin(), dv.end()), dv.end());
     if (dv.size() > 65536) return fail(PLO_E_CAPACITY, "more than 65536 distinct coefficients: the packed row entry holds a 16-bit value index");
     // at most 32 values: the <= 1024 ratios v_i/v_j get identifiers (kernel mode 2: 6-byte aggregation entries, no product in the sweep)
-    const bool ratio_ids = dv.size() <= 32 && !getenv("PLO_BIG_VT_GLOBAL") && !getenv("PLO_BIG_NORID");
+    const bool ratio_ids = dv.size() <= 32 && !K.vt_global && !K.norid;
     std::vector<uint32_t> rat, rv;
     if (ratio_ids) {
         const uint32_t nv = (uint32_t)dv.size();
@@ -284,7 +517,7 @@ int build_big_plan(plo_plan *pl)
     {
         const uint32_t bbres = rb <= 44u ? (48u - rb) / 2u : 0u;            // column bits beside a residue
         const bool fits = rb <= 30u && bbres >= 2u && n + 2ull <= (1ull << bbres) && std::min<uint64_t>(NC, 32768) <= (1ull << bbres);
-        if ((!fits || getenv("PLO_BIG_IDKEYS")) && ratio_ids && rb <= 31u) { idk = true; kb = std::max(1u, ceil_log2((uint32_t)rv.size())); }   // (PLO_BIG_IDKEYS: test knob, identifiers although residues would fit)
+        if ((!fits || K.idkeys) && ratio_ids && rb <= 31u) { idk = true; kb = std::max(1u, ceil_log2((uint32_t)rv.size())); }   // (PLO_BIG_IDKEYS: test knob, identifiers although residues would fit)
         else if (rb > 30 || bbres < 2u) return fail(PLO_E_CAPACITY, "modulus too large for the 48-bit pair key (and more than 32 distinct coefficients: no ratio identifiers)");
     }
     const uint32_t bbmax = std::min(15u, (48u - kb) / 2u);
@@ -307,7 +540,8 @@ int build_big_plan(plo_plan *pl)
     { std::vector<uint32_t> pos(tptr.begin(), tptr.end() - 1);
       for (uint32_t i = 0; i < m; ++i) for (uint32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) trows[pos[col[k]]++] = i; }
     // distinct pair triples, per first column (listpairs :30-41, PairMap :220-225)
-    std::vector<uint64_t> keys; std::vector<uint32_t> cnts; uint64_t pairs0 = 0; uint32_t maxf = 0;
+    BigTriples T;
+    std::vector<uint64_t> &keys = T.keys; std::vector<uint32_t> &cnts = T.cnts;
     {
         std::vector<uint64_t> tmp;
         for (uint32_t a = 0; a < n; ++a) {
@@ -322,18 +556,19 @@ int build_big_plan(plo_plan *pl)
                     tmp.push_back(((uint64_t)a << (bb + kb)) | ((uint64_t)col[y] << kb) | rr);
                 }
             }
-            pairs0 += tmp.size();
+            T.pairs0 += tmp.size();
             std::sort(tmp.begin(), tmp.end());
             for (size_t k = 0; k < tmp.size();) {
                 size_t j = k; while (j < tmp.size() && tmp[j] == tmp[k]) ++j;
-                keys.push_back(tmp[k]); cnts.push_back((uint32_t)(j - k)); maxf = std::max(maxf, (uint32_t)(j - k)); k = j;
+                keys.push_back(tmp[k]); cnts.push_back((uint32_t)(j - k)); T.maxf = std::max(T.maxf, (uint32_t)(j - k)); k = j;
             }
         }
     }
-    pl->pairs0 = pairs0; pl->distinct0 = keys.size();
+    const uint32_t maxf = T.maxf;
+    pl->pairs0 = T.pairs0; pl->distinct0 = keys.size();
     pl->algo_bytes = 8ull * nnz + 16ull * keys.size();       // distinct-triple form of B_cand for HBM-resident candidates
-    B.prune = getenv("PLO_BIG_NOPRUNE") ? 0u : 1u;
-    B.fwin = 2048u; if (const char *e = getenv("PLO_BIG_FWIN")) B.fwin = (uint32_t)std::min<long>(2048, std::max<long>(64, strtol(e, nullptr, 10) / 64 * 64));   // test knob: windows of the flat sweep (a multiple of 64 entries)
+    B.prune = K.noprune ? 0u : 1u;
+    B.fwin = 2048u; if (K.fwin) B.fwin = (uint32_t)std::min<long>(2048, std::max<long>(64, *K.fwin / 64 * 64));   // test knob: windows of the flat sweep (a multiple of 64 entries)
     if (B.prune) {   // triples of frequency 1 are never chosen and never grow: they are not kept (plo_cse_big.hip, "pruning")
         size_t w = 0;
         for (size_t k = 0; k < keys.size(); ++k) if (cnts[k] >= 2u) { keys[w] = keys[k]; cnts[w] = cnts[k]; ++w; }
@@ -343,7 +578,7 @@ int build_big_plan(plo_plan *pl)
     uint64_t cap = 1024;
     // load <= 0.5 at the start: the retirement of a pruned triple probes to the first empty slot, and dead slots are not empty
     while (cap < (uint64_t)pl->big_cap_scale * (2ull * keys.size() + 1024ull) || cap < 2ull * nnz + 2ull * multcap + 64ull) cap <<= 1;
-    if (const char *e = getenv("PLO_BIG_HBITS")) { const long hb = strtol(e, nullptr, 10); if (hb >= 10 && hb <= 30 && (1ull << hb) > keys.size() + keys.size() / 8) cap = 1ull << hb; }   // experiment knob
+    if (K.hbits) { const long hb = *K.hbits; if (hb >= 10 && hb <= 30 && (1ull << hb) > keys.size() + keys.size() / 8) cap = 1ull << hb; }   // experiment knob
     const uint32_t hbits = ceil_log2((uint32_t)std::min<uint64_t>(cap, 1ull << 31));
     if (cap > (1ull << 30)) return fail(PLO_E_CAPACITY, "pair table above 2^30 slots");
     std::vector<uint32_t> hist(maxf + 2, 0);
@@ -353,45 +588,8 @@ int build_big_plan(plo_plan *pl)
     B.dmcap = (uint32_t)std::min<uint64_t>(1u << 20, cap); B.hlcap = (uint32_t)std::min<uint64_t>(1u << 18, cap);   // window list: <= hlcap/2 keys per window, ping-pong halves
     B.mu = (~0ull) / p;
     B.mers = 0; for (uint32_t k = 2; k < 31; ++k) if (p == (1u << k) - 1u) B.mers = k;     // Mersenne modulus: shift-and-add reduction
-    // Deferred cold updates (plo_cse_big.hip, "Deferred cold updates"): partitioned store + log + hot table instead of the one big table.
-    // Taken whenever its LDS budget allows (a partition and its share of the log are summed in a 2^13-slot LDS table); PLO_BIG_EAGER=1
-    // keeps the eager table (the A/B switch of the tests).
-    B.defer = 0u;
-    uint64_t topsum = 0;                                      // entries of the M0 longest rows: a step rewrites at most M0 rows
-    { std::vector<uint32_t> ls(m); for (uint32_t i = 0; i < m; ++i) ls[i] = rowptr[i + 1] - rowptr[i];
-      std::sort(ls.begin(), ls.end(), std::greater<uint32_t>());
-      for (uint32_t i = 0; i < m && i < maxf; ++i) topsum += ls[i]; }
     std::vector<uint64_t> st0; std::vector<uint32_t> pc0;
-    if (B.prune && !getenv("PLO_BIG_EAGER") && !pl->big_no_defer) {
-        uint32_t pbits = 0; while ((keys.size() >> pbits) > 1280u && pbits < 11u) ++pbits;
-        const uint32_t Pn = 1u << pbits;
-        pc0.assign(Pn, 0u);
-        auto part = [&](uint64_t k) { return pbits ? (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> (64u - pbits)) : 0u; };   // == plo::dpart
-        for (uint64_t k : keys) ++pc0[part(k)];
-        const uint32_t maxfill = *std::max_element(pc0.begin(), pc0.end());
-        const uint32_t capp = (maxfill + maxfill / 4u + 64u + 1u) & ~1u;
-        const uint64_t hotmax = std::min<uint64_t>(1ull << 17, pairs0);                 // triples alive at any time <= pair instances of the input
-        const uint64_t stepmax = 3ull * topsum + 3ull * 8192ull;                        // records one step can write
-        if (capp <= 5000u) {
-            const uint64_t lpp = 6080u - capp;                                            // records of a partition's log that still fit the merge beside its live triples (12 records per thread, an LDS table of 2^13 slots)
-            uint64_t budget = lpp * Pn * 5ull / 6ull;                                      // (hash imbalance of the partitions' shares)
-            if (budget > stepmax + hotmax + 4096ull) {
-                uint64_t trig = std::min<uint64_t>(budget - stepmax - hotmax - 4096ull, (uint64_t)PLO_BIG_LOGTRIG_MAX);
-                if (const char *e = getenv("PLO_BIG_LOGTRIG")) trig = std::min<uint64_t>(trig, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));   // test knob: merges forced by the log
-                const uint64_t logcap = trig + stepmax + hotmax + 4096ull;
-                B.defer = 1u; B.pbits = pbits; B.capp = capp; B.logtrig = (uint32_t)trig; B.logcap = (uint32_t)logcap;
-                B.plcap = (uint32_t)std::min<uint64_t>((logcap * 6ull / 5ull + Pn - 1) / Pn + 64ull, lpp + 64ull);
-                B.hwin = 8192u; if (const char *e = getenv("PLO_BIG_HWIN")) B.hwin = (uint32_t)std::max<long>(1, strtol(e, nullptr, 10));   // test knob: window size (triples kept hot)
-                B.hotbits_min = std::min(16u, std::max(10u, ceil_log2((uint32_t)(4u * std::min<uint64_t>(pairs0, 16384u)))));
-                B.hotbits_max = std::max(B.hotbits_min, std::min(19u, ceil_log2((uint32_t)(4u * hotmax + 1024u))));
-                if (const char *e = getenv("PLO_BIG_HOTBITS")) B.hotbits_min = (uint32_t)std::min<long>(B.hotbits_max, std::max<long>(6, strtol(e, nullptr, 10)));   // test knob: a full hot table is reported and the launch repeated with a larger one
-                B.lgrp = 3000u; if (const char *e = getenv("PLO_BIG_LGRP")) B.lgrp = (uint32_t)std::min<long>(7000, std::max<long>(64, strtol(e, nullptr, 10)));   // experiment knob: records per group of partitions summed together
-                st0.assign((size_t)capp * Pn, 0ull);
-                std::vector<uint32_t> fill(Pn, 0u);
-                for (size_t k = 0; k < keys.size(); ++k) { const uint32_t q = part(keys[k]); st0[(size_t)q * capp + fill[q]++] = (keys[k] << PLO_GVB) | 0x8000ull | cnts[k]; }   // a record: key | insert flag | frequency
-            }
-        }
-    }
+    size_big_deferred(pl, K, T, st0, pc0);
     int rc;
     if ((rc = upload(pl, pl->rowptr, &B.rs)) || (rc = upload(pl, ent, &B.ent0)) || (rc = upload(pl, vt, &B.vt)) ||
         (rc = upload(pl, tptr, &B.tptr)) || (rc = upload(pl, trows, &B.trows)) ||
@@ -406,7 +604,7 @@ int build_big_plan(plo_plan *pl)
         }
         if ((rc = upload(pl, tab, &B.tab0))) return rc;
     }
-    B.nv = (uint32_t)dv.size(); B.vt_lds = (dv.size() <= 512 && !getenv("PLO_BIG_VT_GLOBAL")) ? 1u : 0u;   // (test knob: the global-memory value table)
+    B.nv = (uint32_t)dv.size(); B.vt_lds = (dv.size() <= 512 && !K.vt_global) ? 1u : 0u;   // (test knob: the global-memory value table)
     B.mode = B.vt_lds ? 1u : 0u; B.nr = 0;
     if (ratio_ids) {
         const uint32_t nv = (uint32_t)dv.size();
@@ -422,73 +620,70 @@ int build_big_plan(plo_plan *pl)
         for (uint32_t i = 2; i < p; ++i) it[i] = (uint32_t)((uint64_t)(p - p / i) * it[p % i] % p);
         if ((rc = upload(pl, it, &B.invtab))) return rc;
     }
-    // workspace layout of one candidate
-    uint64_t off = 0;
-    auto take = [&](uint64_t bytes) { uint64_t o = off; off = (off + bytes + 255) & ~255ull; return o; };
-    if (B.defer) {
-        // the table region only serves ProgramGen's (column, |v|) multiset: it shares the partitions' logs, idle by then
-        uint64_t pg = 1024; while (pg < 2ull * nnz + 2ull * multcap + 64ull) pg <<= 1;
-        B.hbits = ceil_log2((uint32_t)pg);
-        B.o_store = take(std::max<uint64_t>(((uint64_t)(B.capp + B.plcap) << B.pbits) * 8, pg * 8)); B.o_tab = B.o_store; B.o_plog = 0;
-        B.o_pcount = take(4ull << B.pbits); B.o_ptail = take(4ull << B.pbits);
-        B.o_log = take((uint64_t)B.logcap * 8); B.o_hot = take(8ull << B.hotbits_max);
-    } else B.o_tab = take(cap * 8);
-    B.o_ent = take(((uint64_t)nnz + 128) * 4); B.o_col = take((uint64_t)nnz * 4); B.o_val = take((uint64_t)nnz * 4); B.o_inv = take((uint64_t)nnz * 4);
-    B.o_len = take((uint64_t)m * 4); B.o_ucount = take(NC * 4); B.o_cntM = take(NC * 4);
-    B.o_dm = take((uint64_t)B.dmcap * 8); B.o_hl = take((uint64_t)B.hlcap * 16); B.o_aff = take((uint64_t)m * 32);
-    B.o_ncrptr = take((NC + 2) * 4); B.o_ncr = take(((uint64_t)nnz + 64) * 4);
-    B.o_tl = take(((uint64_t)nnz + 64) * 4); B.o_clen = take(NC * 4); B.o_keep = take(((uint64_t)m + 64) * 4);
-    B.o_multc = take((uint64_t)multcap * 4); B.o_multv = take((uint64_t)multcap * 4);
-    B.o_tcnt = take(NC * 4); B.o_tptr2 = take((NC + 2) * 4); B.o_tlist = take(((uint64_t)nnz + 64) * 4); B.o_cols2 = take(NC * 4); B.o_spill = take(((uint64_t)nnz + 64) * 8);
-    B.ws_stride = off;
-    // dynamic LDS: histogram + max(ProgramGen scratch, aggregation table of 2^aggbits u64)
-    B.aggbits = std::min(13u, std::max(6u, ceil_log2((uint32_t)std::min<uint64_t>(4 * pairs0 + 64, 1u << 13))));
-    if (const char *e = getenv("PLO_BIG_AGGBITS")) B.aggbits = (uint32_t)std::min(14l, std::max(6l, strtol(e, nullptr, 10)));
-    // LDS aggregation entry: key | count.  When column, ratio, inverse ratio and a count up to m fit 64 bits the key carries
-    // both x and 1/x (the flush then needs no inversion); otherwise (column, x) with a 16-bit count.
-    { const uint32_t cb = ceil_log2(m + 2u);
-      if (bb + 2u * rb + cb <= 64u && !getenv("PLO_BIG_NODUAL")) { B.agg_dual = 1u; B.agg_cb = 64u - bb - 2u * rb; if (B.agg_cb > 16u) B.agg_cb = 16u; }
-      else { B.agg_dual = 0u; B.agg_cb = 16u; } }
-    // dynamic LDS, in words: histogram, tables of the mode, then max(ProgramGen scratch, aggregation table: 2^aggbits entries of 8 bytes, 6 in mode 2)
-    const uint32_t agg_words = B.mode == 2u ? (1u << B.aggbits) + (1u << B.aggbits) / 2u : 2u << B.aggbits;
-    uint32_t scr_words = std::max<uint32_t>((PLO_BIG_THREADS / 64) * maxlen, agg_words);
-    uint32_t tab_words = B.mode == 1u ? 2u * ((B.nv + 1u) & ~1u) : B.mode == 2u ? ((B.nr + 1u) & ~1u) + PLO_RSTRIDE * PLO_RSTRIDE / 2u + (B.nr + 3u) / 4u * 2u + (B.defer ? 0u : (1u << B.aggbits) / 2u) : 0u;   // mode 2: ratio values, ratio ids, inverse ids, slot list of the aggregation table (eager flush only)
-    if (B.defer) { tab_words += PLO_DBLOOM_WORDS; scr_words = std::max<uint32_t>(scr_words, PLO_DMREG_WORDS - PLO_DBLOOM_WORDS); }   // Bloom filter, and 64 KB in all for the merge
-    pl->big_lds = (((B.maxf0 + 2u) & ~1u) + tab_words + scr_words) * 4u;
-    if (pl->big_lds + sizeof(plo::BigShared) + 64 > g_lds_max) return fail(PLO_E_CAPACITY, "frequency histogram does not fit LDS");
+    layout_big_workspace(B);
+    if ((rc = size_big_lds(pl, K))) return rc;
     HIPCHK(hipFuncSetAttribute(big_kernel_fn(B), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->big_lds));
     if (!pl->d_err) HIPCHK(hipMalloc((void **)&pl->d_err, sizeof(uint32_t)));
     if (!pl->d_best) HIPCHK(hipMalloc((void **)&pl->d_best, sizeof(unsigned long long)));
     if (!pl->d_next) HIPCHK(hipMalloc((void **)&pl->d_next, sizeof(unsigned long long)));
-    if (!pl->d_stats) HIPCHK(hipMalloc((void **)&pl->d_stats, 64 * sizeof(uint32_t)));
+    if (!pl->d_stats) HIPCHK(hipMalloc((void **)&pl->d_stats, plo::BS_COUNT * sizeof(uint32_t)));
     B.selcap = PLO_BIG_SELCAP;
-    if (const char *e = getenv("PLO_BIG_SELCAP")) B.selcap = (uint32_t)std::min<long>(PLO_BIG_SELCAP, std::max<long>(1, strtol(e, nullptr, 10)));   // test knob: forces the bisection tie pick
+    if (K.selcap) B.selcap = (uint32_t)std::min<long>(PLO_BIG_SELCAP, std::max<long>(1, *K.selcap));   // test knob: forces the bisection tie pick
     pl->big = true; pl->waves_per_wg = PLO_BIG_THREADS / 64; pl->lds_bytes = pl->big_lds + (uint32_t)sizeof(plo::BigShared);
     return PLO_OK;
 }
 
-// The event pair around one launch on g_stream: launch() enqueues the kernel, *ms gets its time
-template <class Launch> int timed(float *ms, Launch launch)
+// frees the plan's device buffers and builds the plan again (a larger table, or the eager one: the caller has set which)
+int rebuild_big_plan(plo_plan *pl)
 {
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, g_stream));
-    launch();
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, g_stream)); HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return PLO_OK;
+    for (void *d : pl->big_bufs) (void)hipFree(d);
+    pl->big_bufs.clear();
+    if (pl->d_ws) { (void)hipFree(pl->d_ws); pl->d_ws = nullptr; pl->ws_slices = 0; }
+    return build_big_plan(pl);
+}
+
+// PLO_BIG_STATS: the counters and phase clocks of the launch that just ended, on stderr
+void print_big_stats(const plo_plan *pl)
+{
+    using namespace plo;
+    uint32_t hs[BS_COUNT] = {0};
+    if (hipMemcpy(hs, pl->d_stats, sizeof hs, hipMemcpyDeviceToHost) != hipSuccess) return;
+    const uint32_t ncand = hs[BS_SUM_CANDIDATES], *mg = hs + BS_LAST_MERGE_US, *ms = hs + BS_LAST_MERGE_SUM_US, *ph = hs + BS_LAST_PHASE_US, *pg = hs + BS_LAST_PGEN_PHASE_US;
+    if (pl->B.defer && ncand) fprintf(stderr, "# big kernel, deferred updates: per candidate %.1f merges (%.2f forced by log/hot pressure), %.0f log records, %.0f hot-table updates; last candidate, merge us: hot->log %u, partition pass %u, sum + write back %u, window %u\n",
+            (double)hs[BS_SUM_FULLSCANS] / ncand, (double)hs[BS_SUM_FORCED_MERGES] / ncand, ((double)hs[BS_SUM_LOG_HI] * 4294967296.0 + hs[BS_SUM_LOG_LO]) / ncand, (double)hs[BS_SUM_HOTOPS] / ncand, mg[0], mg[1], mg[2], mg[3]);
+    if (pl->B.defer && hs[BS_LAST_MERGE_GROUPS]) fprintf(stderr, "#   merge, sum + write back of the last candidate: %u groups; us: sum (loads + table) %u, scan + write back %u, clear + bounds %u\n", hs[BS_LAST_MERGE_GROUPS], ms[0], ms[1], ms[3]);
+    fprintf(stderr, "# big kernel (last candidate): steps %u, full scans %u, level rebuilds %u; phase us: level %u select %u rows %u sweep1 %u flush1 %u sweep2 %u flush2 %u tail %u\n",
+            hs[BS_LAST_STEPS], hs[BS_LAST_FULLSCANS], hs[BS_LAST_REBUILDS], ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6], ph[7]);
+    fprintf(stderr, "# big kernel (last candidate): image load + CSE phase %u us, ProgramGen %u us\n", hs[BS_LAST_CSE_US], hs[BS_LAST_PGEN_US]);
+    fprintf(stderr, "# big kernel (last candidate): image load alone %u us; ProgramGen us: table fill + flags %u, expand + A1 %u, A2 %u, A3 + B + count %u, Triangle set-up %u, Triangle %u, D %u\n",
+            hs[BS_LAST_LOAD_US], pg[0], pg[1], pg[2], pg[3], pg[4], pg[5], pg[6]);
+#ifdef PLO_BIG_PROFILE
+    { unsigned long long g2[40] = {0}; if (hipMemcpyFromSymbol(g2, HIP_SYMBOL(plo::g_prof2), sizeof g2) == hipSuccess && g2[32]) {
+        static const char *cls[4] = {">=256", "64..255", "16..63", "<16"};
+        for (int c_ = 0; c_ < 4; ++c_) { fprintf(stderr, "#   rows/step %-8s ms per candidate: level %.1f select %.1f rows %.1f sweep %.1f flush1 %.1f flush2 %.1f tail %.1f\n", cls[c_],
+            g2[c_ * 8 + 0] / 1e5 / g2[32], g2[c_ * 8 + 1] / 1e5 / g2[32], g2[c_ * 8 + 2] / 1e5 / g2[32], g2[c_ * 8 + 3] / 1e5 / g2[32], g2[c_ * 8 + 4] / 1e5 / g2[32], (g2[c_ * 8 + 6] + g2[c_ * 8 + 5]) / 1e5 / g2[32], g2[c_ * 8 + 7] / 1e5 / g2[32]); } } }
+    { unsigned long long gp[16] = {0};
+      if (hipMemcpyFromSymbol(gp, HIP_SYMBOL(plo::g_prof), sizeof gp) != hipSuccess) memset(gp, 0, sizeof gp);
+      if (gp[3]) fprintf(stderr, "#   sweep of the steps with >= 256 rows, all candidates: %llu trips by %llu wave-sweeps; cycles per trip: chunk wait + stores %.0f, aggregation of both chunks %.0f, rest of the loop %.0f; per wave-sweep %.0f cycles, %.1f trips; probe rounds per trip %.2f, active lanes per trip %.1f\n", gp[3], gp[5], (double)gp[0] / gp[3], (double)gp[1] / gp[3], (double)gp[2] / gp[3], (double)gp[4] / gp[5], (double)gp[3] / gp[5], (double)gp[6] / gp[3], (double)gp[7] / gp[3]);
+      if (gp[3] && pl->B.defer && pl->B.mode == 2u) fprintf(stderr, "#   aggregation of a trip (lane 0 of every wave, big steps), cycles: ratio-id lookup %.0f, pair read %.0f, compare-and-swap %.0f, bitmap + count %.0f\n", (double)gp[14] / gp[3], (double)gp[8] / gp[3], (double)gp[9] / gp[3], (double)gp[10] / gp[3]);
+      if ((gp[14] || gp[15]) && !pl->B.defer) fprintf(stderr, "#   flush 1, all candidates: entries whose pair with a has a as SECOND column %llu, with b %llu\n", gp[14], gp[15]);
+      if (gp[11]) fprintf(stderr, "#   flush 1 of the steps with >= 256 rows: %llu wave-trips by %llu wave-flushes; cycles per trip: fetch + decode %.0f, probe loads %.0f, stores + bookkeeping %.0f; per wave-flush %.0f cycles, %.1f trips\n", gp[11], gp[13], (double)gp[8] / gp[11], (double)gp[9] / gp[11], (double)gp[10] / gp[11], (double)gp[12] / gp[13], (double)gp[11] / gp[13]);
+    }
+    { const uint32_t *s1 = hs + BS_PROF_SWEEP1_US, *s2 = hs + BS_PROF_SWEEP2_US, *nb = hs + BS_PROF_STEPS;
+      fprintf(stderr, "#   steps by rows/step [>=256, 64.., 16.., <16]: %u %u %u %u; sweep1 us %u %u %u %u; sweep2 us %u %u %u %u; fallbacks %u %u; flushed keys %u %u\n",
+            nb[0], nb[1], nb[2], nb[3], s1[0], s1[1], s1[2], s1[3], s2[0], s2[1], s2[2], s2[3], hs[BS_PROF_FALLBACK1], hs[BS_PROF_FALLBACK2], hs[BS_PROF_FLUSHED1], hs[BS_PROF_FLUSHED2]); }
+#endif
 }
 
 // launch of the HBM-resident kernel over J.ncand candidates
 int launch_big(plo_plan *pl, plo::BigJob J, plo_stats_t *st)
 {
+    const BigLaunchKnobs K;
     // one workspace slice per resident workgroup
     uint64_t per_cu = 2;                  // = the resident workgroups (LDS-limited); more slices only enlarge the footprint
-    if (const char *e = getenv("PLO_BIG_WG_PER_CU")) per_cu = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    if (K.wg_per_cu) per_cu = std::max<uint64_t>(1, (uint64_t)*K.wg_per_cu);
     uint64_t want = std::min<uint64_t>(J.ncand, (uint64_t)g_cus * per_cu);
-    if (const char *e = getenv("PLO_BIG_SLICES")) want = std::min<uint64_t>(want, strtoull(e, nullptr, 10));
+    if (K.slices) want = std::min<uint64_t>(want, (uint64_t)*K.slices);
     if (want == 0) want = 1;
     if (pl->ws_slices < want) {
         if (pl->d_ws) { (void)hipFree(pl->d_ws); pl->d_ws = nullptr; pl->ws_slices = 0; }
@@ -503,62 +698,21 @@ int launch_big(plo_plan *pl, plo::BigJob J, plo_stats_t *st)
     pl->B.ws = (uint8_t *)pl->d_ws;
     HIPCHK(hipMemsetAsync(pl->d_err, 0, sizeof(uint32_t), g_stream));
     HIPCHK(hipMemsetAsync(pl->d_next, 0, sizeof(unsigned long long), g_stream));
-    HIPCHK(hipMemsetAsync(pl->d_stats, 0, 64 * sizeof(uint32_t), g_stream));
+    HIPCHK(hipMemsetAsync(pl->d_stats, 0, plo::BS_COUNT * sizeof(uint32_t), g_stream));
     J.err = pl->d_err; J.next = pl->d_next; J.stats = pl->d_stats;
-    float ms = 0;
-    const int trc = timed(&ms, [&] {
-        const plo::BigPlan &B = pl->B;
-        if (B.defer) {
-            if (B.idk) hipLaunchKernelGGL((plo::cse_big_kernel<2, true, true>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
-            else if (B.mode == 2u) hipLaunchKernelGGL((plo::cse_big_kernel<2, true>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
-            else if (B.mode == 1u) hipLaunchKernelGGL((plo::cse_big_kernel<1, true>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
-            else hipLaunchKernelGGL((plo::cse_big_kernel<0, true>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
-        } else {
-            if (B.idk) hipLaunchKernelGGL((plo::cse_big_kernel<2, false, true>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
-            else if (B.mode == 2u) hipLaunchKernelGGL((plo::cse_big_kernel<2, false>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
-            else if (B.mode == 1u) hipLaunchKernelGGL((plo::cse_big_kernel<1, false>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
-            else hipLaunchKernelGGL((plo::cse_big_kernel<0, false>), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), pl->big_lds, g_stream, pl->B, J);
-        }
-    });
+    const LaunchShape shape{grid, pl->lds_bytes, pl->waves_per_wg, pl->algo_bytes};
+    void *args[] = {&pl->B, &J};
+    const int trc = timed_launch(st, &shape, [&] { (void)hipLaunchKernel(big_kernel_fn(pl->B), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), args, pl->big_lds, g_stream); });
     if (trc != PLO_OK) return trc;
     uint32_t err = 0;
     HIPCHK(hipMemcpy(&err, pl->d_err, sizeof err, hipMemcpyDeviceToHost));
-    if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = pl->lds_bytes; st->waves_per_wg = pl->waves_per_wg; st->algo_bytes = pl->algo_bytes; }
-    if (getenv("PLO_BIG_STATS")) {
-        uint32_t hs[64] = {0};
-        if (hipMemcpy(hs, pl->d_stats, sizeof hs, hipMemcpyDeviceToHost) == hipSuccess) {
-            if (pl->B.defer && hs[38]) fprintf(stderr, "# big kernel, deferred updates: per candidate %.1f merges (%.2f forced by log/hot pressure), %.0f log records, %.0f hot-table updates; last candidate, merge us: hot->log %u, partition pass %u, sum + write back %u, window %u\n",
-                    (double)hs[33] / hs[38], (double)hs[39] / hs[38], ((double)hs[42] * 4294967296.0 + hs[41]) / hs[38], (double)hs[40] / hs[38], hs[44], hs[45], hs[46], hs[47]);
-            if (pl->B.defer && hs[52]) fprintf(stderr, "#   merge, sum + write back of the last candidate: %u groups; us: sum (loads + table) %u, scan + write back %u, clear + bounds %u\n", hs[52], hs[48], hs[49], hs[51]);
-            fprintf(stderr, "# big kernel (last candidate): steps %u, full scans %u, level rebuilds %u; phase us: level %u select %u rows %u sweep1 %u flush1 %u sweep2 %u flush2 %u tail %u\n",
-                    hs[0], hs[1], hs[2], hs[4], hs[5], hs[6], hs[7], hs[8], hs[9], hs[10], hs[11]);
-            fprintf(stderr, "# big kernel (last candidate): image load + CSE phase %u us, ProgramGen %u us\n", hs[55], hs[56]);
-            fprintf(stderr, "# big kernel (last candidate): image load alone %u us; ProgramGen us: table fill + flags %u, expand + A1 %u, A2 %u, A3 + B + count %u, Triangle set-up %u, Triangle %u, D %u\n",
-                    hs[12], hs[57], hs[58], hs[59], hs[60], hs[61], hs[62], hs[63]);
-#ifdef PLO_BIG_PROFILE
-            { unsigned long long g2[40] = {0}; if (hipMemcpyFromSymbol(g2, HIP_SYMBOL(plo::g_prof2), sizeof g2) == hipSuccess && g2[32]) {
-                static const char *cls[4] = {">=256", "64..255", "16..63", "<16"};
-                for (int c_ = 0; c_ < 4; ++c_) { fprintf(stderr, "#   rows/step %-8s ms per candidate: level %.1f select %.1f rows %.1f sweep %.1f flush1 %.1f flush2 %.1f tail %.1f\n", cls[c_],
-                    g2[c_ * 8 + 0] / 1e5 / g2[32], g2[c_ * 8 + 1] / 1e5 / g2[32], g2[c_ * 8 + 2] / 1e5 / g2[32], g2[c_ * 8 + 3] / 1e5 / g2[32], g2[c_ * 8 + 4] / 1e5 / g2[32], (g2[c_ * 8 + 6] + g2[c_ * 8 + 5]) / 1e5 / g2[32], g2[c_ * 8 + 7] / 1e5 / g2[32]); } } }
-            { unsigned long long gp[16] = {0}; if (hipMemcpyFromSymbol(gp, HIP_SYMBOL(plo::g_prof), sizeof gp) == hipSuccess && gp[3]) fprintf(stderr, "#   sweep of the steps with >= 256 rows, all candidates: %llu trips by %llu wave-sweeps; cycles per trip: chunk wait + stores %.0f, aggregation of both chunks %.0f, rest of the loop %.0f; per wave-sweep %.0f cycles, %.1f trips; probe rounds per trip %.2f, active lanes per trip %.1f\n", gp[3], gp[5], (double)gp[0] / gp[3], (double)gp[1] / gp[3], (double)gp[2] / gp[3], (double)gp[4] / gp[5], (double)gp[3] / gp[5], (double)gp[6] / gp[3], (double)gp[7] / gp[3]); }
-            { unsigned long long gp[16] = {0}; if (hipMemcpyFromSymbol(gp, HIP_SYMBOL(plo::g_prof), sizeof gp) == hipSuccess && gp[3] && pl->B.defer && pl->B.mode == 2u) fprintf(stderr, "#   aggregation of a trip (lane 0 of every wave, big steps), cycles: ratio-id lookup %.0f, pair read %.0f, compare-and-swap %.0f, bitmap + count %.0f\n", (double)gp[14] / gp[3], (double)gp[8] / gp[3], (double)gp[9] / gp[3], (double)gp[10] / gp[3]); }
-            { unsigned long long gp[16] = {0}; if (hipMemcpyFromSymbol(gp, HIP_SYMBOL(plo::g_prof), sizeof gp) == hipSuccess && (gp[14] || gp[15]) && !pl->B.defer) fprintf(stderr, "#   flush 1, all candidates: entries whose pair with a has a as SECOND column %llu, with b %llu\n", gp[14], gp[15]); }
-            { unsigned long long gp[16] = {0}; if (hipMemcpyFromSymbol(gp, HIP_SYMBOL(plo::g_prof), sizeof gp) == hipSuccess && gp[11]) fprintf(stderr, "#   flush 1 of the steps with >= 256 rows: %llu wave-trips by %llu wave-flushes; cycles per trip: fetch + decode %.0f, probe loads %.0f, stores + bookkeeping %.0f; per wave-flush %.0f cycles, %.1f trips\n", gp[11], gp[13], (double)gp[8] / gp[11], (double)gp[9] / gp[11], (double)gp[10] / gp[11], (double)gp[12] / gp[13], (double)gp[11] / gp[13]); }
-            fprintf(stderr, "#   steps by rows/step [>=256, 64.., 16.., <16]: %u %u %u %u; sweep1 us %u %u %u %u; sweep2 us %u %u %u %u; fallbacks %u %u; flushed keys %u %u\n",
-                    hs[24], hs[25], hs[26], hs[27], hs[16], hs[17], hs[18], hs[19], hs[20], hs[21], hs[22], hs[23], hs[28], hs[29], hs[30], hs[31]);
-#endif
-        }
-    }
+    if (K.stats) print_big_stats(pl);
     if (err == plo::BERR_TABLE && !pl->B.defer && pl->big_cap_scale < 256u) {
         // eager table full: the live triples of frequency >= 2 can outnumber the input's (new columns pair with every column of the rows
         // they enter); four times the slots and again (the workspace grows, fewer candidates are resident)
         pl->big_cap_scale *= 4u; ++pl->big_refits;
-        for (void *d : pl->big_bufs) (void)hipFree(d);
-        pl->big_bufs.clear();
-        if (pl->d_ws) { (void)hipFree(pl->d_ws); pl->d_ws = nullptr; pl->ws_slices = 0; }
-        const int rc = build_big_plan(pl);
-        if (rc != PLO_OK) return rc;
-        return launch_big(pl, J, st);
+        const int rc = rebuild_big_plan(pl);
+        return rc != PLO_OK ? rc : launch_big(pl, J, st);
     }
     if (err == plo::BERR_TABLE && pl->B.defer && !pl->big_no_defer) {
         // The structures of the deferred updates are sized from the INPUT's triples (a partition's live triples: its initial share + 25 %;
@@ -566,16 +720,12 @@ int launch_big(plo_plan *pl, plo::BigJob J, plo_stats_t *st)
         // with few distinct values do (tests/soak_hbm.py) -- is reported by the device.  The plan is rebuilt with the eager table of
         // round 2 (sized for every pair instance of the input, dead slots reclaimed) and the launch repeated: same results, slower.
         pl->big_no_defer = true; ++pl->big_refits;
-        for (void *d : pl->big_bufs) (void)hipFree(d);
-        pl->big_bufs.clear();
-        if (pl->d_ws) { (void)hipFree(pl->d_ws); pl->d_ws = nullptr; pl->ws_slices = 0; }
-        const int rc = build_big_plan(pl);
-        if (rc != PLO_OK) return rc;
-        return launch_big(pl, J, st);
+        const int rc = rebuild_big_plan(pl);
+        return rc != PLO_OK ? rc : launch_big(pl, J, st);
     }
     if (err) {
         static const char *names[] = {"pair table", "frequency/row-count mismatch", "column bound", "level list", "window list", "multiplier list", "tie selection", "ProgramGen"};
-        uint32_t site = 0; (void)hipMemcpy(&site, pl->d_stats + 43, sizeof site, hipMemcpyDeviceToHost);
+        uint32_t site = 0; (void)hipMemcpy(&site, pl->d_stats + plo::BS_ERR_SITE, sizeof site, hipMemcpyDeviceToHost);
         // BERR_PGEN: ProgramGen's Triangle keeps the rows of a column one per lane (more than 64 rows with a non +-1 entry in one column), or its
         // multiset does not fit the table region: a limit of this build, not an inconsistency -- the tools then search on the host
         return fail(err == plo::BERR_COLS || err == plo::BERR_DM || err == plo::BERR_HL ? PLO_E_CAPACITY : err == plo::BERR_PGEN ? PLO_E_UNSUPPORTED : PLO_E_INTERNAL,
@@ -585,7 +735,7 @@ int launch_big(plo_plan *pl, plo::BigJob J, plo_stats_t *st)
 }
 
 // one launch over [first, first+count) candidates of a job
-int launch(plo_plan *pl, plo::WaveJob J, plo_stats_t *st, float *ms_out)
+int launch(plo_plan *pl, plo::WaveJob J, plo_stats_t *st)
 {
     const uint32_t W = pl->waves_per_wg;
     uint64_t need = (J.ncand + W - 1) / W;
@@ -593,16 +743,14 @@ int launch(plo_plan *pl, plo::WaveJob J, plo_stats_t *st, float *ms_out)
     if (grid == 0) grid = 1;
     HIPCHK(hipMemsetAsync(pl->d_err, 0, sizeof(uint32_t), g_stream));
     J.err = pl->d_err;
-    float ms = 0;
-    const int trc = timed(&ms, [&] {
+    const LaunchShape shape{grid, pl->lds_bytes, W, pl->algo_bytes};
+    const int trc = timed_launch(st, &shape, [&] {
         if (pl->P.unit) hipLaunchKernelGGL(plo::cse_wave_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), pl->lds_bytes, g_stream, pl->P, J);
         else hipLaunchKernelGGL(plo::cse_wave_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), pl->lds_bytes, g_stream, pl->P, J);
     });
     if (trc != PLO_OK) return trc;
     uint32_t err = 0;
     HIPCHK(hipMemcpy(&err, pl->d_err, sizeof err, hipMemcpyDeviceToHost));
-    if (ms_out) *ms_out = ms;
-    if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = pl->lds_bytes; st->waves_per_wg = W; st->algo_bytes = pl->algo_bytes; }
 #ifdef PLO_WAVE_PROFILE
     if (getenv("PLO_WAVE_STATS")) {
         unsigned long long g[12] = {0};
@@ -628,7 +776,7 @@ int device_error(int err) {
 int run_job(plo_plan *pl, plo::WaveJob J, plo_stats_t *st)
 {
     for (int attempt = 0; attempt < 4; ++attempt) {
-        int err = launch(pl, J, st, nullptr);
+        int err = launch(pl, J, st);
         if (err < 0) return err;
         if (err == 0) return PLO_OK;
         if (err != plo::ERR_TABLE) return device_error(err);
@@ -640,6 +788,16 @@ int run_job(plo_plan *pl, plo::WaveJob J, plo_stats_t *st)
     return device_error(plo::ERR_TABLE);
 }
 
+// a job of random-restart candidates on the plan's own kernel family
+int run_plan_job(plo_plan *pl, uint64_t seed0, const uint64_t *seeds, uint64_t n, uint32_t *adds, uint32_t *muls, unsigned long long *best, int cost_mode, plo_stats_t *st)
+{
+    if (pl->big) {
+        plo::BigJob J{}; J.seed0 = seed0; J.seeds = seeds; J.ncand = n; J.adds = adds; J.muls = muls; J.best = best; J.cost_mode = (uint32_t)cost_mode;
+        return launch_big(pl, J, st);
+    }
+    plo::WaveJob J{}; J.seed0 = seed0; J.seeds = seeds; J.ncand = n; J.adds = adds; J.muls = muls; J.best = best; J.cost_mode = (uint32_t)cost_mode;
+    return run_job(pl, J, st);
+}
 
 } // namespace
 
@@ -656,14 +814,7 @@ int chain_config(plo_chain *ch)
     const plo::WavePlan &A = ch->st[0]->P, &B = ch->st[1]->P;
     const uint32_t region = std::max(A.region_bytes, B.region_bytes), fixed = A.rs_bytes + B.rs_bytes;
     if (fixed + region > g_lds_max) return fail(PLO_E_CAPACITY, "chained candidate state does not fit LDS");
-    uint32_t W = 1, bestw = 0;
-    for (uint32_t w : {4u, 2u, 1u}) {
-        const uint32_t lds = fixed + w * region;
-        if (lds > g_lds_max) continue;
-        const uint32_t waves = std::min<uint32_t>(32u, (uint32_t)(g_lds_max / lds) * w);
-        if (waves > bestw) { bestw = waves; W = w; }
-    }
-    ch->W = W; ch->lds = fixed + W * region;
+    const uint32_t W = ch->W = pick_waves([&](uint32_t w) { return fixed + w * region; }, true, g_lds_max, &ch->lds);
     HIPCHK(hipFuncSetAttribute((const void *)plo::cse_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ch->lds));
     int nb = 0;
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)plo::cse_chain_kernel, (int)(W * 64), ch->lds));
@@ -679,13 +830,11 @@ int run_chain(plo_chain *ch, plo::WaveJob J, plo_stats_t *st)
         const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * ch->blocks_per_cu, need));
         HIPCHK(hipMemsetAsync(p0->d_err, 0, sizeof(uint32_t), g_stream));
         J.err = p0->d_err;
-        float ms = 0;
-        const int trc = timed(&ms, [&] { hipLaunchKernelGGL(plo::cse_chain_kernel, dim3((uint32_t)grid), dim3(ch->W * 64), ch->lds, g_stream, ch->st[0]->P, ch->st[1]->P, J); });
+        const LaunchShape shape{grid, ch->lds, ch->W, ch->st[0]->algo_bytes + ch->st[1]->algo_bytes};
+        const int trc = timed_launch(st, &shape, [&] { hipLaunchKernelGGL(plo::cse_chain_kernel, dim3((uint32_t)grid), dim3(ch->W * 64), ch->lds, g_stream, ch->st[0]->P, ch->st[1]->P, J); });
         if (trc != PLO_OK) return trc;
         uint32_t err = 0;
         HIPCHK(hipMemcpy(&err, p0->d_err, sizeof err, hipMemcpyDeviceToHost));
-        if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = ch->lds; st->waves_per_wg = ch->W;
-                  st->algo_bytes = ch->st[0]->algo_bytes + ch->st[1]->algo_bytes; }
         if (err == 0) return PLO_OK;
         if (err != plo::ERR_TABLE) return device_error((int)err);
         for (int k = 0; k < 2; ++k) { ch->st[k]->cap_scale *= 2; int rc = build_plan(ch->st[k]); if (rc != PLO_OK) return rc; }
@@ -741,10 +890,7 @@ int plo_cse_plan_create_ex(const plo_csr_t *A, uint32_t p, uint32_t flags, plo_p
     if (g_device < 0) { int rc = plo_init(0); if (rc != PLO_OK) return rc; }
     if (const char *bad = csr_defect(A, p)) return fail(PLO_E_ARG, bad);
     plo_plan *pl = new plo_plan();
-    pl->m = A->m; pl->n = A->n; pl->p = p;
-    pl->rowptr.assign(A->rowptr, A->rowptr + A->m + 1);
-    pl->col.assign(A->col, A->col + A->rowptr[A->m]);
-    pl->val.assign(A->val, A->val + A->rowptr[A->m]);
+    set_matrix(pl, A, p);
     int rc = (flags & PLO_PLAN_HBM) ? PLO_E_CAPACITY : build_plan(pl);
     if (rc == PLO_E_CAPACITY) rc = build_big_plan(pl);       // does not fit LDS: HBM-resident kernel family
     if (rc != PLO_OK) { plo_cse_plan_destroy(pl); return rc; }
@@ -760,9 +906,9 @@ int plo_cse_plan_hbm_counters(const plo_plan_t *pl, uint32_t out[8])
 {
     if (!pl || !out) return fail(PLO_E_ARG, "null argument");
     if (!pl->big || !pl->d_stats) return fail(PLO_E_UNSUPPORTED, "the counters belong to the HBM-resident kernel family");
-    uint32_t hs[64];
+    uint32_t hs[plo::BS_COUNT];
     HIPCHK(hipMemcpy(hs, pl->d_stats, sizeof hs, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 7; ++k) out[k] = hs[32 + k];
+    for (int k = 0; k < 7; ++k) out[k] = hs[plo::BS_SUM_STEPS + k];      // ... BS_SUM_CANDIDATES
     out[7] = pl->big_refits;
     return PLO_OK;
 }
@@ -773,10 +919,10 @@ int plo_cse_plan_hbm_counters_ex(const plo_plan_t *pl, uint32_t *out, uint32_t n
     uint32_t o[13] = {0};
     const int rc = plo_cse_plan_hbm_counters(pl, o);
     if (rc != PLO_OK) return rc;
-    uint32_t hs[64];
+    uint32_t hs[plo::BS_COUNT];
     HIPCHK(hipMemcpy(hs, pl->d_stats, sizeof hs, hipMemcpyDeviceToHost));
-    o[8] = hs[53]; o[9] = hs[54];
-    o[10] = hs[39]; o[11] = hs[13]; o[12] = hs[14];         // the merge: forced by log / hot pressure, groups summed, records loaded behind the prefetch
+    o[8] = hs[plo::BS_SUM_EXTRA_WINDOWS]; o[9] = hs[plo::BS_SUM_ROWS_SEARCHED];
+    o[10] = hs[plo::BS_SUM_FORCED_MERGES]; o[11] = hs[plo::BS_SUM_MERGE_GROUPS]; o[12] = hs[plo::BS_SUM_MERGE_LOOP];         // the merge: forced by log / hot pressure, groups summed, records loaded behind the prefetch
     for (uint32_t k = 0; k < n; ++k) out[k] = o[k];
     return PLO_OK;
 }
@@ -814,26 +960,10 @@ int plo_cse_cost_many_plan(plo_plan_t *pl, const uint64_t *seeds, uint64_t seed0
     plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
     auto t0 = std::chrono::steady_clock::now();
     if (n == 0) return PLO_OK;
-    uint32_t *d_adds = nullptr, *d_muls = nullptr; uint64_t *d_seeds = nullptr;
-    HIPCHK(hipMalloc((void **)&d_adds, n * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&d_muls, n * sizeof(uint32_t)));
-    if (seeds) { HIPCHK(hipMalloc((void **)&d_seeds, n * sizeof(uint64_t))); HIPCHK(hipMemcpy(d_seeds, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice)); }
-    int rc;
-    if (pl->big) {
-        plo::BigJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.adds = d_adds; J.muls = d_muls; J.best = nullptr; J.cost_mode = 0;
-        rc = launch_big(pl, J, st);
-    } else {
-        plo::WaveJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.adds = d_adds; J.muls = d_muls; J.best = nullptr; J.cost_mode = 0;
-        rc = run_job(pl, J, st);
-    }
-    if (rc == PLO_OK) {
-        hipError_t e1 = hipMemcpy(adds, d_adds, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        hipError_t e2 = hipMemcpy(muls, d_muls, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (e1 != hipSuccess || e2 != hipSuccess) rc = fail(PLO_E_HIP, "copy back failed");
-    }
-    (void)hipFree(d_adds); (void)hipFree(d_muls); if (d_seeds) (void)hipFree(d_seeds);
-    st->candidates = n;
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const int rc = cse_cost_many_run(n, seeds, adds, muls, nullptr, st, [&](uint32_t *d_adds, uint32_t *d_muls, uint64_t *d_seeds) {
+        return run_plan_job(pl, seed0, d_seeds, n, d_adds, d_muls, nullptr, 0, st);
+    });
+    st->seconds = seconds_since(t0);
     return rc;
 }
 
@@ -858,58 +988,23 @@ int plo_cse_search_plan(plo_plan_t *pl, uint64_t seed0, uint64_t nseeds, int cos
     auto t0 = std::chrono::steady_clock::now();
     out->adds = out->muls = 0xFFFFFFFFu; out->seed = ~0ull;
     uint64_t bkey = ~0ull, bseed = ~0ull;
-    if (pl->big) {
-        const uint64_t CHB = 1ull << 24;                      // 24-bit seed offsets in the 64-bit cost word of the HBM variant
-        uint32_t ba = 0, bm = 0;
-        for (uint64_t done = 0; done < nseeds;) {
-            const uint64_t cnt = std::min<uint64_t>(CHB, nseeds - done);
-            HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, sizeof(unsigned long long), g_stream));
-            plo::BigJob J{}; J.seed0 = seed0 + done; J.seeds = nullptr; J.ncand = cnt; J.best = pl->d_best; J.cost_mode = (uint32_t)cost_mode;
-            int rc = launch_big(pl, J, st);
-            if (rc != PLO_OK) return rc;
-            unsigned long long w = 0;
-            HIPCHK(hipMemcpy(&w, pl->d_best, sizeof w, hipMemcpyDeviceToHost));
-            const uint64_t key = w >> 24, sd = seed0 + done + (w & 0xFFFFFFull);
-            if (key < bkey || (key == bkey && sd < bseed)) { bkey = key; bseed = sd; }
-            done += cnt;
-        }
-        if (nseeds) {
-            if (cost_mode == PLO_COST_SUM_THEN_ADD) { ba = (uint32_t)(bkey & 0xFFFFFu); bm = (uint32_t)(bkey >> 20) - ba; }
-            else if (cost_mode == PLO_COST_ADD_THEN_MUL) { ba = (uint32_t)(bkey >> 20); bm = (uint32_t)(bkey & 0xFFFFFu); }
-            else { plo_stats_t s2{}; int rc = plo_cse_cost_many_plan(pl, &bseed, 0, 1, &ba, &bm, &s2); if (rc != PLO_OK) return rc; }
-            out->adds = ba; out->muls = bm; out->seed = bseed;
-        }
-        st->candidates = nseeds;
-        st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return PLO_OK;
-    }
-    const uint64_t CH = 0xFFFFFFFFull;                        // seed offsets inside a launch are 32-bit
-    for (uint64_t done = 0; done < nseeds;) {
-        const uint64_t cnt = std::min<uint64_t>(CH, nseeds - done);
-        HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, sizeof(unsigned long long), g_stream));
-        plo::WaveJob J{}; J.seed0 = seed0 + done; J.seeds = nullptr; J.ncand = cnt; J.best = pl->d_best; J.cost_mode = (uint32_t)cost_mode;
-        int rc = run_job(pl, J, st);
-        if (rc != PLO_OK) return rc;
-        unsigned long long w = 0;
-        HIPCHK(hipMemcpy(&w, pl->d_best, sizeof w, hipMemcpyDeviceToHost));
-        const uint64_t key = w >> 32, sd = seed0 + done + (w & 0xFFFFFFFFull);
-        if (key < bkey || (key == bkey && sd < bseed)) { bkey = key; bseed = sd; }
-        done += cnt;
-    }
+    const bool big = pl->big;             // the 64-bit cost word of the HBM variant: 20-bit fields over 24-bit seed offsets; 16 over 32 otherwise
+    int rc = chunked_min(pl->d_best, seed0, nseeds, big ? 1ull << 24 : 0xFFFFFFFFull, big ? 24u : 32u, &bkey, &bseed, [&](uint64_t s0, uint64_t cnt) {
+        return run_plan_job(pl, s0, nullptr, cnt, nullptr, nullptr, pl->d_best, cost_mode, st);
+    });
+    if (rc != PLO_OK) return rc;
     if (nseeds) {
         uint32_t a = 0, mu = 0;
-        if (cost_mode == PLO_COST_SUM_THEN_ADD) { a = (uint32_t)(bkey & 0xFFFFu); mu = (uint32_t)(bkey >> 16) - a; }
-        else if (cost_mode == PLO_COST_ADD_THEN_MUL) { a = (uint32_t)(bkey >> 16); mu = (uint32_t)(bkey & 0xFFFFu); }
-        else {
+        if (!decode_key(bkey, cost_mode, big ? 20u : 16u, &a, &mu)) {
             plo_stats_t s2{};                                                // sum-only key: ask the device for the split
-            int rc = plo_cse_cost_many_plan(pl, &bseed, 0, 1, &a, &mu, &s2);
+            rc = plo_cse_cost_many_plan(pl, &bseed, 0, 1, &a, &mu, &s2);
             if (rc != PLO_OK) return rc;
-            if ((plo_pack_cost(a, mu, cost_mode, 0) >> 32) != bkey) return fail(PLO_E_INTERNAL, "winner cost does not match the reduced key");
+            if (!big && (plo_pack_cost(a, mu, cost_mode, 0) >> 32) != bkey) return fail(PLO_E_INTERNAL, "winner cost does not match the reduced key");
         }
         out->adds = a; out->muls = mu; out->seed = bseed;
     }
     st->candidates = nseeds;
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    st->seconds = seconds_since(t0);
     return PLO_OK;
 }
 
@@ -923,22 +1018,12 @@ int plo_cse_enum_cost_many_plan(plo_plan_t *pl, uint64_t first, uint64_t n, uint
     auto t0 = std::chrono::steady_clock::now();
     if (n == 0) return PLO_OK;
     if (n > 0xFFFFFFFFull) return fail(PLO_E_ARG, "at most 2^32-1 schedules per call");
-    uint32_t *d_adds = nullptr, *d_muls = nullptr; unsigned long long *d_prods = nullptr;
-    HIPCHK(hipMalloc((void **)&d_adds, n * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&d_muls, n * sizeof(uint32_t)));
-    if (prods) HIPCHK(hipMalloc((void **)&d_prods, n * sizeof(unsigned long long)));
-    plo::WaveJob J{}; J.seed0 = first; J.seeds = nullptr; J.ncand = n; J.adds = d_adds; J.muls = d_muls; J.best = nullptr; J.cost_mode = 0;
-    J.enumerate = 1u; J.prods = d_prods; J.prodmax = nullptr;
-    int rc = run_job(pl, J, st);
-    if (rc == PLO_OK) {
-        hipError_t e1 = hipMemcpy(adds, d_adds, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        hipError_t e2 = hipMemcpy(muls, d_muls, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        hipError_t e3 = prods ? hipMemcpy(prods, d_prods, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) : hipSuccess;
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) rc = fail(PLO_E_HIP, "copy back failed");
-    }
-    (void)hipFree(d_adds); (void)hipFree(d_muls); if (d_prods) (void)hipFree(d_prods);
-    st->candidates = n;
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const int rc = cse_cost_many_run(n, nullptr, adds, muls, prods, st, [&](uint32_t *d_adds, uint32_t *d_muls, uint64_t *d_prods) {
+        plo::WaveJob J{}; J.seed0 = first; J.seeds = nullptr; J.ncand = n; J.adds = d_adds; J.muls = d_muls; J.best = nullptr; J.cost_mode = 0;
+        J.enumerate = 1u; J.prods = (unsigned long long *)d_prods; J.prodmax = nullptr;
+        return run_job(pl, J, st);
+    });
+    st->seconds = seconds_since(t0);
     return rc;
 }
 
@@ -951,38 +1036,22 @@ int plo_cse_enum_search_plan(plo_plan_t *pl, uint64_t first, uint64_t count, int
     plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
     auto t0 = std::chrono::steady_clock::now();
     out->adds = out->muls = 0xFFFFFFFFu; out->seed = ~0ull; *maxprod = 0;
-    unsigned long long *d_pm = nullptr;
-    HIPCHK(hipMalloc((void **)&d_pm, sizeof(unsigned long long)));
+    DevBuf<unsigned long long> d_pm;
+    HIPCHK(hipMalloc((void **)&d_pm.p, sizeof(unsigned long long)));
     HIPCHK(hipMemsetAsync(d_pm, 0, sizeof(unsigned long long), g_stream));
     uint64_t bkey = ~0ull, bidx = ~0ull;
-    const uint64_t CH = 0xFFFFFFFFull;
-    int rc = PLO_OK;
-    for (uint64_t done = 0; done < count && rc == PLO_OK;) {
-        const uint64_t cnt = std::min<uint64_t>(CH, count - done);
-        if (hipMemsetAsync(pl->d_best, 0xFF, sizeof(unsigned long long), g_stream) != hipSuccess) { rc = fail(PLO_E_HIP, "memset"); break; }
-        plo::WaveJob J{}; J.seed0 = first + done; J.seeds = nullptr; J.ncand = cnt; J.best = pl->d_best; J.cost_mode = (uint32_t)cost_mode;
+    const int rc = chunked_min(pl->d_best, first, count, 0xFFFFFFFFull, 32, &bkey, &bidx, [&](uint64_t s0, uint64_t cnt) {
+        plo::WaveJob J{}; J.seed0 = s0; J.seeds = nullptr; J.ncand = cnt; J.best = pl->d_best; J.cost_mode = (uint32_t)cost_mode;
         J.enumerate = 1u; J.prodmax = d_pm;
-        rc = run_job(pl, J, st);
-        if (rc != PLO_OK) break;
-        unsigned long long w = 0;
-        if (hipMemcpy(&w, pl->d_best, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(PLO_E_HIP, "copy back"); break; }
-        const uint64_t key = w >> 32, ix = first + done + (w & 0xFFFFFFFFull);
-        if (key < bkey || (key == bkey && ix < bidx)) { bkey = key; bidx = ix; }
-        done += cnt;
-    }
-    unsigned long long pm = 0;
-    if (rc == PLO_OK && hipMemcpy(&pm, d_pm, sizeof pm, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back");
-    (void)hipFree(d_pm);
+        return run_job(pl, J, st);
+    });
     if (rc != PLO_OK) return rc;
-    if (count) {
-        uint32_t a, mu;
-        if (cost_mode == PLO_COST_SUM_THEN_ADD) { a = (uint32_t)(bkey & 0xFFFFu); mu = (uint32_t)(bkey >> 16) - a; }
-        else { a = (uint32_t)(bkey >> 16); mu = (uint32_t)(bkey & 0xFFFFu); }
-        out->adds = a; out->muls = mu; out->seed = bidx;
-    }
+    unsigned long long pm = 0;
+    HIPCHK(hipMemcpy(&pm, d_pm, sizeof pm, hipMemcpyDeviceToHost));
+    if (count) { decode_key(bkey, cost_mode, 16u, &out->adds, &out->muls); out->seed = bidx; }
     *maxprod = pm;
     st->candidates = count;
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    st->seconds = seconds_since(t0);
     return PLO_OK;
 }
 
@@ -1287,10 +1356,9 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
                     const long long k = next.fetch_add(1);
                     if (k >= 2ll * npairs) break;
                     const plo_csr_t *A = (k & 1) ? &seconds[k >> 1] : &firsts[k >> 1];
-                    plo_plan tmp; tmp.m = A->m; tmp.n = A->n; tmp.p = p; tmp.cap_scale = cap_scale;
+                    plo_plan tmp; tmp.cap_scale = cap_scale;
                     if (!A->rowptr || (A->rowptr[A->m] && (!A->col || !A->val))) { rcs[k] = PLO_E_ARG; errs[k] = "null matrix arrays"; continue; }
-                    tmp.rowptr.assign(A->rowptr, A->rowptr + A->m + 1);
-                    tmp.col.assign(A->col, A->col + A->rowptr[A->m]); tmp.val.assign(A->val, A->val + A->rowptr[A->m]);
+                    set_matrix(&tmp, A, p);
                     rcs[k] = build_plan(&tmp, &imgs[k]);
                     if (rcs[k] != PLO_OK) errs[k] = g_err; else plans[k] = tmp.P;
                 }
@@ -1304,56 +1372,43 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
         for (size_t k = 0; k < rcs.size(); ++k) if (rcs[k] != PLO_OK) return fail(rcs[k], "pair " + std::to_string(k >> 1) + ": " + errs[k]);
         uint32_t region = 0, rsmax = 0; size_t total = 0; std::vector<size_t> offs(imgs.size());
         for (size_t k = 0; k < imgs.size(); ++k) { region = std::max(region, plans[k].region_bytes); rsmax = std::max(rsmax, plans[k].rs_bytes); offs[k] = total; total += round_up((uint32_t)imgs[k].size(), 64); }
-        uint32_t W = 0, lds = 0;
-        for (uint32_t w : {4u, 2u, 1u}) { const uint32_t l = 64u + w * (2u * rsmax + region); if (l <= g_lds_max) { W = w; lds = l; break; } }
+        uint32_t lds = 0;
+        const uint32_t W = pick_waves([&](uint32_t w) { return 64u + w * (2u * rsmax + region); }, false, g_lds_max, &lds);
         if (!W) return fail(PLO_E_CAPACITY, "chained candidate state does not fit LDS");
-        uint8_t *d_img = nullptr; plo::WavePlan *d_plans = nullptr; uint32_t *d_adds = nullptr, *d_muls = nullptr, *d_err = nullptr; unsigned long long *d_best = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
+        DevBuf<uint8_t> d_img; DevBuf<plo::WavePlan> d_plans; DevBuf<uint32_t> d_adds, d_muls, d_err; DevBuf<unsigned long long> d_best;
         std::vector<uint8_t> blob(total + 64, 0);
         for (size_t k = 0; k < imgs.size(); ++k) std::memcpy(blob.data() + offs[k], imgs[k].data(), imgs[k].size());
-        auto cleanup = [&]() { if (d_img) (void)hipFree(d_img); if (d_plans) (void)hipFree(d_plans); if (d_adds) (void)hipFree(d_adds); if (d_muls) (void)hipFree(d_muls); if (d_err) (void)hipFree(d_err); if (d_best) (void)hipFree(d_best); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); e0 = e1 = nullptr; };
-#define BCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(PLO_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-        BCHK(hipMalloc((void **)&d_img, blob.size()));
-        BCHK(hipMemcpy(d_img, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc((void **)&d_img.p, blob.size()));
+        HIPCHK(hipMemcpy(d_img, blob.data(), blob.size(), hipMemcpyHostToDevice));
         for (size_t k = 0; k < plans.size(); ++k) plans[k].tmpl = (const uint64_t *)(d_img + offs[k]);
-        BCHK(hipMalloc((void **)&d_plans, plans.size() * sizeof(plo::WavePlan)));
-        BCHK(hipMemcpy(d_plans, plans.data(), plans.size() * sizeof(plo::WavePlan), hipMemcpyHostToDevice));
-        BCHK(hipMalloc((void **)&d_err, 4)); BCHK(hipMemsetAsync(d_err, 0, 4, g_stream));
-        BCHK(hipMalloc((void **)&d_best, 8)); BCHK(hipMemsetAsync(d_best, 0xFF, 8, g_stream));
-        if (adds) BCHK(hipMalloc((void **)&d_adds, ncand * 4));
-        if (muls) BCHK(hipMalloc((void **)&d_muls, ncand * 4));
-        BCHK(hipFuncSetAttribute((const void *)plo::cse_chain_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipMalloc((void **)&d_plans.p, plans.size() * sizeof(plo::WavePlan)));
+        HIPCHK(hipMemcpy(d_plans, plans.data(), plans.size() * sizeof(plo::WavePlan), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc((void **)&d_err.p, 4)); HIPCHK(hipMemsetAsync(d_err, 0, 4, g_stream));
+        HIPCHK(hipMalloc((void **)&d_best.p, 8)); HIPCHK(hipMemsetAsync(d_best, 0xFF, 8, g_stream));
+        if (adds) HIPCHK(hipMalloc((void **)&d_adds.p, ncand * 4));
+        if (muls) HIPCHK(hipMalloc((void **)&d_muls.p, ncand * 4));
+        HIPCHK(hipFuncSetAttribute((const void *)plo::cse_chain_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int nb = 0;
-        BCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)plo::cse_chain_batch_kernel, (int)(W * 64), lds));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)plo::cse_chain_batch_kernel, (int)(W * 64), lds));
         const uint64_t need = (ncand + W - 1) / W;
         const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * std::max(nb, 1), need));
-        plo::WaveJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = ncand; J.adds = d_adds; J.muls = d_muls; J.best = best ? d_best : nullptr; J.cost_mode = (uint32_t)cost_mode; J.err = d_err;
-        BCHK(hipEventCreate(&e0)); BCHK(hipEventCreate(&e1));
-        BCHK(hipEventRecord(e0, g_stream));
-        hipLaunchKernelGGL(plo::cse_chain_batch_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, (const plo::WavePlan *)d_plans, per_pair, region, rsmax, J);
-        BCHK(hipGetLastError());
-        BCHK(hipEventRecord(e1, g_stream)); BCHK(hipEventSynchronize(e1));
-        float ms = 0; BCHK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); e0 = e1 = nullptr;
+        plo::WaveJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = ncand; J.adds = d_adds; J.muls = d_muls; J.best = best ? d_best.p : nullptr; J.cost_mode = (uint32_t)cost_mode; J.err = d_err;
+        const LaunchShape shape{grid, lds, W, 0};
+        const int trc = timed_launch(st, &shape, [&] { hipLaunchKernelGGL(plo::cse_chain_batch_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, (const plo::WavePlan *)d_plans, per_pair, region, rsmax, J); });
+        if (trc != PLO_OK) return trc;
+        st->candidates = ncand;
         uint32_t err = 0; unsigned long long w = 0;
-        BCHK(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost));
-        st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = lds; st->waves_per_wg = W; st->candidates = ncand;
-        if (err == plo::ERR_TABLE) { cleanup(); continue; }                         // a pair table filled up: all plans again with twice the slots
-        if (err) { cleanup(); return device_error((int)err); }
-        if (adds) BCHK(hipMemcpy(adds, d_adds, ncand * 4, hipMemcpyDeviceToHost));
-        if (muls) BCHK(hipMemcpy(muls, d_muls, ncand * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost));
+        if (err == plo::ERR_TABLE) continue;                                        // a pair table filled up: all plans again with twice the slots
+        if (err) return device_error((int)err);
+        if (adds) HIPCHK(hipMemcpy(adds, d_adds, ncand * 4, hipMemcpyDeviceToHost));
+        if (muls) HIPCHK(hipMemcpy(muls, d_muls, ncand * 4, hipMemcpyDeviceToHost));
         if (best) {
-            BCHK(hipMemcpy(&w, d_best, 8, hipMemcpyDeviceToHost));
-            const uint64_t key = w >> 32, off = w & 0xFFFFFFFFull;
-            uint32_t a = 0, mu = 0;
-            if (cost_mode == PLO_COST_SUM_THEN_ADD) { a = (uint32_t)(key & 0xFFFFu); mu = (uint32_t)(key >> 16) - a; }
-            else if (cost_mode == PLO_COST_ADD_THEN_MUL) { a = (uint32_t)(key >> 16); mu = (uint32_t)(key & 0xFFFFu); }
-            else { a = (uint32_t)(key >> 16); mu = 0; }                             // sum only (cost_key32: the sum above 16 zero bits): reported in .adds
-            best->adds = a; best->muls = mu; best->seed = seed0 + off;
+            HIPCHK(hipMemcpy(&w, d_best, 8, hipMemcpyDeviceToHost));
+            decode_key(w >> 32, cost_mode, 16u, &best->adds, &best->muls);          // (a sum-only key: the sum in .adds)
+            best->seed = seed0 + (w & 0xFFFFFFFFull);
         }
-#undef BCHK
-        cleanup();
-        st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        st->seconds = seconds_since(t0);
         return PLO_OK;
     }
     return device_error(plo::ERR_TABLE);
@@ -1392,22 +1447,7 @@ int layout_plan(plo::WavePlan &P, uint32_t m, uint32_t n, uint32_t nnz, uint32_t
     P.m = m; P.n = n; P.nnz = nnz; P.p = p; P.NC = (uint32_t)NC; P.cap = cap; P.hbits = ceil_log2(cap);
     P.lpr_log2 = std::max(2u, ceil_log2(std::max(maxlen, 1u))); P.mw = mw; P.unit = 0u;
     P.multcap = (uint32_t)(naive / 2 + 8); P.maxlen = maxlen; P.rb = rb; P.bb = bb; P.mu = (~0ull) / p;
-    uint32_t off = 0;
-    P.off_tab = off;   off += cap * 8u;
-    P.off_val = off;   off += nnz * 4u;
-    P.off_inv = off;   off += nnz * 4u;
-    P.off_col = off;   off += nnz * 2u;
-    P.off_len = off;   off += m * 2u;
-    off = round_up(off, 8);
-    P.off_cmask = off; P.off_umask = off + mw * 8u;
-    P.tmpl_bytes = off + n * 2u * mw * 8u;
-    off += (uint32_t)NC * 2u * mw * 8u;
-    P.off_aff = off;   off += (2u * mw + 1u) * 8u;
-    P.off_ties = off;  off += cap * 2u;
-    off = round_up(off, 8);
-    P.off_mult = off;  off += P.multcap * 8u;
-    P.region_bytes = round_up(off, 16);
-    P.rs_bytes = round_up((m + 1) * 2u, 16);
+    layout_wave_image(P);
     return PLO_OK;
 }
 } // namespace
@@ -1430,25 +1470,18 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
     if (ndeps > 64) return fail(PLO_E_UNSUPPORTED, "more than 64 dependent rows: Dep's ProgramGen keeps one row per lane");
     if (R == 0) return fail(PLO_E_UNSUPPORTED, "zero matrix");
 
-    uint8_t *d_img = nullptr; uint64_t *d_rsD = nullptr; uint32_t *d_adds = nullptr, *d_muls = nullptr, *d_info = nullptr, *d_err = nullptr, *d_sz = nullptr; unsigned long long *d_best = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&]() {
-        for (void *q : {(void *)d_img, (void *)d_rsD, (void *)d_adds, (void *)d_muls, (void *)d_info, (void *)d_err, (void *)d_sz, (void *)d_best}) if (q) (void)hipFree(q);
-        d_img = nullptr; d_rsD = nullptr; d_adds = d_muls = d_info = d_err = d_sz = nullptr; d_best = nullptr;
-        if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); e0 = e1 = nullptr;
-    };
-#define KCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(PLO_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
     uint32_t pairs_max = 0, ent_max = 0;
     // Dep's table starts at 0.75 x the sampled PAIR count (an upper bound of its distinct triples, usually far above it): a
     // smaller image means more resident waves; a full table is reported by the device and the launch repeated with twice the slots
     for (uint32_t cap_scale = 1; cap_scale <= 32; cap_scale *= 2) {
         plo::KPlan K{};
+        DevBuf<uint8_t> d_img; DevBuf<uint32_t> d_adds, d_muls, d_info, d_err, d_sz; DevBuf<unsigned long long> d_best;      // of this attempt
         // plan and image of M (the layout of Free)
-        plo_plan tmp; tmp.m = m; tmp.n = n; tmp.p = p; tmp.cap_scale = std::max(2u, cap_scale);
-        tmp.rowptr.assign(M->rowptr, M->rowptr + m + 1); tmp.col.assign(M->col, M->col + M->rowptr[m]); tmp.val.assign(M->val, M->val + M->rowptr[m]);
+        plo_plan tmp; tmp.cap_scale = std::max(2u, cap_scale);
+        set_matrix(&tmp, M, p);
         std::vector<uint8_t> img;
         int rc = build_plan(&tmp, &img);
-        if (rc != PLO_OK) { cleanup(); return rc; }
+        if (rc != PLO_OK) return rc;
         K.PM = tmp.P; K.m = m; K.n = n; K.rank = R; K.ndeps = ndeps; K.per_block = per_block;
         K.mers = 0; for (uint32_t kk = 2; kk < 31; ++kk) if (p == (1u << kk) - 1u) K.mers = kk;
         uint32_t off = 0;
@@ -1464,29 +1497,25 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
         K.scratch_bytes = round_up(off, 16);
         K.off_vc = round_up(K.PM.tmpl_bytes, 16);                                 // V (m x (n+1)) and C (m x (rank+1)) of the elimination, behind M's template
         const uint32_t vc_end = K.off_vc + m * (n + 1u + R + 1u) * 4u;
-        KCHK(hipMalloc((void **)&d_img, img.size() + 64)); KCHK(hipMemcpy(d_img, img.data(), img.size(), hipMemcpyHostToDevice));
-        K.PM.tmpl = (const uint64_t *)d_img;
-        KCHK(hipMalloc((void **)&d_err, 4)); KCHK(hipMemsetAsync(d_err, 0, 4, g_stream));
-        KCHK(hipEventCreate(&e0)); KCHK(hipEventCreate(&e1));
+        HIPCHK(hipMalloc((void **)&d_img.p, img.size() + 64)); HIPCHK(hipMemcpy(d_img, img.data(), img.size(), hipMemcpyHostToDevice));
+        K.PM.tmpl = (const uint64_t *)d_img.p;
+        HIPCHK(hipMalloc((void **)&d_err.p, 4)); HIPCHK(hipMemsetAsync(d_err, 0, 4, g_stream));
         if (cap_scale == 1) {
             // sizing launch: Dep's pair count over a sample of the decompositions
             K.region = round_up(std::max(K.PM.region_bytes, vc_end), 16);
             if (depc_inside) { const uint32_t at = round_up(std::max(K.PM.region_bytes, vc_end), 16); K.region = at + depc_bytes; K.off_depc = -(int32_t)depc_bytes; }
-            uint32_t W = 0, lds = 0;
-            for (uint32_t w : {4u, 2u, 1u}) { const uint32_t l = K.PM.rs_bytes + w * (K.region + K.scratch_bytes); if (l <= g_lds_max) { W = w; lds = l; break; } }
-            if (!W) { cleanup(); return fail(PLO_E_CAPACITY, "kernel-method state does not fit LDS"); }
-            KCHK(hipMalloc((void **)&d_sz, 16)); KCHK(hipMemsetAsync(d_sz, 0, 16, g_stream));
-            KCHK(hipFuncSetAttribute((const void *)plo::kmethod_size_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            uint32_t lds = 0;
+            const uint32_t W = pick_waves([&](uint32_t w) { return K.PM.rs_bytes + w * (K.region + K.scratch_bytes); }, false, g_lds_max, &lds);
+            if (!W) return fail(PLO_E_CAPACITY, "kernel-method state does not fit LDS");
+            HIPCHK(hipMalloc((void **)&d_sz.p, 16)); HIPCHK(hipMemsetAsync(d_sz, 0, 16, g_stream));
+            HIPCHK(hipFuncSetAttribute((const void *)plo::kmethod_size_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             plo::WaveJob J{}; J.seed0 = seed0; J.ncand = std::min<uint64_t>(nrestarts, 4096); J.err = d_err;
             const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * 2u, (J.ncand + W - 1) / W));
-            KCHK(hipEventRecord(e0, g_stream));
-            hipLaunchKernelGGL(plo::kmethod_size_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, d_sz);
-            KCHK(hipGetLastError());
-            KCHK(hipEventRecord(e1, g_stream)); KCHK(hipEventSynchronize(e1));
-            float ms = 0; KCHK(hipEventElapsedTime(&ms, e0, e1)); st->kernel_ms += ms; st->launches += 1;
+            const int trc = timed_launch(st, nullptr, [&] { hipLaunchKernelGGL(plo::kmethod_size_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, d_sz.p); });
+            if (trc != PLO_OK) return trc;
             uint32_t sz[4] = {0, 0, 0, 0};
-            KCHK(hipMemcpy(sz, d_sz, 16, hipMemcpyDeviceToHost));
-            if (sz[2]) { cleanup(); return device_error(plo::ERR_KDEC); }
+            HIPCHK(hipMemcpy(sz, d_sz, 16, hipMemcpyDeviceToHost));
+            if (sz[2]) return device_error(plo::ERR_KDEC);
             pairs_max = sz[0]; ent_max = sz[1];
             if (const char *e = getenv("PLO_KMETHOD_PAIRS_DIV")) pairs_max /= (uint32_t)std::max(1l, strtol(e, nullptr, 10));   // test knob: undersized first table, exercises the repeat-with-more-slots path
         }
@@ -1499,7 +1528,7 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
         uint32_t entD = (cap_scale == 1 && !getenv("PLO_KMETHOD_HARD_BOUNDS")) ? std::min<uint32_t>(ndeps * R, ent_max + (uint32_t)((uint64_t)ent_max * (getenv("PLO_KMETHOD_ENT_MARGIN") ? (uint32_t)atoi(getenv("PLO_KMETHOD_ENT_MARGIN")) : 60u) / 100u) + 16u) : ndeps * R;
         if (const char *e = getenv("PLO_KMETHOD_ENT_DIV")) { if (cap_scale == 1) entD = std::max<uint32_t>(R, entD / (uint32_t)std::max(1l, strtol(e, nullptr, 10))); }   // test knob: undersized entry arrays, exercises the repeat-with-hard-bounds path
         rc = layout_plan(K.PD, ndeps, m, entD, p, R, entD, capD);
-        if (rc != PLO_OK) { cleanup(); return rc; }
+        if (rc != PLO_OK) return rc;
         K.rsD = nullptr;                                                          // Dep's row starts are computed per restart on the device
         K.region = round_up(std::max(std::max(K.PM.region_bytes, K.PD.region_bytes), vc_end), 16);
         if (depc_inside) {
@@ -1510,35 +1539,30 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
             K.region = std::max(K.region, at + depc_bytes);
             K.off_depc = (int32_t)at - (int32_t)K.region;
         }
-        uint32_t W = 0, lds = 0, bestw = 0;
-        for (uint32_t w : {4u, 2u, 1u}) {
-            const uint32_t l = K.PM.rs_bytes + K.PD.rs_bytes + w * (K.region + K.scratch_bytes);
-            if (l > g_lds_max) continue;
-            const uint32_t waves = std::min<uint32_t>(32u, (uint32_t)(g_lds_max / l) * w);
-            if (waves > bestw) { bestw = waves; W = w; lds = l; }
-        }
-        if (!W) { cleanup(); return fail(PLO_E_CAPACITY, "kernel-method state does not fit LDS"); }
+        uint32_t lds = 0, bestw = 0;
+        const uint32_t W = pick_waves([&](uint32_t w) { return K.PM.rs_bytes + K.PD.rs_bytes + w * (K.region + K.scratch_bytes); }, true, g_lds_max, &lds, &bestw);
+        if (!W) return fail(PLO_E_CAPACITY, "kernel-method state does not fit LDS");
         if (getenv("PLO_KM_DEBUG")) fprintf(stderr, "# kernel method layout: region of M %u B (table %u slots), of Dep %u B (table %u slots, sampled pairs %u, entries %u of at most %u), elimination arrays end at %u B, scratch %u B; %u waves per workgroup, %u B of LDS, %u waves per CU\n",
                                             K.PM.region_bytes, K.PM.cap, K.PD.region_bytes, K.PD.cap, pairs_max, K.PD.nnz, ndeps * R, vc_end, K.scratch_bytes, W, lds, bestw);
-        KCHK(hipMalloc((void **)&d_best, 8)); KCHK(hipMemsetAsync(d_best, 0xFF, 8, g_stream));
-        if (adds) KCHK(hipMalloc((void **)&d_adds, nrestarts * 4));
-        if (muls) KCHK(hipMalloc((void **)&d_muls, nrestarts * 4));
-        if (info) KCHK(hipMalloc((void **)&d_info, nrestarts * 12));
+        HIPCHK(hipMalloc((void **)&d_best.p, 8)); HIPCHK(hipMemsetAsync(d_best, 0xFF, 8, g_stream));
+        if (adds) HIPCHK(hipMalloc((void **)&d_adds.p, nrestarts * 4));
+        if (muls) HIPCHK(hipMalloc((void **)&d_muls.p, nrestarts * 4));
+        if (info) HIPCHK(hipMalloc((void **)&d_info.p, nrestarts * 12));
         const void *fn = K.PM.unit ? (const void *)plo::kmethod_kernel<true> : (const void *)plo::kmethod_kernel<false>;
-        KCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int nb = 0;
-        KCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)(W * 64), lds));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)(W * 64), lds));
         const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * std::max(nb, 1), (nrestarts + W - 1) / W));
-        plo::WaveJob J{}; J.seed0 = seed0; J.ncand = nrestarts; J.adds = d_adds; J.muls = d_muls; J.best = best ? d_best : nullptr; J.cost_mode = (uint32_t)cost_mode; J.err = d_err;
-        plo::KInfo I{d_info};
-        KCHK(hipEventRecord(e0, g_stream));
-        if (K.PM.unit) hipLaunchKernelGGL(plo::kmethod_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I);
-        else hipLaunchKernelGGL(plo::kmethod_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I);
-        KCHK(hipGetLastError());
-        KCHK(hipEventRecord(e1, g_stream)); KCHK(hipEventSynchronize(e1));
-        float ms = 0; KCHK(hipEventElapsedTime(&ms, e0, e1));
-        uint32_t err = 0; KCHK(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost));
-        st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = lds; st->waves_per_wg = W; st->candidates = nrestarts;
+        plo::WaveJob J{}; J.seed0 = seed0; J.ncand = nrestarts; J.adds = d_adds; J.muls = d_muls; J.best = best ? d_best.p : nullptr; J.cost_mode = (uint32_t)cost_mode; J.err = d_err;
+        plo::KInfo I{d_info.p};
+        const LaunchShape shape{grid, lds, W, 0};
+        const int trc = timed_launch(st, &shape, [&] {
+            if (K.PM.unit) hipLaunchKernelGGL(plo::kmethod_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I);
+            else hipLaunchKernelGGL(plo::kmethod_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I);
+        });
+        if (trc != PLO_OK) return trc;
+        uint32_t err = 0; HIPCHK(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost));
+        st->candidates = nrestarts;
 #ifdef PLO_KM_PROFILE
         if (getenv("PLO_KM_STATS")) {
             unsigned long long g[8] = {0};
@@ -1547,26 +1571,20 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
                         g[5], (double)g[0] / g[5], (double)g[1] / g[5], (double)g[2] / g[5], (double)g[3] / g[5], (double)g[4] / g[5], (double)g[6] / g[5], (double)g[7] / g[5]);
         }
 #endif
-        if (err == plo::ERR_TABLE) { cleanup(); continue; }                      // a pair table filled up: again with twice the slots
-        if (err) { cleanup(); return device_error((int)err); }
-        if (adds) KCHK(hipMemcpy(adds, d_adds, nrestarts * 4, hipMemcpyDeviceToHost));
-        if (muls) KCHK(hipMemcpy(muls, d_muls, nrestarts * 4, hipMemcpyDeviceToHost));
-        if (info) KCHK(hipMemcpy(info, d_info, nrestarts * 12, hipMemcpyDeviceToHost));
+        if (err == plo::ERR_TABLE) continue;                                     // a pair table filled up: again with twice the slots
+        if (err) return device_error((int)err);
+        if (adds) HIPCHK(hipMemcpy(adds, d_adds, nrestarts * 4, hipMemcpyDeviceToHost));
+        if (muls) HIPCHK(hipMemcpy(muls, d_muls, nrestarts * 4, hipMemcpyDeviceToHost));
+        if (info) HIPCHK(hipMemcpy(info, d_info, nrestarts * 12, hipMemcpyDeviceToHost));
         if (best) {
             unsigned long long w = 0;
-            KCHK(hipMemcpy(&w, d_best, 8, hipMemcpyDeviceToHost));
-            const uint64_t key = w >> 32, o = w & 0xFFFFFFFFull;
-            uint32_t a = 0, mu = 0;
-            if (cost_mode == PLO_COST_SUM_THEN_ADD) { a = (uint32_t)(key & 0xFFFFu); mu = (uint32_t)(key >> 16) - a; }
-            else if (cost_mode == PLO_COST_ADD_THEN_MUL) { a = (uint32_t)(key >> 16); mu = (uint32_t)(key & 0xFFFFu); }
-            else { a = (uint32_t)(key >> 16); mu = 0; }                             // sum only: reported in .adds, as plo_cse_chain_batch
-            best->adds = a; best->muls = mu; best->seed = seed0 + o;
+            HIPCHK(hipMemcpy(&w, d_best, 8, hipMemcpyDeviceToHost));
+            decode_key(w >> 32, cost_mode, 16u, &best->adds, &best->muls);          // (a sum-only key: the sum in .adds, as plo_cse_chain_batch)
+            best->seed = seed0 + (w & 0xFFFFFFFFull);
         }
-        cleanup();
-        st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        st->seconds = seconds_since(t0);
         return PLO_OK;
     }
-#undef KCHK
     return device_error(plo::ERR_TABLE);
 }
 
@@ -1576,20 +1594,10 @@ int plo_cse_chain_cost_many(plo_chain_t *ch, const uint64_t *seeds, uint64_t see
     if (!ch || !adds || !muls) return fail(PLO_E_ARG, "null argument");
     plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
     if (n == 0) return PLO_OK;
-    uint32_t *d_adds = nullptr, *d_muls = nullptr; uint64_t *d_seeds = nullptr;
-    HIPCHK(hipMalloc((void **)&d_adds, n * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&d_muls, n * sizeof(uint32_t)));
-    if (seeds) { HIPCHK(hipMalloc((void **)&d_seeds, n * sizeof(uint64_t))); HIPCHK(hipMemcpy(d_seeds, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice)); }
-    plo::WaveJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.adds = d_adds; J.muls = d_muls; J.best = nullptr; J.cost_mode = 0;
-    int rc = run_chain(ch, J, st);
-    if (rc == PLO_OK) {
-        hipError_t e1 = hipMemcpy(adds, d_adds, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        hipError_t e2 = hipMemcpy(muls, d_muls, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (e1 != hipSuccess || e2 != hipSuccess) rc = fail(PLO_E_HIP, "copy back failed");
-    }
-    (void)hipFree(d_adds); (void)hipFree(d_muls); if (d_seeds) (void)hipFree(d_seeds);
-    st->candidates = n;
-    return rc;
+    return cse_cost_many_run(n, seeds, adds, muls, nullptr, st, [&](uint32_t *d_adds, uint32_t *d_muls, uint64_t *d_seeds) {
+        plo::WaveJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.adds = d_adds; J.muls = d_muls; J.best = nullptr; J.cost_mode = 0;
+        return run_chain(ch, J, st);
+    });
 }
 
 int plo_cse_chain_search(plo_chain_t *ch, uint64_t seed0, uint64_t nseeds, int cost_mode, plo_best_t *out, plo_stats_t *st)
@@ -1599,22 +1607,15 @@ int plo_cse_chain_search(plo_chain_t *ch, uint64_t seed0, uint64_t nseeds, int c
     plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
     out->adds = out->muls = 0xFFFFFFFFu; out->seed = ~0ull;
     uint64_t bkey = ~0ull, bseed = ~0ull;
-    plo_plan *p0 = ch->st[0];
-    for (uint64_t done = 0; done < nseeds;) {
-        const uint64_t cnt = std::min<uint64_t>(0xFFFFFFFFull, nseeds - done);
-        HIPCHK(hipMemsetAsync(p0->d_best, 0xFF, sizeof(unsigned long long), g_stream));
-        plo::WaveJob J{}; J.seed0 = seed0 + done; J.ncand = cnt; J.best = p0->d_best; J.cost_mode = (uint32_t)cost_mode;
-        int rc = run_chain(ch, J, st);
-        if (rc != PLO_OK) return rc;
-        unsigned long long w = 0;
-        HIPCHK(hipMemcpy(&w, p0->d_best, sizeof w, hipMemcpyDeviceToHost));
-        const uint64_t key = w >> 32, sd = seed0 + done + (w & 0xFFFFFFFFull);
-        if (key < bkey || (key == bkey && sd < bseed)) { bkey = key; bseed = sd; }
-        done += cnt;
-    }
+    unsigned long long *d_best = ch->st[0]->d_best;
+    int rc = chunked_min(d_best, seed0, nseeds, 0xFFFFFFFFull, 32, &bkey, &bseed, [&](uint64_t s0, uint64_t cnt) {
+        plo::WaveJob J{}; J.seed0 = s0; J.ncand = cnt; J.best = d_best; J.cost_mode = (uint32_t)cost_mode;
+        return run_chain(ch, J, st);
+    });
+    if (rc != PLO_OK) return rc;
     if (nseeds) {
-        uint32_t a = 0, mu = 0; plo_stats_t s2{};
-        int rc = plo_cse_chain_cost_many(ch, &bseed, 0, 1, &a, &mu, &s2);
+        uint32_t a = 0, mu = 0; plo_stats_t s2{};                            // the winner's costs from the device, whatever the key holds
+        rc = plo_cse_chain_cost_many(ch, &bseed, 0, 1, &a, &mu, &s2);
         if (rc != PLO_OK) return rc;
         out->adds = a; out->muls = mu; out->seed = bseed;
     }
@@ -1827,15 +1828,6 @@ struct plo_tril_plan : AtomsPlan { plo::TrilPlan P{}; };
 struct plo_lin_plan : AtomsPlan { plo::LinPlan P{}; };
 
 namespace {
-// One timed launch of a search kernel (trilplacer, inplacer, orbiter) and its statistics
-template <class Plan, class Launch> int timed_launch(Plan *pl, uint64_t grid, uint64_t ncand, plo_stats_t *st, Launch launch) {
-    float ms = 0;
-    const int rc = timed(&ms, launch);
-    if (rc != PLO_OK) return rc;
-    if (st) { st->kernel_ms += ms; st->launches += 1; st->grid = (uint32_t)grid; st->lds_bytes = pl->lds_bytes; st->waves_per_wg = pl->waves_per_wg; st->algo_bytes = pl->algo_bytes; st->candidates += ncand; }
-    return PLO_OK;
-}
-
 // Launch of a trilplacer or inplacer job (one wavefront per candidate, plo::TrilJob): `kernel` is the plan's instantiation, `tool` names it in the error text
 template <class Plan, class Kernel> int atoms_launch(Plan *pl, Kernel kernel, const char *tool, plo::TrilJob J, plo_stats_t *st) {
     HIPCHK(hipMemsetAsync(pl->d_err, 0, sizeof(uint32_t), g_stream));
@@ -1859,15 +1851,12 @@ template <class Launch> int cost_many_run(const void *pl, const uint64_t *seeds,
     plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
     const auto t0 = std::chrono::steady_clock::now();
     if (n == 0) return PLO_OK;
-    uint32_t *d_out = nullptr; uint64_t *d_seeds = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, n * width * sizeof(uint32_t)));
-    if (seeds && (hipMalloc((void **)&d_seeds, n * 8) != hipSuccess || hipMemcpy(d_seeds, seeds, n * 8, hipMemcpyHostToDevice) != hipSuccess)) {
-        (void)hipFree(d_out); if (d_seeds) (void)hipFree(d_seeds); return fail(PLO_E_HIP, "seed upload");
-    }
-    int rc = launch(d_out, d_seeds, st);
+    DevBuf<uint32_t> d_out; DevBuf<uint64_t> d_seeds;
+    HIPCHK(hipMalloc((void **)&d_out.p, n * width * sizeof(uint32_t)));
+    if (seeds && (hipMalloc((void **)&d_seeds.p, n * 8) != hipSuccess || hipMemcpy(d_seeds, seeds, n * 8, hipMemcpyHostToDevice) != hipSuccess)) return fail(PLO_E_HIP, "seed upload");
+    int rc = launch(d_out.p, d_seeds.p, st);
     if (rc == PLO_OK && hipMemcpy(out, d_out, n * width * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back");
-    (void)hipFree(d_out); if (d_seeds) (void)hipFree(d_seeds);
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    st->seconds = seconds_since(t0);
     return rc;
 }
 
@@ -2282,9 +2271,9 @@ int plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const pl
     Q.off_cnt = off; off += round_up(2u * nrows + 2u, 16);
     Q.lds_per_wave = off;
     pl->algo_bytes = 10ull * nnz + 12ull * nrows;
-    pl->lds_bytes = 0; pl->action = action;
-    for (uint32_t w : {4u, 2u, 1u}) { const uint32_t b = Q.shared_bytes + w * Q.lds_per_wave; if (b <= g_lds_max && b <= 64u * 1024u) { pl->waves_per_wg = w; pl->lds_bytes = b; break; } }
-    if (!pl->lds_bytes) { delete pl; return fail(PLO_E_CAPACITY, "input does not fit LDS"); }
+    pl->action = action;
+    pl->waves_per_wg = pick_waves([&](uint32_t w) { return Q.shared_bytes + w * Q.lds_per_wave; }, false, std::min<size_t>(g_lds_max, 64u * 1024u), &pl->lds_bytes);
+    if (!pl->waves_per_wg) { delete pl; return fail(PLO_E_CAPACITY, "input does not fit LDS"); }
     pl->blocks_per_cu = blocks_per_cu(pl->waves_per_wg, pl->lds_bytes);
     pl->grid_max = (uint32_t)g_cus * pl->blocks_per_cu;
     // the device image: values, scales, row pointers, positions
@@ -2428,9 +2417,8 @@ int plo_dep_plan_create_q(const plo_qcsr_t *M, const int64_t *cnum, const int64_
     const uint32_t cap = (uint32_t)std::min<size_t>(g_lds_max, 64u * 1024u);
     pl->m_in_lds = (uint64_t)m_bytes + c_bytes + 4u * Q.lds_per_wave <= cap;
     Q.off_coef = pl->m_in_lds ? m_bytes : 0u; Q.off_wave = Q.off_coef + c_bytes;
-    pl->lds_bytes = 0;
-    for (uint32_t w : {4u, 2u, 1u}) { const uint64_t b = (uint64_t)Q.off_wave + (uint64_t)w * Q.lds_per_wave; if (b <= cap) { pl->waves_per_wg = w; pl->lds_bytes = (uint32_t)b; break; } }
-    if (!pl->lds_bytes) { delete pl; return fail(PLO_E_CAPACITY, "the vectors of this level do not fit LDS"); }
+    pl->waves_per_wg = pick_waves([&](uint32_t w) { return (uint64_t)Q.off_wave + (uint64_t)w * Q.lds_per_wave; }, false, cap, &pl->lds_bytes);
+    if (!pl->waves_per_wg) { delete pl; return fail(PLO_E_CAPACITY, "the vectors of this level do not fit LDS"); }
     pl->blocks_per_cu = blocks_per_cu(pl->waves_per_wg, pl->lds_bytes);
     pl->grid_max = (uint32_t)g_cus * pl->blocks_per_cu;
     pl->algo_bytes = 4ull * m * ld + 4ull * ncoef;
@@ -2471,11 +2459,10 @@ int plo_dep_search(plo_dep_plan_t *pl, uint32_t row0, uint32_t row1, plo_dep_hit
     const uint64_t ntasks = toff[nrows];
     if (pl->level < 2u || ntasks == 0) return PLO_OK;
     const uint64_t dcap = std::min<uint64_t>(cap, PLO_DEP_MAX_HITS);
-    uint64_t *d_toff = nullptr; plo_dep_hit_t *d_hits = nullptr;
-    auto release = [&] { if (d_toff) (void)hipFree(d_toff); if (d_hits) (void)hipFree(d_hits); };
-    if (hipMalloc((void **)&d_toff, 8ull * (nrows + 1u)) != hipSuccess || hipMemcpy(d_toff, toff.data(), 8ull * (nrows + 1u), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc((void **)&d_hits, std::max<uint64_t>(1, dcap) * sizeof(plo_dep_hit_t)) != hipSuccess ||
-        hipMemsetAsync(pl->d_ctr, 0, 16, g_stream) != hipSuccess) { release(); return fail(PLO_E_HIP, "device buffers of the dependency search"); }
+    DevBuf<uint64_t> d_toff; DevBuf<plo_dep_hit_t> d_hits;
+    if (hipMalloc((void **)&d_toff.p, 8ull * (nrows + 1u)) != hipSuccess || hipMemcpy(d_toff, toff.data(), 8ull * (nrows + 1u), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc((void **)&d_hits.p, std::max<uint64_t>(1, dcap) * sizeof(plo_dep_hit_t)) != hipSuccess ||
+        hipMemsetAsync(pl->d_ctr, 0, 16, g_stream) != hipSuccess) return fail(PLO_E_HIP, "device buffers of the dependency search");
     plo::DepJob J{}; J.row0 = row0; J.nrows = nrows; J.toff = d_toff; J.ntasks = ntasks; J.next = pl->d_ctr; J.count = pl->d_ctr + 1; J.hits = d_hits; J.cap = dcap;
     const uint64_t need = (ntasks + pl->waves_per_wg - 1) / pl->waves_per_wg;
     const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(pl->grid_max, need));
@@ -2493,7 +2480,6 @@ int plo_dep_search(plo_dep_plan_t *pl, uint32_t row0, uint32_t row1, plo_dep_hit
         else if (found > cap) rc = fail(PLO_E_CAPACITY, std::to_string(found) + " hits for a buffer of " + std::to_string(cap));
         else std::sort(hits, hits + found, dep_before);
     }
-    release();
     st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return rc;
 }

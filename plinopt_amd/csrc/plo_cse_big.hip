@@ -97,7 +97,33 @@ struct BigJob {
     uint64_t seed0; const uint64_t *seeds; uint64_t ncand;
     uint32_t *adds, *muls; unsigned long long *best; uint32_t cost_mode; uint32_t *err;
     unsigned long long *next;     // work counter: candidates are handed out dynamically
-    uint32_t *stats;              // optional: [0]=steps of last candidate, [1]=full scans, [2]=level rebuilds
+    uint32_t *stats;              // optional: BS_COUNT words, indexed by BigStat
+};
+
+// The words of BigJob::stats.  LAST: of the candidate that finished last; SUM: added up over the candidates of the launch
+// (the host clears the words before every launch).  Times are in microseconds.
+enum BigStat {
+    BS_LAST_STEPS = 0, BS_LAST_FULLSCANS = 1, BS_LAST_REBUILDS = 2,
+    BS_LAST_PHASE_US = 4,           // 8 words: level, select, rows, sweep 1, flush 1, sweep 2, flush 2, tail
+    BS_LAST_LOAD_US = 12,           // image load alone
+    BS_SUM_MERGE_GROUPS = 13,       // the merge: groups of partitions summed
+    BS_SUM_MERGE_LOOP = 14,         // the merge: records loaded behind the prefetch
+    BS_PROF_SWEEP1_US = 16, BS_PROF_SWEEP2_US = 20, BS_PROF_STEPS = 24,     // PLO_BIG_PROFILE, 4 words each: by rows per step (>=256, 64.., 16.., <16)
+    BS_PROF_FALLBACK1 = 28, BS_PROF_FALLBACK2 = 29, BS_PROF_FLUSHED1 = 30, BS_PROF_FLUSHED2 = 31,
+    BS_SUM_STEPS = 32, BS_SUM_FULLSCANS = 33, BS_SUM_REBUILDS = 34, BS_SUM_BISECTIONS = 35, BS_SUM_SPILLED = 36, BS_SUM_LISTOVER = 37,
+    BS_SUM_CANDIDATES = 38,         // (these seven, in this order, are plo_cse_plan_hbm_counters' first seven)
+    BS_SUM_FORCED_MERGES = 39,      // merges forced by log / hot pressure
+    BS_SUM_HOTOPS = 40,             // hot-table updates
+    BS_SUM_LOG_LO = 41, BS_SUM_LOG_HI = 42,     // log records, 64 bits
+    BS_ERR_SITE = 43,               // maximum of the sites that reported an error (sh.derr)
+    BS_LAST_MERGE_US = 44,          // 4 words: hot->log, partition pass, sum + write back, window
+    BS_LAST_MERGE_SUM_US = 48,      // 4 words: sum (loads + table), scan + write back, (a word the printer skips), clear + bounds
+    BS_LAST_MERGE_GROUPS = 52,
+    BS_SUM_EXTRA_WINDOWS = 53, BS_SUM_ROWS_SEARCHED = 54,
+    BS_LAST_CSE_US = 55,            // image load + CSE phase
+    BS_LAST_PGEN_US = 56,           // ProgramGen
+    BS_LAST_PGEN_PHASE_US = 57,     // 7 words: table fill + flags, expand + A1, A2, A3 + B + count, Triangle set-up, Triangle, D
+    BS_COUNT = 64
 };
 
 enum { BERR_TABLE = 11, BERR_FREQ = 12, BERR_COLS = 13, BERR_DM = 14, BERR_HL = 15, BERR_MULT = 16, BERR_SEL = 17, BERR_PGEN = 18 };
@@ -2138,11 +2164,35 @@ template <int MODE, bool DEFER, bool IDK = false> __global__ __launch_bounds__(P
             const uint32_t a = (uint32_t)(res >> 32), mu_ = (uint32_t)res;
             if (J.adds) J.adds[c] = a;
             if (J.muls) J.muls[c] = mu_;
-            if (J.stats) { atomicAdd(&J.stats[32], sh.steps); atomicAdd(&J.stats[33], sh.fullscans); atomicAdd(&J.stats[34], sh.rebuilds); atomicAdd(&J.stats[35], sh.nbisect); atomicAdd(&J.stats[36], sh.spilltot); atomicAdd(&J.stats[37], sh.listover); atomicAdd(&J.stats[38], 1u); atomicAdd(&J.stats[39], sh.nforced); atomicMax(&J.stats[43], sh.derr); for (int q = 0; q < 4; ++q) { J.stats[44 + q] = (uint32_t)(sh.tmg[q] / 100ull); J.stats[48 + q] = (uint32_t)(sh.tmb[q] / 100ull); } J.stats[52] = sh.ngrp; atomicAdd(&J.stats[13], sh.ngrp); atomicAdd(&J.stats[14], sh.nloop); J.stats[55] = (uint32_t)((tk1 - tk0) / 100ull); J.stats[56] = (uint32_t)((tk2 - tk1) / 100ull); J.stats[12] = (uint32_t)(sh.tld / 100ull); for (int q = 0; q < 7; ++q) J.stats[57 + q] = ok ? (uint32_t)(sh.tpg[q] / 100ull) : 0u; atomicAdd(&J.stats[53], sh.nwin); atomicAdd(&J.stats[54], sh.nsearched); atomicAdd(&J.stats[40], sh.hotops); { const uint32_t lo_ = atomicAdd(&J.stats[41], sh.logtot_lo); if (lo_ + sh.logtot_lo < lo_) atomicAdd(&J.stats[42], 1u); atomicAdd(&J.stats[42], sh.logtot_hi); }
-                J.stats[0] = sh.steps; J.stats[1] = sh.fullscans; J.stats[2] = sh.rebuilds; for (int q = 0; q < 8; ++q) J.stats[4 + q] = (uint32_t)(sh.tph[q] / 100ull);
+            if (J.stats) {
+                atomicAdd(&J.stats[BS_SUM_STEPS], sh.steps);
+                atomicAdd(&J.stats[BS_SUM_FULLSCANS], sh.fullscans);
+                atomicAdd(&J.stats[BS_SUM_REBUILDS], sh.rebuilds);
+                atomicAdd(&J.stats[BS_SUM_BISECTIONS], sh.nbisect);
+                atomicAdd(&J.stats[BS_SUM_SPILLED], sh.spilltot);
+                atomicAdd(&J.stats[BS_SUM_LISTOVER], sh.listover);
+                atomicAdd(&J.stats[BS_SUM_CANDIDATES], 1u);
+                atomicAdd(&J.stats[BS_SUM_FORCED_MERGES], sh.nforced);
+                atomicMax(&J.stats[BS_ERR_SITE], sh.derr);
+                for (int q = 0; q < 4; ++q) { J.stats[BS_LAST_MERGE_US + q] = (uint32_t)(sh.tmg[q] / 100ull); J.stats[BS_LAST_MERGE_SUM_US + q] = (uint32_t)(sh.tmb[q] / 100ull); }
+                J.stats[BS_LAST_MERGE_GROUPS] = sh.ngrp;
+                atomicAdd(&J.stats[BS_SUM_MERGE_GROUPS], sh.ngrp);
+                atomicAdd(&J.stats[BS_SUM_MERGE_LOOP], sh.nloop);
+                J.stats[BS_LAST_CSE_US] = (uint32_t)((tk1 - tk0) / 100ull);
+                J.stats[BS_LAST_PGEN_US] = (uint32_t)((tk2 - tk1) / 100ull);
+                J.stats[BS_LAST_LOAD_US] = (uint32_t)(sh.tld / 100ull);
+                for (int q = 0; q < 7; ++q) J.stats[BS_LAST_PGEN_PHASE_US + q] = ok ? (uint32_t)(sh.tpg[q] / 100ull) : 0u;
+                atomicAdd(&J.stats[BS_SUM_EXTRA_WINDOWS], sh.nwin);
+                atomicAdd(&J.stats[BS_SUM_ROWS_SEARCHED], sh.nsearched);
+                atomicAdd(&J.stats[BS_SUM_HOTOPS], sh.hotops);
+                { const uint32_t lo_ = atomicAdd(&J.stats[BS_SUM_LOG_LO], sh.logtot_lo); if (lo_ + sh.logtot_lo < lo_) atomicAdd(&J.stats[BS_SUM_LOG_HI], 1u); atomicAdd(&J.stats[BS_SUM_LOG_HI], sh.logtot_hi); }
+                J.stats[BS_LAST_STEPS] = sh.steps;
+                J.stats[BS_LAST_FULLSCANS] = sh.fullscans;
+                J.stats[BS_LAST_REBUILDS] = sh.rebuilds;
+                for (int q = 0; q < 8; ++q) J.stats[BS_LAST_PHASE_US + q] = (uint32_t)(sh.tph[q] / 100ull);
 #ifdef PLO_BIG_PROFILE
-                for (int q = 0; q < 4; ++q) { J.stats[16 + q] = (uint32_t)(sh.tb1[q] / 100ull); J.stats[20 + q] = (uint32_t)(sh.tb2[q] / 100ull); J.stats[24 + q] = sh.nb[q]; }
-                J.stats[28] = sh.fb1; J.stats[29] = sh.fb2; J.stats[30] = sh.fl1; J.stats[31] = sh.fl2;
+                for (int q = 0; q < 4; ++q) { J.stats[BS_PROF_SWEEP1_US + q] = (uint32_t)(sh.tb1[q] / 100ull); J.stats[BS_PROF_SWEEP2_US + q] = (uint32_t)(sh.tb2[q] / 100ull); J.stats[BS_PROF_STEPS + q] = sh.nb[q]; }
+                J.stats[BS_PROF_FALLBACK1] = sh.fb1; J.stats[BS_PROF_FALLBACK2] = sh.fb2; J.stats[BS_PROF_FLUSHED1] = sh.fl1; J.stats[BS_PROF_FLUSHED2] = sh.fl2;
                 for (int q = 0; q < 16; ++q) atomicAdd(&g_prof[q], sh.pw[q]);
                 for (int c_ = 0; c_ < 4; ++c_) for (int q = 0; q < 8; ++q) atomicAdd(&g_prof2[c_ * 8 + q], sh.tpc[c_][q]);
                 atomicAdd(&g_prof2[32], 1ull);
