@@ -106,6 +106,11 @@ int plo_cse_plan_hbm_counters(const plo_plan_t *plan, uint32_t out[8]);
  * (the length of the shorter row list of a step's two columns, summed over steps: reference include/plinopt_optimize.inl:92-94 walks
  * every row). */
 int plo_cse_plan_hbm_counters_ex(const plo_plan_t *plan, uint32_t *out, uint32_t n);
+/* Host only (no device is touched): the workspace slice the HBM-resident family lays out for one candidate of a matrix with `rows` rows,
+ * `nnz` entries, at most `ncmax` columns (created ones included) and an eager pair table of 2^table_bits slots (10..30).
+ * out[0] = bytes of the front region (every array but the table, which comes last: the kernels address the front region with 32-bit
+ * offsets), out[1] = bytes of the slice, out[2] = 1 when the front region passes 4 GiB and the plan takes the kernels with 64-bit offsets. */
+int plo_cse_hbm_workspace_layout(uint32_t rows, uint32_t nnz, uint32_t ncmax, uint32_t table_bits, uint64_t out[3]);
 int plo_cse_plan_destroy(plo_plan_t *plan);
 
 /* Replaces the body of `#pragma omp parallel for` in CSEOptimiser,

@@ -374,17 +374,19 @@ template <class T> int upload(plo_plan *pl, const std::vector<T> &v, const T **d
     return PLO_OK;
 }
 
-const void *big_kernel_fn(const plo::BigPlan &B)
+template <bool WIDE> const void *big_kernel_fn_w(const plo::BigPlan &B)
 {
-    if (B.idk) return B.defer ? (const void *)plo::cse_big_kernel<2, true, true> : (const void *)plo::cse_big_kernel<2, false, true>;
-    if (B.defer) return B.mode == 2u ? (const void *)plo::cse_big_kernel<2, true> : B.mode == 1u ? (const void *)plo::cse_big_kernel<1, true> : (const void *)plo::cse_big_kernel<0, true>;
-    return B.mode == 2u ? (const void *)plo::cse_big_kernel<2, false> : B.mode == 1u ? (const void *)plo::cse_big_kernel<1, false> : (const void *)plo::cse_big_kernel<0, false>;
+    if (B.idk) return B.defer ? (const void *)plo::cse_big_kernel<2, true, true, WIDE> : (const void *)plo::cse_big_kernel<2, false, true, WIDE>;
+    if (B.defer) return B.mode == 2u ? (const void *)plo::cse_big_kernel<2, true, false, WIDE> : B.mode == 1u ? (const void *)plo::cse_big_kernel<1, true, false, WIDE> : (const void *)plo::cse_big_kernel<0, true, false, WIDE>;
+    return B.mode == 2u ? (const void *)plo::cse_big_kernel<2, false, false, WIDE> : B.mode == 1u ? (const void *)plo::cse_big_kernel<1, false, false, WIDE> : (const void *)plo::cse_big_kernel<0, false, false, WIDE>;
 }
+// (BigPlan::wide: the kernels that address the workspace slice with 64-bit offsets, layout_big_workspace)
+const void *big_kernel_fn(const plo::BigPlan &B) { return B.wide ? big_kernel_fn_w<true>(B) : big_kernel_fn_w<false>(B); }
 
-// The PLO_BIG_* knobs of a plan (tests and experiments).  The first six are flags; the clamps of the others are where they are used.
+// The PLO_BIG_* knobs of a plan (tests and experiments).  The first seven are flags; the clamps of the others are where they are used.
 struct BigPlanKnobs {
     std::optional<long> vt_global = env_knob("PLO_BIG_VT_GLOBAL"), norid = env_knob("PLO_BIG_NORID"), idkeys = env_knob("PLO_BIG_IDKEYS"),
-                        noprune = env_knob("PLO_BIG_NOPRUNE"), eager = env_knob("PLO_BIG_EAGER"), nodual = env_knob("PLO_BIG_NODUAL");
+                        noprune = env_knob("PLO_BIG_NOPRUNE"), eager = env_knob("PLO_BIG_EAGER"), nodual = env_knob("PLO_BIG_NODUAL"), wide = env_knob("PLO_BIG_WIDE");
     std::optional<long> fwin = env_knob("PLO_BIG_FWIN"), hbits = env_knob("PLO_BIG_HBITS"), logtrig = env_knob("PLO_BIG_LOGTRIG"), hwin = env_knob("PLO_BIG_HWIN"),
                         hotbits = env_knob("PLO_BIG_HOTBITS"), lgrp = env_knob("PLO_BIG_LGRP"), aggbits = env_knob("PLO_BIG_AGGBITS"), selcap = env_knob("PLO_BIG_SELCAP");
 };
@@ -436,20 +438,20 @@ void size_big_deferred(plo_plan *pl, const BigPlanKnobs &K, const BigTriples &T,
     for (size_t k = 0; k < keys.size(); ++k) { const uint32_t q = part(keys[k]); st0[(size_t)q * capp + fill[q]++] = (keys[k] << PLO_GVB) | 0x8000ull | cnts[k]; }   // a record: key | insert flag | frequency
 }
 
-// workspace layout of one candidate (the eager table has 2^hbits slots; with deferred updates hbits becomes ProgramGen's)
-void layout_big_workspace(plo::BigPlan &B)
+// Workspace layout of one candidate (the eager table has 2^hbits slots; with deferred updates hbits becomes ProgramGen's).  The kernels
+// address everything but the large region -- the eager table, which the capacity refits multiply by up to 256, or the deferred store --
+// as the slice's base plus a 32-bit byte offset (plo::WsArr), so that region comes LAST with a pointer of its own and everything else
+// lies in front of it.  The front region is 36 bytes per entry and more: at the kernels' limits (32766 rows of 8192 entries) it can pass
+// 4 GiB, and such a plan -- or any plan, with the test knob `force_wide` -- takes the kernels with 64-bit offsets (B.wide).
+void layout_big_workspace(plo::BigPlan &B, bool force_wide = false)
 {
     const uint64_t nnz = B.nnz, m = B.m, NC = B.NCmax, multcap = B.multcap;
     uint64_t off = 0;
     auto take = [&](uint64_t bytes) { uint64_t o = off; off = (off + bytes + 255) & ~255ull; return o; };
     if (B.defer) {
-        // the table region only serves ProgramGen's (column, |v|) multiset: it shares the partitions' logs, idle by then
-        uint64_t pg = 1024; while (pg < 2ull * nnz + 2ull * multcap + 64ull) pg <<= 1;
-        B.hbits = ceil_log2((uint32_t)pg);
-        B.o_store = take(std::max<uint64_t>(((uint64_t)(B.capp + B.plcap) << B.pbits) * 8, pg * 8)); B.o_tab = B.o_store; B.o_plog = 0;
         B.o_pcount = take(4ull << B.pbits); B.o_ptail = take(4ull << B.pbits);
         B.o_log = take((uint64_t)B.logcap * 8); B.o_hot = take(8ull << B.hotbits_max);
-    } else B.o_tab = take(8ull << B.hbits);
+    }
     B.o_ent = take((nnz + 128) * 4); B.o_col = take(nnz * 4); B.o_val = take(nnz * 4); B.o_inv = take(nnz * 4);
     B.o_len = take(m * 4); B.o_ucount = take(NC * 4); B.o_cntM = take(NC * 4);
     B.o_dm = take((uint64_t)B.dmcap * 8); B.o_hl = take((uint64_t)B.hlcap * 16); B.o_aff = take(m * 32);
@@ -457,6 +459,13 @@ void layout_big_workspace(plo::BigPlan &B)
     B.o_tl = take((nnz + 64) * 4); B.o_clen = take(NC * 4); B.o_keep = take((m + 64) * 4);
     B.o_multc = take(multcap * 4); B.o_multv = take(multcap * 4);
     B.o_tcnt = take(NC * 4); B.o_tptr2 = take((NC + 2) * 4); B.o_tlist = take((nnz + 64) * 4); B.o_cols2 = take(NC * 4); B.o_spill = take((nnz + 64) * 8);
+    B.wide = (force_wide || off > 0xFFFFFFFFull) ? 1u : 0u;           // `off` = the front region's bytes
+    if (B.defer) {
+        // the table region only serves ProgramGen's (column, |v|) multiset: it shares the partitions' logs, idle by then
+        uint64_t pg = 1024; while (pg < 2ull * nnz + 2ull * multcap + 64ull) pg <<= 1;
+        B.hbits = ceil_log2((uint32_t)pg);
+        B.o_store = take(std::max<uint64_t>(((uint64_t)(B.capp + B.plcap) << B.pbits) * 8, pg * 8)); B.o_tab = B.o_store; B.o_plog = 0;
+    } else B.o_tab = take(8ull << B.hbits);
     B.ws_stride = off;
 }
 
@@ -620,7 +629,7 @@ int build_big_plan(plo_plan *pl)
         for (uint32_t i = 2; i < p; ++i) it[i] = (uint32_t)((uint64_t)(p - p / i) * it[p % i] % p);
         if ((rc = upload(pl, it, &B.invtab))) return rc;
     }
-    layout_big_workspace(B);
+    layout_big_workspace(B, K.wide.has_value());
     if ((rc = size_big_lds(pl, K))) return rc;
     HIPCHK(hipFuncSetAttribute(big_kernel_fn(B), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->big_lds));
     if (!pl->d_err) HIPCHK(hipMalloc((void **)&pl->d_err, sizeof(uint32_t)));
@@ -910,6 +919,18 @@ int plo_cse_plan_hbm_counters(const plo_plan_t *pl, uint32_t out[8])
     HIPCHK(hipMemcpy(hs, pl->d_stats, sizeof hs, hipMemcpyDeviceToHost));
     for (int k = 0; k < 7; ++k) out[k] = hs[plo::BS_SUM_STEPS + k];      // ... BS_SUM_CANDIDATES
     out[7] = pl->big_refits;
+    return PLO_OK;
+}
+
+// host only, no device: the eager layout of a matrix of the given size (multcap at its bound NCmax, list capacities as build_big_plan sets them)
+int plo_cse_hbm_workspace_layout(uint32_t rows, uint32_t nnz, uint32_t ncmax, uint32_t table_bits, uint64_t out[3])
+{
+    if (!out || table_bits < 10u || table_bits > 30u) return PLO_E_ARG;
+    plo::BigPlan B{};
+    B.m = rows; B.nnz = nnz; B.NCmax = ncmax; B.multcap = ncmax; B.hbits = table_bits; B.defer = 0u;
+    B.dmcap = (uint32_t)std::min<uint64_t>(1u << 20, 1ull << table_bits); B.hlcap = (uint32_t)std::min<uint64_t>(1u << 18, 1ull << table_bits);
+    layout_big_workspace(B);
+    out[0] = B.o_tab; out[1] = B.ws_stride; out[2] = B.wide;
     return PLO_OK;
 }
 

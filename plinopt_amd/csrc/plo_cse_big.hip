@@ -50,15 +50,17 @@
 //              and fences on its workspace are WORKGROUP scope, so the XCD's L2
 //              serves them (agent scope = memory side of the fabric on a part whose
 //              XCD L2s are not coherent with each other: 2.3x slower).
+//   addressing a candidate's arrays are its workspace slice's base plus 32-bit byte offsets (WsArr): one
+//              scalar pair for all of them; only the large region (eager table / deferred store), last
+//              in the slice, has a pointer.  The plan's words are read from the kernel-argument segment
+//              at the head of the phase that uses them (plan_word), not held from the kernel's entry.
 // The work per candidate is ~2.5e8 pair retirements + 1.2e8 pair insertions (1.5e7 table
-// updates after aggregation).  Round 4 state: 5.8e7 L2 requests and 1.85 GB of HBM traffic per
-// candidate (30x the algorithmic bytes), and NOT bound by the memory system: a candidate alone
-// on the chip takes 0.44 s, 512 together 0.63 s each -- the bound is the dependent chain of one
-// workgroup per candidate, two per CU (round 2's "random-access request rate"
-// diagnosis was retracted in round 3).
+// updates after aggregation).  Where the time of a candidate goes, what bounds it and every
+// measurement behind that: DESIGN.md 2.2 (figures quoted here went stale twice).
 // ===========================================================================
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace plo {
 
@@ -90,6 +92,7 @@ struct BigPlan {
     uint32_t fwin;                        // entries per window of the flat sweep (2048 = 32 trips: the marks of a window are 32 words per wave; a test knob makes it smaller)
     const uint64_t *st0; const uint32_t *pcount0;     // store image: 2^pbits partitions of capp entries (key48<<16 | count16), entries per partition
     uint64_t o_store, o_pcount, o_ptail, o_log, o_plog, o_hot;
+    uint32_t wide;                        // the slice's front region (everything but the table / store, which comes last) passes 4 GiB: kernels with 64-bit offsets
     uint32_t kb, idk;                     // idk: the ratio field of a pair key holds the ratio's identifier (kb bits), not the residue (cse_big_kernel<2, ., true>)
 };
 
@@ -142,6 +145,33 @@ template <class T> __device__ __forceinline__ T wg_cas(T *p, T expected, T desir
     __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, PLO_BIG_SCOPE);
     return expected;
 }
+// (the offset as a scalar of its own: the plan's words arrive by kernel-argument loads of up to 16 words, and a word used straight out of
+// such a tuple keeps all 16 alive -- and spilled and reloaded together -- for as long as it lives)
+template <class O> __device__ __forceinline__ O ws_off(uint64_t o) { O x = (O)o; asm("" : "+s"(x)); return x; }
+template <class T> __device__ __forceinline__ T sreg(T x) { asm("" : "+s"(x)); return x; }      // (any plan word, the same way)
+// A word of the plan read again from the kernel-argument segment, where it is used (the plan is the kernel's first argument).  The step
+// loop reads its plan words this way at the head of the phase that needs them: a scalar load from the constant cache costs the vector
+// pipe nothing, while a word captured at the kernel's entry occupies a scalar register -- or a spill lane and a v_readlane per use --
+// through every phase that never looks at it.  (The pointer is opaque so that the load stays where it is written.)  Offset 0 of the
+// segment is the plan: see the invariant at cse_big_kernel.
+template <class T> __device__ __forceinline__ T plan_word(uint32_t off) {
+    typedef const __attribute__((address_space(4))) uint8_t *kptr;
+    kptr k = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return *(const __attribute__((address_space(4))) T *)(k + off);
+}
+#define PW(f_) plan_word<decltype(BigPlan::f_)>((uint32_t)__builtin_offsetof(BigPlan, f_))
+// An array in a candidate's workspace slice, held as the slice's base plus a BYTE OFFSET instead of a pointer of its own.  The base is one
+// scalar pair shared by every array; with O = uint32_t (the default kernels: everything in front of the large table / store region lies
+// below 4 GiB, layout_big_workspace) an offset is ONE scalar and an access is `global_* v, voff, s[base]` with voff = offset + (index << 2|3),
+// the single address instruction a pointer costs too.  O = uint64_t: the WIDE kernels for slices whose front region passes 4 GiB.
+// Indexing, `arr + k` and casts to a pointer work as they do on a pointer, so the code that uses an array does not care.
+template <class T, class O> struct WsArr {
+    uint8_t *ws; O off;
+    __device__ __forceinline__ T &operator[](uint32_t i) const { return *(T *)(ws + (O)(off + (O)i * (O)sizeof(T))); }
+    __device__ __forceinline__ WsArr operator+(uint32_t i) const { return WsArr{ws, (O)(off + (O)i * (O)sizeof(T))}; }
+    template <class U> __device__ __forceinline__ explicit operator U *() const { return (U *)(ws + off); }
+};
 __device__ __forceinline__ uint64_t gload64(const uint64_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, PLO_BIG_SCOPE); }
 __device__ __forceinline__ void gstore64(uint64_t *p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, PLO_BIG_SCOPE); }
 __device__ __forceinline__ uint32_t gload32(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, PLO_BIG_SCOPE); }
@@ -175,7 +205,7 @@ __device__ __forceinline__ uint32_t babs(uint32_t e, uint32_t p) { uint32_t a = 
 // 2^22 dependent memory round trips per key (seconds each: the launch looked hung).  Lookups end at the first empty slot.
 #define PLO_GPROBE_INS 16384u
 // frequency[key] -= 1; returns the frequency before (0 = key not found: corruption)
-__device__ __forceinline__ uint32_t gtab_dec(uint64_t *tab, uint64_t key, uint32_t hbits) {
+template <class TAB> __device__ __forceinline__ uint32_t gtab_dec(TAB tab, uint64_t key, uint32_t hbits) {
     const uint32_t mask = (1u << hbits) - 1u;
     uint32_t s = ghash(key, hbits);
     for (uint32_t pr = 0; pr < (1u << 22); ++pr) {
@@ -187,7 +217,7 @@ __device__ __forceinline__ uint32_t gtab_dec(uint64_t *tab, uint64_t key, uint32
     return 0u;
 }
 // frequency[key] += 1 (claims an empty or dead slot); returns the new frequency (0 = table full)
-__device__ __forceinline__ uint32_t gtab_inc(uint64_t *tab, uint64_t key, uint32_t hbits) {
+template <class TAB> __device__ __forceinline__ uint32_t gtab_inc(TAB tab, uint64_t key, uint32_t hbits) {
     const uint32_t mask = (1u << hbits) - 1u;
     uint32_t s = ghash(key, hbits);
     for (uint32_t pr = 0; pr < PLO_GPROBE_INS; ++pr) {
@@ -202,7 +232,7 @@ __device__ __forceinline__ uint32_t gtab_inc(uint64_t *tab, uint64_t key, uint32
     }
     return 0u;
 }
-__device__ __forceinline__ uint32_t gtab_find(const uint64_t *tab, uint64_t key, uint32_t hbits) {
+template <class TAB> __device__ __forceinline__ uint32_t gtab_find(TAB tab, uint64_t key, uint32_t hbits) {
     const uint32_t mask = (1u << hbits) - 1u;
     uint32_t s = ghash(key, hbits);
     for (uint32_t pr = 0; pr < (1u << 22); ++pr) {
@@ -214,7 +244,7 @@ __device__ __forceinline__ uint32_t gtab_find(const uint64_t *tab, uint64_t key,
     return 0u;
 }
 // value add with claim of EMPTY slots only (ProgramGen multiset; no dead slots there)
-__device__ __forceinline__ bool gtab_add(uint64_t *tab, uint64_t key, uint32_t incv, uint32_t hbits) {
+template <class TAB> __device__ __forceinline__ bool gtab_add(TAB tab, uint64_t key, uint32_t incv, uint32_t hbits) {
     const uint32_t mask = (1u << hbits) - 1u;
     uint32_t s = ghash(key, hbits);
     for (uint32_t pr = 0; pr < PLO_GPROBE_INS; ++pr) {
@@ -231,7 +261,7 @@ __device__ __forceinline__ bool gtab_add(uint64_t *tab, uint64_t key, uint32_t i
 }
 
 // set a flag bit on the key's value (insert the key if absent); idempotent, unlike an add
-__device__ __forceinline__ bool gtab_flag(uint64_t *tab, uint64_t key, uint32_t flag, uint32_t hbits) {
+template <class TAB> __device__ __forceinline__ bool gtab_flag(TAB tab, uint64_t key, uint32_t flag, uint32_t hbits) {
     const uint32_t mask = (1u << hbits) - 1u;
     uint32_t s = ghash(key, hbits);
     for (uint32_t pr = 0; pr < PLO_GPROBE_INS; ++pr) {
@@ -248,7 +278,7 @@ __device__ __forceinline__ bool gtab_flag(uint64_t *tab, uint64_t key, uint32_t 
 }
 
 // frequency[key] -= d; returns the frequency before (0 = key not found)
-__device__ __forceinline__ uint32_t gtab_subn(uint64_t *tab, uint64_t key, uint32_t d, uint32_t hbits) {
+template <class TAB> __device__ __forceinline__ uint32_t gtab_subn(TAB tab, uint64_t key, uint32_t d, uint32_t hbits) {
     const uint32_t mask = (1u << hbits) - 1u;
     uint32_t s = ghash(key, hbits);
     for (uint32_t pr = 0; pr < (1u << 22); ++pr) {
@@ -269,7 +299,7 @@ __device__ __forceinline__ uint32_t gtab_subn(uint64_t *tab, uint64_t key, uint3
 #define PLO_FLU 2u       /* aggregated entries per thread and trip of the flush */
 #endif
 // frequency[key] += d (claims the first empty or dead slot in probe order); returns the frequency before, 0xFFFFFFFF = table full
-__device__ __forceinline__ uint32_t gtab_addn(uint64_t *tab, uint64_t key, uint32_t d, uint32_t hbits) {
+template <class TAB> __device__ __forceinline__ uint32_t gtab_addn(TAB tab, uint64_t key, uint32_t d, uint32_t hbits) {
     const uint32_t mask = (1u << hbits) - 1u;
     uint32_t s = ghash(key, hbits);
     for (uint32_t pr = 0; pr < PLO_GPROBE_INS; pr += PLO_GWIN) {
@@ -295,7 +325,7 @@ __device__ __forceinline__ uint32_t gtab_addn(uint64_t *tab, uint64_t key, uint3
 
 // N insertions of one thread in lock step (second flush pass: PLO_FLU entries per trip; the table is far larger than the
 // caches, every probe is a memory round trip, and only independent ones overlap).  live[q] = false: key q is skipped.
-template <int N> __device__ __forceinline__ void gtab_addnN(uint64_t *tab, const uint64_t (&key)[N], const uint32_t (&d)[N], const bool (&live)[N], uint32_t hbits, uint32_t (&o)[N]) {
+template <int N, class TAB> __device__ __forceinline__ void gtab_addnN(TAB tab, const uint64_t (&key)[N], const uint32_t (&d)[N], const bool (&live)[N], uint32_t hbits, uint32_t (&o)[N]) {
     const uint32_t mask = (1u << hbits) - 1u;
     uint32_t s[N]; bool pend[N];
 #pragma unroll
@@ -424,10 +454,11 @@ __device__ __forceinline__ bool agg_add_rid(uint32_t *aggk, uint32_t *aggc32, ui
 
 // The same probe loop for the staged sweep (mode 2 with deferred updates): a claimed slot sets its bit in a bitmap with a
 // fire-and-forget atomic -- no counter with a returned value, no slot list (two LDS round trips less on the claim path).
-__device__ __forceinline__ bool agg_add_rid_bm(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, uint32_t *bm, uint32_t *iters = nullptr) {
+// hshift = 32 - aggbits: the sweep hands it over in a vector register (below).
+__device__ __forceinline__ bool agg_add_rid_bm(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, uint32_t *bm, uint32_t hshift, uint32_t *iters = nullptr) {
     // aligned pairs of slots (one ds_read_b64, the two counts share a word); the hash is a 24-bit product (full rate)
     const uint32_t mask = (1u << aggbits) - 1u;
-    uint32_t s = ((uint32_t)__umul24(key, 0x9E3779u) >> (32u - aggbits)) & ~1u;      // (__umul24 returns int: an arithmetic shift without the cast)
+    uint32_t s = ((uint32_t)__umul24(key, 0x9E3779u) >> hshift) & ~1u;      // (__umul24 returns int: an arithmetic shift without the cast)
     for (uint32_t pr = 0; pr < PLO_AGG_PROBES;) {
         if (iters) ++*iters;
         const unsigned long long kk = __hip_atomic_load((unsigned long long *)(aggk + s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -473,7 +504,7 @@ __device__ __forceinline__ bool agg_add_rid_first_prof(uint32_t *aggk, uint32_t 
 #define PLO_EUNIT(e_) (((e_) >> 15) & 1u)
 #define PLO_EVI(e_) ((e_) >> 16)
 // position of column c in row [base, base+L) (sorted by column), or -1
-__device__ __forceinline__ int row_find(const uint32_t *ent, uint32_t base, uint32_t L, uint32_t c) {
+template <class ENT> __device__ __forceinline__ int row_find(ENT ent, uint32_t base, uint32_t L, uint32_t c) {
     uint32_t lo = 0, hi = L;
     while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (PLO_ECOL(ent[base + mid]) < c) lo = mid + 1; else hi = mid; }
     return (lo < L && PLO_ECOL(ent[base + lo]) == c) ? (int)lo : -1;
@@ -553,7 +584,7 @@ __device__ __forceinline__ void dbloom_set(uint32_t *bl, uint64_t key) {
     wg_or(&bl[i1 >> 5], 1u << (i1 & 31u)); wg_or(&bl[i2 >> 5], 1u << (i2 & 31u)); wg_or(&bl[i3 >> 5], 1u << (i3 & 31u));
 }
 // slot of `key` in the hot table (v = its word), 0xFFFFFFFF when absent.  No slot is ever emptied between merges.
-__device__ __forceinline__ uint32_t hot_slot(const uint64_t *hot, uint64_t key, uint32_t hb, uint64_t &v) {
+template <class TAB> __device__ __forceinline__ uint32_t hot_slot(TAB hot, uint64_t key, uint32_t hb, uint64_t &v) {
     const uint32_t mask = (1u << hb) - 1u;
     uint32_t s = ghash(key, hb);
     for (uint32_t pr = 0; pr <= mask; ++pr) {
@@ -565,7 +596,7 @@ __device__ __forceinline__ uint32_t hot_slot(const uint64_t *hot, uint64_t key, 
     return 0xFFFFFFFFu;
 }
 // frequency[key] += d in the hot table, claiming EMPTY slots only; returns the frequency before (0 = new key), 0xFFFFFFFF = table full
-__device__ __forceinline__ uint32_t hot_addn(uint64_t *hot, uint64_t key, uint32_t d, uint32_t hb, uint32_t *hotn) {
+template <class TAB> __device__ __forceinline__ uint32_t hot_addn(TAB hot, uint64_t key, uint32_t d, uint32_t hb, uint32_t *hotn) {
     const uint32_t mask = (1u << hb) - 1u;
     uint32_t s = ghash(key, hb);
     for (uint32_t pr = 0; pr <= 2u * mask + 1u; ++pr) {
@@ -584,7 +615,7 @@ __device__ __forceinline__ uint32_t hot_addn(uint64_t *hot, uint64_t key, uint32
 #define PLO_DREC(key_, d_, ins_) (((uint64_t)(key_) << 16) | ((ins_) ? 0x8000ull : 0ull) | (uint64_t)((d_) & 0x7FFFu))
 // wave-collective append of up to three records per lane (all lanes of the wave call it): one counter update per wave,
 // the records of each kind are stored side by side
-__device__ __forceinline__ void dlog_append3(uint64_t *dlog, uint32_t *logn, uint32_t logcap, bool h1, uint64_t e1, bool h2, uint64_t e2, bool h3, uint64_t e3, uint32_t *errflag) {
+template <class LOG> __device__ __forceinline__ void dlog_append3(LOG dlog, uint32_t *logn, uint32_t logcap, bool h1, uint64_t e1, bool h2, uint64_t e2, bool h3, uint64_t e3, uint32_t *errflag) {
     const unsigned long long m1 = __builtin_amdgcn_ballot_w64(h1), m2 = __builtin_amdgcn_ballot_w64(h2), m3 = __builtin_amdgcn_ballot_w64(h3);
     const uint32_t n1 = (uint32_t)__builtin_popcountll(m1), n2 = (uint32_t)__builtin_popcountll(m2), n3 = (uint32_t)__builtin_popcountll(m3);
     if (n1 + n2 + n3 == 0u) return;
@@ -623,12 +654,15 @@ __device__ __forceinline__ bool lt_put(uint64_t *ltab, uint64_t key, int32_t del
 
 // The merge (all threads of the workgroup).  `mreg` = the Bloom filter followed by the scratch region (PLO_DMREG_WORDS words).
 // first = true: the store is the plan's image and hist[] its histogram, only the window is chosen.
-__device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigShared &sh, uint32_t *hist, uint32_t *mreg, bool first)
+template <class O> __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigShared &sh, uint32_t *hist, uint32_t *mreg, bool first)
 {
     const uint32_t tid = threadIdx.x, nth = blockDim.x, lane = tid & 63u, wave = tid >> 6, nwaves = nth >> 6;
-    uint64_t *store = (uint64_t *)(ws + P.o_store), *dlog = (uint64_t *)(ws + P.o_log), *hot = (uint64_t *)(ws + P.o_hot), *HL = (uint64_t *)(ws + P.o_hl);
-    uint32_t *pcount = (uint32_t *)(ws + P.o_pcount), *ptail = (uint32_t *)(ws + P.o_ptail);
-    const uint32_t pbits = P.pbits, Pn = 1u << pbits, capp = P.capp, rcap = P.capp + P.plcap;
+    uint64_t *store = (uint64_t *)(ws + P.o_store);                      // the large region, last in the slice: the one array with a pointer of its own
+    const WsArr<uint64_t, O> dlog{ws, ws_off<O>(P.o_log)}, hot{ws, ws_off<O>(P.o_hot)}, HL{ws, ws_off<O>(P.o_hl)};
+    const WsArr<uint32_t, O> pcount{ws, ws_off<O>(P.o_pcount)}, ptail{ws, ws_off<O>(P.o_ptail)};
+    // (the plan's words are read here, from the kernel-argument segment: plan_word)
+    const uint32_t pbits = PW(pbits), Pn = 1u << pbits, capp = PW(capp), rcap = capp + PW(plcap);
+    const uint32_t logcap = PW(logcap), maxf0 = PW(maxf0), hlcap = PW(hlcap), lgrp = PW(lgrp), hwin = PW(hwin), hotbits_max = PW(hotbits_max);
     unsigned long long tm0 = wall_clock64();
 #define PLO_MSTAMP(q_) do { if (tid == 0) { const unsigned long long t_ = wall_clock64(); sh.tmg[q_] += t_ - tm0; tm0 = t_; } } while (0)
     if (!first) {
@@ -639,7 +673,7 @@ __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigSh
                 const uint32_t s = s0 + tid;
                 const uint64_t v = s < hslots ? gload64(&hot[s]) : PLO_GEMPTY;
                 const bool have = v != PLO_GEMPTY && (uint32_t)(v & PLO_GVMASK) >= 2u;
-                dlog_append3(dlog, &sh.logn, P.logcap, have, (v & ~PLO_GVMASK) | 0x8000ull | (v & 0x7FFFull), false, 0ull, false, 0ull, &sh.errflag);
+                dlog_append3(dlog, &sh.logn, logcap, have, (v & ~PLO_GVMASK) | 0x8000ull | (v & 0x7FFFull), false, 0ull, false, 0ull, &sh.errflag);
             }
         }
         PLO_BIG_FENCE(); BSYNC();
@@ -649,7 +683,7 @@ __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigSh
         {
             uint64_t *stage = (uint64_t *)mreg; uint32_t *cnt = mreg + 2u * PLO_DCH, *pos = cnt + PLO_DPMAX, *tail = pos + PLO_DPMAX;
             for (uint32_t q = tid; q < Pn; q += nth) tail[q] = pcount[q];
-            const uint32_t nlog = sh.logn < P.logcap ? sh.logn : P.logcap;
+            const uint32_t nlog = sh.logn < logcap ? sh.logn : logcap;
             constexpr uint32_t U = PLO_DCH / PLO_BIG_THREADS;
             const uint32_t K = (Pn + nth - 1u) / nth;                       // partitions per thread in the prefix sum (<= 4)
             for (uint32_t base = 0; base < nlog; base += PLO_DCH) {
@@ -695,7 +729,7 @@ __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigSh
         if (sh.errflag) return;
         // ---- B. every group of partitions is summed in LDS; live triples go back to the store, the histogram is recounted
         {
-            for (uint32_t f = tid; f <= P.maxf0; f += nth) hist[f] = 0u;
+            for (uint32_t f = tid; f <= maxf0; f += nth) hist[f] = 0u;
             uint64_t *ltab = (uint64_t *)mreg;
             for (uint32_t s = tid; s < (1u << PLO_DLB); s += nth) ltab[s] = PLO_LEMPTY;      // once: the scan of a group leaves its slots empty again
             if (tid < 64u) sh.outcnt[tid] = 0u;
@@ -709,7 +743,7 @@ __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigSh
                 const uint32_t o = p_ - W + lane;                                  // 0 .. 127
                 const uint32_t x0 = (uint32_t)__shfl((int)cW, (int)(o & 63u)), x1 = (uint32_t)__shfl((int)cW2, (int)(o & 63u));
                 inc_ = wave_incl_scan(o < 64u ? x0 : x1);
-                const unsigned long long okm = __builtin_amdgcn_ballot_w64(inc_ <= P.lgrp);
+                const unsigned long long okm = __builtin_amdgcn_ballot_w64(inc_ <= lgrp);
                 g = okm == ~0ull ? 64u : (uint32_t)__builtin_ctzll(~okm);
                 if (g == 0u) g = 1u;
                 if (g > Pn - p_) g = Pn - p_;
@@ -761,7 +795,7 @@ __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigSh
                     const uint32_t cb = (uint32_t)(v & 0xFFFFull);
                     if (cb < PLO_DBIAS + 2u) continue;                       // frequency below 2: never chosen, never rises -- dropped
                     const uint32_t c = cb - PLO_DBIAS; const uint64_t k = v >> 16;
-                    if (c > P.maxf0) { wg_max(&sh.errflag, (uint32_t)BERR_FREQ); continue; }
+                    if (c > maxf0) { wg_max(&sh.errflag, (uint32_t)BERR_FREQ); continue; }
                     wg_add(&hist[c], 1u);
                     const uint32_t j = dpart(k, pbits) - p;
                     const uint32_t idx = j < 64u ? wg_add(&sh.outcnt[j], 1u) : capp;
@@ -781,11 +815,11 @@ __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigSh
     }
     // ---- the new window [theta, M]: at most hwin triples (the whole top level in any case), then the hot table of its triples
     if (tid == 0) {
-        uint32_t Mx = P.M0; while (Mx >= 2u && hist[Mx] == 0u) --Mx;
+        uint32_t Mx = PW(M0); while (Mx >= 2u && hist[Mx] == 0u) --Mx;
         uint64_t acc = 0; uint32_t th = 2u;
-        if (Mx >= 2u) { th = Mx; for (uint32_t f = Mx; f >= 2u; --f) { if (f != Mx && acc + hist[f] > P.hwin) break; acc += hist[f]; th = f; } }
-        if (acc > P.hlcap / 2u) wg_max(&sh.errflag, (uint32_t)BERR_HL);
-        uint32_t hb = P.hotbits_min; while ((1ull << hb) < 4ull * acc + 1024ull && hb < P.hotbits_max) ++hb;
+        if (Mx >= 2u) { th = Mx; for (uint32_t f = Mx; f >= 2u; --f) { if (f != Mx && acc + hist[f] > hwin) break; acc += hist[f]; th = f; } }
+        if (acc > hlcap / 2u) wg_max(&sh.errflag, (uint32_t)BERR_HL);
+        uint32_t hb = PW(hotbits_min); while ((1ull << hb) < 4ull * acc + 1024ull && hb < hotbits_max) ++hb;
 #ifdef PLO_BIG_MERGELOG
         printf("# merge %u at step %u: M %u theta %u window %llu triples (hot table 2^%u); histogram of the levels below: [%u]=%u [%u]=%u [%u]=%u; log %u records\n", sh.fullscans, sh.steps, Mx, th, (unsigned long long)acc, hb,
                th > 2u ? th - 1u : 0u, th > 2u ? hist[th - 1u] : 0u, th > 3u ? th - 2u : 0u, th > 3u ? hist[th - 2u] : 0u, 2u, hist[2], sh.logn);
@@ -815,7 +849,7 @@ __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigSh
                             if (hot_addn(hot, k, c, hb, &sh.hotn) != 0u) { wg_max(&sh.errflag, (uint32_t)BERR_TABLE); wg_max(&sh.derr, 106u); }
                             dbloom_set(mreg, k);
                             const uint32_t idx = wg_add(&sh.hlcount, 1u);
-                            if (idx < P.hlcap) HL[idx] = k; else wg_max(&sh.errflag, (uint32_t)BERR_HL);
+                            if (idx < hlcap) HL[idx] = k; else wg_max(&sh.errflag, (uint32_t)BERR_HL);
                             sp[e] = v[u] & ~0x7FFFull;                        // left the store (a flagged record of frequency 0)
                         }
                     }
@@ -831,38 +865,42 @@ __device__ __forceinline__ void defer_merge(const BigPlan &P, uint8_t *ws, BigSh
 // ---------------------------------------------------------------------------
 // One candidate by one workgroup.  Returns (adds<<32 | muls) in thread 0.
 // ---------------------------------------------------------------------------
-template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t big_candidate(const BigPlan &P, uint8_t *ws, uint64_t seed, BigShared &sh, uint32_t *hist, uint64_t *agg, uint32_t aggbits, const BigTabs &TB, uint32_t *errw)
+template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ uint64_t big_candidate(const BigPlan &P, uint8_t *ws, uint64_t seed, BigShared &sh, uint32_t *hist, uint64_t *agg, uint32_t aggbits, const BigTabs &TB, uint32_t *errw)
 {
     const uint32_t tid = threadIdx.x, nth = blockDim.x, lane = tid & 63u, wave = tid >> 6, nwaves = nth >> 6;
-    uint64_t *tab   = (uint64_t *)(ws + (DEFER ? P.o_hot : P.o_tab));      // the table the level code and the tie pick look triples up in (DEFER: the hot table)
-    uint64_t *dlog  = (uint64_t *)(ws + P.o_log); uint32_t *bloom = TB.bloom;   // DEFER
-    uint32_t *ent   = (uint32_t *)(ws + P.o_ent);
-    uint32_t *len   = (uint32_t *)(ws + P.o_len), *ucount = (uint32_t *)(ws + P.o_ucount), *cntM = (uint32_t *)(ws + P.o_cntM);
-    uint64_t *DM    = (uint64_t *)(ws + P.o_dm), *HL = (uint64_t *)(ws + P.o_hl);
+    // The arrays of the slice are base + byte offset (WsArr).  Only the eager table -- the large region, last in the slice, which the
+    // capacity refits can take past 4 GiB -- is a pointer; DEFER: the store is (defer_merge), the table looked up here is the hot table.
+    typedef WsArr<uint32_t, O> A32; typedef WsArr<uint64_t, O> A64;
+    auto tab = [&] { if constexpr (DEFER) return A64{ws, ws_off<O>(P.o_hot)}; else return (uint64_t *)(ws + P.o_tab); }();      // the table the level code and the tie pick look triples up in
+    const A64 dlog{ws, ws_off<O>(P.o_log)}; uint32_t *bloom = TB.bloom;   // DEFER
+    const A32 ent{ws, ws_off<O>(P.o_ent)};
+    const A32 len{ws, ws_off<O>(P.o_len)}, ucount{ws, ws_off<O>(P.o_ucount)}, cntM{ws, ws_off<O>(P.o_cntM)};
+    const A64 DM{ws, ws_off<O>(P.o_dm)}, HL{ws, ws_off<O>(P.o_hl)};
     // {value, inverse} per value index: LDS copy, or global memory above 512 values.  Two typed accesses,
     // never one generic pointer: a flat load waits for vmcnt(0) AND lgkmcnt(0) and would drain every prefetch.
     // (MODE is a template parameter: the compiler turns a run-time choice between the two address spaces into a flat load)
-    const uint2 *vtg = P.vt; const uint2 *vts = TB.vts;
+    const uint2 *vtg = PW(vt); const uint2 *vts = TB.vts;
     auto VT = [&](uint32_t vi) -> uint2 { if constexpr (MODE == 1) return vts[vi]; else return vtg[vi]; };
     const uint16_t *rtid = TB.rtid, *invid = TB.invid; const uint32_t *rval = TB.rval;   // mode 2
     uint32_t *aggk = (uint32_t *)agg, *aggc32 = aggk + (1u << aggbits); uint16_t *aggc16 = (uint16_t *)aggc32;      // mode 2: key array, count array
-    uint32_t *aff   = (uint32_t *)(ws + P.o_aff), *ncrptr = (uint32_t *)(ws + P.o_ncrptr), *ncr = (uint32_t *)(ws + P.o_ncr);
+    const A32 aff{ws, ws_off<O>(P.o_aff)}, ncrptr{ws, ws_off<O>(P.o_ncrptr)}, ncr{ws, ws_off<O>(P.o_ncr)};
     // slots claimed in the aggregation table by the running sweep (the flush walks this list, not the table): mode 2 has room
     // for every slot; the other modes keep a short list in the tie-selection buffer, idle during the sweeps, and walk the
     // table when a step claims more
     constexpr bool FAST = MODE == 2 && DEFER;                                  // staged aggregation with deferred claims, bitmap of claimed slots
     uint32_t *aggbm = (uint32_t *)sh.sel;                                       // FAST: one bit per aggregation slot (2^aggbits <= 2^14 bits; the tie-selection buffer is idle during the sweeps)
     uint16_t *agglist = (MODE == 2 && !DEFER) ? TB.list : (uint16_t *)sh.sel; const uint32_t listcap = (MODE == 2 && !DEFER) ? (1u << aggbits) : PLO_AGG_LIST;   // (DEFER: the Bloom filter has the place of mode 2's full list)
-    uint64_t *spill = (uint64_t *)(ws + P.o_spill); const uint32_t spillcap = P.nnz + 64u;   // new-column pairs of entries that found no room in LDS (a step touches every entry at most once)
-    uint32_t *multc = (uint32_t *)(ws + P.o_multc), *multv = (uint32_t *)(ws + P.o_multv);
+    const A64 spill{ws, ws_off<O>(P.o_spill)}; const uint32_t spillcap = PW(nnz) + 64u;   // new-column pairs of entries that found no room in LDS (a step touches every entry at most once)
+    const A32 multc{ws, ws_off<O>(P.o_multc)}, multv{ws, ws_off<O>(P.o_multv)};
     // A pair key is (first column, second column, ratio) in 48 bits.  The ratio field holds the residue (rb bits) -- or, IDK (mode 2 only:
     // a modulus too wide for 48 bits, e.g. a 31-bit prime with 32768 columns), the ratio's IDENTIFIER (kb <= 10 bits).  Identifiers are
     // ranks in the sorted list of ratios, so keys compare as they do with residues (the tie pick walks triples in key order, :244-253).
-    const uint32_t p = P.p, rb = P.rb, kb = IDK ? P.kb : P.rb, abits = kb + P.bb, n = P.n, m = P.m, mers = P.mers;
-    uint32_t hbits = DEFER ? P.hotbits_min : P.hbits;                                // DEFER: the hot table is sized anew at every merge
-    const uint64_t mu = P.mu, cap = 1ull << P.hbits;
+    const uint32_t p = PW(p), rb = PW(rb), kb = IDK ? PW(kb) : rb, abits = kb + PW(bb), n = PW(n), m = PW(m), mers = PW(mers);
+    uint32_t hbits = DEFER ? PW(hotbits_min) : PW(hbits);                          // DEFER: the hot table is sized anew at every merge
+    const uint64_t mu = PW(mu), cap = 1ull << PW(hbits);
+    const uint32_t nr_ = (MODE == 2 && IDK) ? PW(nr) : 0u;
     auto key_ratio = [&](uint32_t x) -> uint32_t {                                   // the ratio field of a key for the residue x
-        if constexpr (MODE == 2 && IDK) { uint32_t lo = 0, hi = P.nr; while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (rval[mid] < x) lo = mid + 1u; else hi = mid; } return lo; }
+        if constexpr (MODE == 2 && IDK) { uint32_t lo = 0, hi = nr_; while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (rval[mid] < x) lo = mid + 1u; else hi = mid; } return lo; }
         else return x;
     };
 #define BKEY(a_, b_, r_) (((uint64_t)(a_) << abits) | ((uint64_t)(b_) << kb) | (uint64_t)key_ratio(r_))
@@ -870,49 +908,53 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
     // ---- load the candidate image
     const unsigned long long tld0 = wall_clock64();
     {   // 16-byte copies, 4 in flight per thread (all buffers are 256-byte aligned, sizes padded by the host)
-        const uint4 *s4 = (const uint4 *)P.tab0; uint4 *d4 = (uint4 *)tab;
+        const uint4 *s4 = (const uint4 *)PW(tab0); uint4 *d4 = (uint4 *)tab;
         const uint64_t n4 = DEFER ? 0ull : cap >> 1;                                                // (DEFER: the store image is copied partition by partition below)
         for (uint64_t s = tid; s < n4; s += 4ull * nth) {
             uint4 x0 = s4[s], x1, x2, x3; const bool b1 = s + nth < n4, b2 = s + 2ull * nth < n4, b3 = s + 3ull * nth < n4;
             if (b1) x1 = s4[s + nth]; if (b2) x2 = s4[s + 2ull * nth]; if (b3) x3 = s4[s + 3ull * nth];
             d4[s] = x0; if (b1) d4[s + nth] = x1; if (b2) d4[s + 2ull * nth] = x2; if (b3) d4[s + 3ull * nth] = x3;
         }
-        const uint32_t q4 = (P.nnz + 3u) >> 2;
-        const uint4 *e4 = (const uint4 *)P.ent0; uint4 *de = (uint4 *)ent;
+        const uint32_t q4 = (PW(nnz) + 3u) >> 2;
+        const uint4 *e4 = (const uint4 *)PW(ent0); uint4 *de = (uint4 *)ent;
         for (uint32_t k = tid; k < q4; k += 2u * nth) { uint4 x = e4[k], y; const bool b1 = k + nth < q4; if (b1) y = e4[k + nth]; de[k] = x; if (b1) de[k + nth] = y; }
     }
     if constexpr (DEFER) {
-        uint32_t *pcount = (uint32_t *)(ws + P.o_pcount), *ptail = (uint32_t *)(ws + P.o_ptail);
-        for (uint32_t q = tid; q < (1u << P.pbits); q += nth) { pcount[q] = P.pcount0[q]; ptail[q] = P.pcount0[q]; }
-        uint64_t *store = (uint64_t *)(ws + P.o_store); const uint32_t rcap = P.capp + P.plcap;
-        for (uint32_t q = wave; q < (1u << P.pbits); q += nwaves) {           // a wave copies whole partitions of the image (stride capp) to the store (stride capp + plcap)
-            const uint32_t nq = P.pcount0[q]; const uint64_t *sp = P.st0 + (uint64_t)q * P.capp; uint64_t *dp = store + (uint64_t)q * rcap;
+        const A32 pcount{ws, ws_off<O>(P.o_pcount)}, ptail{ws, ws_off<O>(P.o_ptail)};
+        const uint32_t Pn = 1u << PW(pbits), capp = PW(capp), rcap = capp + PW(plcap); const uint32_t *const pcount0 = PW(pcount0); const uint64_t *const st0 = PW(st0);
+        for (uint32_t q = tid; q < Pn; q += nth) { pcount[q] = pcount0[q]; ptail[q] = pcount0[q]; }
+        uint64_t *store = (uint64_t *)(ws + P.o_store);
+        for (uint32_t q = wave; q < Pn; q += nwaves) {           // a wave copies whole partitions of the image (stride capp) to the store (stride capp + plcap)
+            const uint32_t nq = pcount0[q]; const uint64_t *sp = st0 + (uint64_t)q * capp; uint64_t *dp = store + (uint64_t)q * rcap;
             for (uint32_t e = lane; e < nq; e += 128u) { const uint64_t x0 = sp[e], x1 = e + 64u < nq ? sp[e + 64u] : 0ull; dp[e] = x0; if (e + 64u < nq) dp[e + 64u] = x1; }
         }
     }
-    uint32_t *tl = (uint32_t *)(ws + P.o_tl), *clen = (uint32_t *)(ws + P.o_clen), *keep = (uint32_t *)(ws + P.o_keep);
+    const A32 tl{ws, ws_off<O>(P.o_tl)}, clen{ws, ws_off<O>(P.o_clen)}, keep{ws, ws_off<O>(P.o_keep)};
     {   // this candidate's copy of the input columns' row lists (compacted in place as the steps walk them)
-        const uint32_t q4 = (P.nnz + 3u) >> 2;
-        const uint4 *t4 = (const uint4 *)P.trows; uint4 *d4 = (uint4 *)tl;
+        const uint32_t q4 = (PW(nnz) + 3u) >> 2;
+        const uint4 *t4 = (const uint4 *)PW(trows); uint4 *d4 = (uint4 *)tl;
         for (uint32_t k = tid; k < q4; k += 2u * nth) { uint4 x = t4[k], y; const bool b1 = k + nth < q4; if (b1) y = t4[k + nth]; d4[k] = x; if (b1) d4[k + nth] = y; }
     }
-    for (uint32_t i = tid; i < m; i += nth) len[i] = P.rs[i + 1] - P.rs[i];
-    for (uint32_t c = tid; c < P.NCmax; c += nth) { ucount[c] = c < n ? P.ucount0[c] : 0u; cntM[c] = 0u; clen[c] = c < n ? P.tptr[c + 1] - P.tptr[c] : 0u; }
-    for (uint32_t f = tid; f <= P.maxf0; f += nth) hist[f] = P.hist0[f];
-    const uint32_t acb = P.agg_cb; const uint64_t AEMPTY = ~0ull << acb;
+    {
+        const uint32_t *const rs = PW(rs), *const ucount0 = PW(ucount0), *const tptr = PW(tptr), *const hist0 = PW(hist0); const uint32_t NCmax = PW(NCmax), maxf0 = PW(maxf0);
+        for (uint32_t i = tid; i < m; i += nth) len[i] = rs[i + 1] - rs[i];
+        for (uint32_t c = tid; c < NCmax; c += nth) { ucount[c] = c < n ? ucount0[c] : 0u; cntM[c] = 0u; clen[c] = c < n ? tptr[c + 1] - tptr[c] : 0u; }
+        for (uint32_t f = tid; f <= maxf0; f += nth) hist[f] = hist0[f];
+    }
+    const uint32_t acb = PW(agg_cb); const uint64_t AEMPTY = ~0ull << acb;
     if constexpr (MODE == 2) { for (uint32_t s = tid; s < (1u << aggbits); s += nth) { aggk[s] = 0xFFFFFFFFu; aggc16[s] = 0; } }
     else for (uint32_t s = tid; s < (1u << aggbits); s += nth) agg[s] = AEMPTY;
     if (tid == 0) {
         uint64_t x = seed + 0x9E3779B97F4A7C15ull;
         x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; x ^= x >> 31;
         sh.rng = 1u + (uint32_t)(x % 2147483646ull);
-        sh.M = P.M0; sh.theta = P.M0 + 1u; sh.ncols = n; sh.nbadd = 0; sh.nbmul = 0; sh.nmult = 0; sh.dmcount = 0; sh.hlcount = 0;
+        sh.M = PW(M0); sh.theta = PW(M0) + 1u; sh.ncols = n; sh.nbadd = 0; sh.nbmul = 0; sh.nmult = 0; sh.dmcount = 0; sh.hlcount = 0;
         for (int q = 0; q < 8; ++q) sh.tph[q] = 0;
 #ifdef PLO_BIG_PROFILE
         for (int q = 0; q < 4; ++q) { sh.tb1[q] = sh.tb2[q] = 0; sh.nb[q] = 0; } sh.fb1 = sh.fb2 = sh.fl1 = sh.fl2 = 0; for (int q = 0; q < 16; ++q) sh.pw[q] = 0; for (int c_ = 0; c_ < 4; ++c_) for (int q = 0; q < 8; ++q) sh.tpc[c_][q] = 0;
 #endif
         sh.errflag = 0; sh.fullscans = 0; sh.rebuilds = 0; sh.steps = 0; sh.hlbad = 0; ncrptr[0] = 0; sh.nbisect = 0; sh.spilltot = 0; sh.listover = 0; sh.nwin = 0; sh.nsearched = 0;
-        sh.logn = 0; sh.hotn = 0; sh.hotbits = P.hotbits_min; sh.derr = 0; for (int q = 0; q < 4; ++q) { sh.tmg[q] = 0; sh.tmb[q] = 0; } sh.ngrp = 0; sh.nloop = 0; sh.nforced = 0; sh.hotops = 0; sh.logtot_lo = 0; sh.logtot_hi = 0;
+        sh.logn = 0; sh.hotn = 0; sh.hotbits = PW(hotbits_min); sh.derr = 0; for (int q = 0; q < 4; ++q) { sh.tmg[q] = 0; sh.tmb[q] = 0; } sh.ngrp = 0; sh.nloop = 0; sh.nforced = 0; sh.hotops = 0; sh.logtot_lo = 0; sh.logtot_hi = 0;
     }
     PLO_BIG_FENCE(); BSYNC();
     if (tid == 0) sh.tld = wall_clock64() - tld0;
@@ -929,7 +971,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                 if (tid == 0) {
                     uint32_t M = sh.M; const uint32_t th = sh.theta;
                     while (M >= th && hist[M] == 0u) --M;
-                    const bool low = M < th, pressure = sh.logn > P.logtrig || sh.hotn > (1u << sh.hotbits) / 2u || sh.hlbad;
+                    const bool low = M < th, pressure = sh.logn > PW(logtrig) || sh.hotn > (1u << sh.hotbits) / 2u || sh.hlbad;
                     sh.part[0] = (M != sh.M) ? 1u : 0u; sh.part[1] = (low || pressure) ? 1u : 0u;
                     if (!low) { sh.M = M; if (pressure) ++sh.nforced; }
                 }
@@ -939,7 +981,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                 BSYNC();
                 if (!mg) break;
                 { const uint32_t ln_ = sh.logn; if (tid == 0) { const uint32_t lo_ = sh.logtot_lo; sh.logtot_lo = lo_ + ln_; if (sh.logtot_lo < lo_) ++sh.logtot_hi; } }
-                defer_merge(P, ws, sh, hist, bloom, dfirst);
+                defer_merge<O>(P, ws, sh, hist, bloom, dfirst);
                 if (!dfirst) {                                                // the merge worked in the scratch region: the aggregation table is empty again
                     if constexpr (MODE == 2) { for (uint32_t s = tid; s < (1u << aggbits); s += nth) { aggk[s] = 0xFFFFFFFFu; aggc16[s] = 0; } }
                     else for (uint32_t s = tid; s < (1u << aggbits); s += nth) agg[s] = AEMPTY;
@@ -963,12 +1005,13 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
         if (!DEFER && sh.part[0]) need_rebuild = true;
         BSYNC();
         if (need_rebuild) {
+            const uint32_t hlcap = PW(hlcap), dmcap = PW(dmcap);              // (plan words of this phase)
             if (!DEFER && (M < sh.theta || sh.hlbad)) {
                 // full table scan: new window [theta', M] holding at most hlcap/2 keys
                 if (tid == 0) {
                     uint64_t acc = 0; uint32_t th = M;
-                    for (uint32_t f = M; f >= 2u; --f) { if (acc + hist[f] > P.hlcap / 2u) break; acc += hist[f]; th = f; }
-                    if (hist[M] > P.hlcap / 2u) wg_max(&sh.errflag, (uint32_t)BERR_HL);
+                    for (uint32_t f = M; f >= 2u; --f) { if (acc + hist[f] > hlcap / 2u) break; acc += hist[f]; th = f; }
+                    if (hist[M] > hlcap / 2u) wg_max(&sh.errflag, (uint32_t)BERR_HL);
                     sh.theta = th; sh.hlcount = 0; sh.hlbad = 0; ++sh.fullscans;
                 }
                 BSYNC();
@@ -981,7 +1024,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                     for (int u = 0; u < 4; ++u)
                         if ((uint32_t)(v[u] & PLO_GVMASK) >= th && v[u] != PLO_GEMPTY) {
                             uint32_t idx = wg_add(&sh.hlcount, 1u);
-                            if (idx < P.hlcap) HL[idx] = v[u] >> PLO_GVB; else wg_max(&sh.errflag, (uint32_t)BERR_HL);
+                            if (idx < hlcap) HL[idx] = v[u] >> PLO_GVB; else wg_max(&sh.errflag, (uint32_t)BERR_HL);
                         }
                 }
                 BSYNC();
@@ -990,11 +1033,11 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
             // the window are dropped from it (they can never come back)
             for (uint32_t c = tid; c < sh.ncols; c += nth) cntM[c] = 0u;
             for (uint32_t c = tid; c < 512u; c += nth) sh.cblk[c] = 0u;
-            const uint32_t hn = sh.hlcount < P.hlcap ? sh.hlcount : P.hlcap;
+            const uint32_t hn = sh.hlcount < hlcap ? sh.hlcount : hlcap;
             PLO_BIG_FENCE(); BSYNC();
             if (tid == 0) { sh.dmcount = 0; sh.hlcount = 0; ++sh.rebuilds; }
             BSYNC();
-            uint64_t *HL2 = HL + P.hlcap;                                       // ping-pong halves of the window list
+            const A64 HL2 = HL + hlcap;                                       // ping-pong halves of the window list
             const uint32_t th2 = sh.theta;
             for (uint32_t k = tid; k < hn; k += nth) {
                 const uint64_t key = HL[k];
@@ -1004,7 +1047,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                     const uint32_t fc = (uint32_t)(key >> abits);
                     wg_add(&cntM[fc], 1u); wg_add(&sh.cblk[fc >> 6], 1u);
                     uint32_t idx = wg_add(&sh.dmcount, 1u);
-                    if (idx < P.dmcap) DM[idx] = key; else wg_max(&sh.errflag, (uint32_t)BERR_DM);
+                    if (idx < dmcap) DM[idx] = key; else wg_max(&sh.errflag, (uint32_t)BERR_DM);
                 }
             }
             PLO_BIG_FENCE(); BSYNC();
@@ -1016,6 +1059,10 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
         PLO_STAMP(0);
         // ---- tie pick (OneSub :244-265): k-th triple of frequency M in map order
         const uint32_t ncols = sh.ncols;
+        // (plan words of the tie pick AND of the row search, requested together here, ahead of the tie pick's barriers: at the row
+        // search's own head they would be scalar-cache round trips on the step's dependent chain)
+        const uint32_t dmcap = PW(dmcap), selcap = PW(selcap), bb = PW(bb), NCmax = PW(NCmax);
+        const uint32_t *const rs = PW(rs), *const tptr = PW(tptr);
         {
             if (wave == 0) {
                 // block of 64 first columns from the LDS block sums, then one wave-wide load of that block.  The 512 block sums are
@@ -1057,12 +1104,12 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
             BSYNC();
             if (sh.errflag) break;
             const uint32_t a = sh.a;
-            const uint32_t dn = sh.dmcount < P.dmcap ? sh.dmcount : P.dmcap;
+            const uint32_t dn = sh.dmcount < dmcap ? sh.dmcount : dmcap;
             for (uint32_t k = tid; k < dn; k += nth) {
                 const uint64_t key = DM[k];
                 if ((uint32_t)(key >> abits) == a && gtab_find(tab, key, hbits) == M) {
                     uint32_t idx = wg_add(&sh.sel_n, 1u);
-                    if (idx < P.selcap) sh.sel[idx] = key; else sh.sel_over = 1u;
+                    if (idx < selcap) sh.sel[idx] = key; else sh.sel_over = 1u;
                 }
             }
             BSYNC();
@@ -1100,10 +1147,10 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
         }
         const uint64_t key = sh.selkey;
         PLO_STAMP(1);
-        const uint32_t rfield = (uint32_t)(key & ((1ull << kb) - 1ull)), b = (uint32_t)(key >> kb) & ((1u << P.bb) - 1u), a = (uint32_t)(key >> abits);
+        const uint32_t rfield = (uint32_t)(key & ((1ull << kb) - 1ull)), b = (uint32_t)(key >> kb) & ((1u << bb) - 1u), a = (uint32_t)(key >> abits);
         uint32_t r = rfield; if constexpr (MODE == 2 && IDK) r = rval[rfield];
         const uint32_t lm = ncols;
-        if (lm + 1u >= P.NCmax) { if (tid == 0) wg_max(&sh.errflag, (uint32_t)BERR_COLS); BSYNC(); break; }
+        if (lm + 1u >= NCmax) { if (tid == 0) wg_max(&sh.errflag, (uint32_t)BERR_COLS); BSYNC(); break; }
         // ---- RemOneCSE :60-194
         const bool swap = gload32(&ucount[a]) < gload32(&ucount[b]);      // :70-88
         const uint32_t l0 = swap ? b : a, l1 = swap ? a : b;
@@ -1112,15 +1159,15 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
         BSYNC();
 #define RL(v_, k_) ((uint32_t)__builtin_amdgcn_readlane((int)(v_), (int)(k_)))
         {   // rows holding the triple: walk the shorter row list of the two columns
-            uint32_t *la = a < n ? tl + P.tptr[a] : ncr + ncrptr[a - n], *lb = b < n ? tl + P.tptr[b] : ncr + ncrptr[b - n];
+            const A32 la = a < n ? tl + tptr[a] : ncr + ncrptr[a - n], lb = b < n ? tl + tptr[b] : ncr + ncrptr[b - n];
             const uint32_t na = gload32(&clen[a]), nb = gload32(&clen[b]);          // live lengths: what earlier walks left of the lists
             const bool walk_a = na <= nb;
-            const uint32_t *lst = walk_a ? la : lb; const uint32_t ln = walk_a ? na : nb;
+            const A32 lst = walk_a ? la : lb; const uint32_t ln = walk_a ? na : nb;
             if (tid == 0) sh.nsearched += ln;
             // Two rows per thread and trip, both columns of both rows searched in lock step: the four binary searches have
             // their loads in flight together (8 dependent memory round trips for two rows instead of 36).  A search keeps
             // the last entry it saw at its upper bound: when it ends that is the entry at the found position.
-            uint32_t *newrows = ncr + ncrptr[lm - n];
+            const A32 newrows = ncr + ncrptr[lm - n];
             auto emit = [&](uint32_t i, uint32_t base, uint32_t L, uint32_t pa, uint32_t pb, uint32_t ea, uint32_t eb) -> bool {      // true: the row holds the triple
                 uint32_t inv_r;
                 if constexpr (MODE == 2) {
@@ -1142,7 +1189,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                     // spills two more scalar registers (the register allocation here is on a knife edge)
                     *(uint4 *)(aff + 4u * idx) = make_uint4(pa | (pb << 16), base, L | (PLO_EUNIT(ea) << 14) | (PLO_EVI(ea) << 15) | (PLO_EUNIT(eb) << 20) | (PLO_EVI(eb) << 21) | 0x7C000000u, i);
                 } else {
-                uint32_t *rec = aff + 8u * idx;                             // record: row, positions (16 bits each), row start and length; the two packed entries
+                uint32_t *rec = &aff[8u * idx];                             // record: row, positions (16 bits each), row start and length; the two packed entries
                 *(uint4 *)rec = make_uint4(i, pa | (pb << 16), base, L);
                 *(uint2 *)(rec + 4) = make_uint2(ea, eb);
                 }
@@ -1163,7 +1210,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
             for (uint32_t k = tid; k < ln; k += 2u * nth) {
                 const bool two = k + nth < ln;
                 const uint32_t i0 = lst[k], i1 = two ? lst[k + nth] : i0;
-                const uint32_t bs0 = P.rs[i0], bs1 = P.rs[i1], L0 = len[i0], L1 = two ? len[i1] : 0u;
+                const uint32_t bs0 = rs[i0], bs1 = rs[i1], L0 = len[i0], L1 = two ? len[i1] : 0u;
                 uint32_t lo[4] = {0u, 0u, 0u, 0u}, hi[4] = {L0, L0, L1, L1}, ev[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
                 for (;;) {
                     uint32_t v[4], mid[4]; bool any = false;
@@ -1190,7 +1237,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
         const uint32_t naff = sh.naff;
         {   // the walked list, compacted (it is read next in a later step, many barriers from here)
             const uint32_t nk = sh.keepn, lc = gload32(&clen[a]) <= gload32(&clen[b]) ? a : b;
-            uint32_t *dst = lc < n ? tl + P.tptr[lc] : ncr + ncrptr[lc - n];
+            const A32 dst = lc < n ? tl + tptr[lc] : ncr + ncrptr[lc - n];
             for (uint32_t k = tid; k < nk; k += nth) dst[k] = keep[k];
             BSYNC();                                                           // (every thread has read both lengths)
             if (tid == 0) clen[lc] = nk;
@@ -1207,6 +1254,11 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
 #ifdef PLO_BIG_PROFILE
             uint32_t probe_iters = 0; unsigned long long pq[3] = {0, 0, 0}, prt = 0;
 #endif
+            // The hash's shift count lives in a vector register through the sweep: it is the one scalar of the trip's straight path
+            // that found no scalar register (a v_readlane per trip), and the kernel has vector registers to spare for one word.
+            uint32_t aggsh = 32u - aggbits; asm("" : "+v"(aggsh));
+            const uint32_t agg_dual = MODE == 2 ? 0u : PW(agg_dual), logcap = DEFER ? PW(logcap) : 0u;       // (plan words of this phase; none is read inside the trip:
+            // the kernel-argument pointer would have to be at hand there, and it is a spilled pair)
             auto retire_entry = [&](uint32_t e, uint32_t via, uint32_t vib, uint2 VA, uint2 VB, bool noagg = false) {      // noagg: the LDS table had no room for it (already tried)
                 const uint32_t c = PLO_ECOL(e);
                 // x = v_a/v_c (c < a) or v_c/v_a (c > a) names both retired pairs; y = v_a/v_c names the pair with the new column
@@ -1223,10 +1275,10 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); prt += clock64() - cr0;
                         const bool pend = agg_add_rid_first_prof(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm, pq);
                         if (!__builtin_amdgcn_ballot_w64(pend)) return;
-                        if (!pend || agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm, &probe_iters)) return;
+                        if (!pend || agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm, aggsh, &probe_iters)) return;
                     }
 #else
-                    if constexpr (FAST) { if (!noagg) { if (agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm)) return; } }
+                    if constexpr (FAST) { if (!noagg) { if (__builtin_expect(agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm, aggsh), 1)) return; } }
 #endif
                     else if (agg_add_rid(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, &sh.aggn, agglist, listcap)) return;
                     const uint32_t bc = rval[rtid[vib * PLO_RSTRIDE + vi]];                                  // v_b / v_c
@@ -1238,7 +1290,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                     y = bmul(VA.x, V.y, p, mu, mers);
                     x = c < a ? y : bmul(V.x, VA.y, p, mu, mers);
                     const uint64_t cx = ((uint64_t)c << rb) | x;
-                    if (agg_add(agg, aggbits, acb, P.agg_dual ? (cx << rb) | y : cx, (uint32_t)cx ^ ((uint32_t)(cx >> 32) * 0x85EBCA6Bu), &sh.aggn, agglist, listcap)) return;
+                    if (agg_add(agg, aggbits, acb, agg_dual ? (cx << rb) | y : cx, (uint32_t)cx ^ ((uint32_t)(cx >> 32) * 0x85EBCA6Bu), &sh.aggn, agglist, listcap)) return;
                     q2 = c < b ? bmul(VB.x, V.y, p, mu, mers) : bmul(V.x, VB.y, p, mu, mers);
                     ins = bmul(l0 == a ? VA.x : VB.x, V.y, p, mu, mers);
                 }
@@ -1263,7 +1315,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                                 done = true;
                             }
                         }
-                        if (!done) { const uint32_t li = wg_add(&sh.logn, 1u); if (li < P.logcap) dlog[li] = PLO_DREC(kk, 1u, false); else wg_max(&sh.errflag, (uint32_t)BERR_TABLE); }
+                        if (!done) { const uint32_t li = wg_add(&sh.logn, 1u); if (li < logcap) dlog[li] = PLO_DREC(kk, 1u, false); else wg_max(&sh.errflag, (uint32_t)BERR_TABLE); }
                     }
                     const uint32_t idx = wg_add(&sh.nspill, 1u);
                     if (idx < spillcap) spill[idx] = BKEY(c, lm, ins); else wg_max(&sh.errflag, (uint32_t)BERR_TABLE);
@@ -1303,7 +1355,8 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
             // Stores of a trip reach back at most two positions and never into the next trip's entries (requested a trip
             // earlier), so no load sees a store.
             uint64_t *fm = sh.sel + 256u + 32u * wave;                  // (the bitmap of claimed slots takes at most the first 2 KB)
-            const uint32_t dump = P.nnz + 64u + lane;                   // (the entry array has 128 spare words)
+            const uint32_t FW = PW(fwin);
+            const uint32_t dump = PW(nnz) + 64u + lane;                   // (the entry array has 128 spare words)
             const uint32_t selsh = l0 == a ? 14u : 20u;                 // the new column's entry carries the +-1 flag and the value index of the l0 entry
             for (uint32_t k0 = 0; k0 < nrw; k0 += 64u) {
                 const bool have = k0 + lane < nrw;
@@ -1313,7 +1366,6 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                 const uint32_t E = wave_incl_scan(Lr), S = E - Lr, T = RL(E, 63);
                 const uint32_t safe = RL(R0.y, 0);
                 uint32_t qlo = 0;
-                const uint32_t FW = P.fwin;
                 for (uint32_t w0 = 0; w0 < T; w0 += FW) {
                     if (w0 && tid == 0) ++sh.nwin;
                     if (lane < 32u) __hip_atomic_store(&fm[lane], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1470,6 +1522,8 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
             // Flush (DEFER), ONE pass over the aggregation table: an entry (c, x) x d retires two triples and creates one.  A triple
             // that may be hot (Bloom filter, then the hot table) is updated there, exactly; everything else is a log record.
             const uint32_t invr = sh.invr, theta = sh.theta;
+            const uint32_t maxf0 = PW(maxf0), hlcap = PW(hlcap), dmcap = PW(dmcap), logcap = PW(logcap);     // (plan words of this phase)
+            const uint32_t agg_dual = MODE == 2 ? 0u : PW(agg_dual); const uint32_t *const invtab = MODE == 2 ? nullptr : PW(invtab);
             auto retired = [&](uint64_t k, uint32_t d, uint32_t o) {
                 if (o < d) { { wg_max(&sh.errflag, (uint32_t)BERR_TABLE); wg_max(&sh.derr, 201u); } return; }
                 wg_sub(&hist[o], 1u); if (o > d) wg_add(&hist[o - d], 1u);
@@ -1477,14 +1531,14 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
             };
             auto inserted = [&](uint64_t k, uint32_t o, uint32_t d) {
                 const uint32_t nc = o + d;
-                if (nc > P.maxf0 || nc > M) { wg_max(&sh.errflag, (uint32_t)BERR_FREQ); return; }
+                if (nc > maxf0 || nc > M) { wg_max(&sh.errflag, (uint32_t)BERR_FREQ); return; }
                 if (o > 0u) wg_sub(&hist[o], 1u);
                 wg_add(&hist[nc], 1u);
-                if (o < theta && nc >= theta) { uint32_t idx = wg_add(&sh.hlcount, 1u); if (idx < P.hlcap) HL[idx] = k; else sh.hlbad = 1u; }
+                if (o < theta && nc >= theta) { uint32_t idx = wg_add(&sh.hlcount, 1u); if (idx < hlcap) HL[idx] = k; else sh.hlbad = 1u; }
                 if (nc == M) {
                     wg_add(&cntM[(uint32_t)(k >> abits)], 1u); wg_add(&sh.cblk[(uint32_t)(k >> abits) >> 6], 1u);
                     uint32_t idx = wg_add(&sh.dmcount, 1u);
-                    if (idx < P.dmcap) DM[idx] = k; else wg_max(&sh.errflag, (uint32_t)BERR_DM);
+                    if (idx < dmcap) DM[idx] = k; else wg_max(&sh.errflag, (uint32_t)BERR_DM);
                 }
             };
             if (tid == 0) {                                                   // the chosen triple loses its M instances (it is of level M >= theta: hot)
@@ -1519,9 +1573,9 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                     if (valid) {
                         agg[s] = AEMPTY;
                         uint64_t k = v >> acb; d = (uint32_t)(v & ((1ull << acb) - 1ull));
-                        if (P.agg_dual) { y = (uint32_t)(k & ((1ull << rb) - 1ull)); k >>= rb; }
+                        if (agg_dual) { y = (uint32_t)(k & ((1ull << rb) - 1ull)); k >>= rb; }
                         c = (uint32_t)(k >> rb); x = (uint32_t)(k & ((1ull << rb) - 1ull));
-                        if (!P.agg_dual) y = c > a ? (P.invtab ? P.invtab[x] : binv(x, p, mu, mers)) : x;   // v_a / v_c
+                        if (!agg_dual) y = c > a ? (invtab ? invtab[x] : binv(x, p, mu, mers)) : x;   // v_a / v_c
                     }
                 }
                 uint64_t k1 = 0, k2 = 0, k3 = 0;
@@ -1545,7 +1599,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                     const uint32_t o = hot_addn(tab, k3, d, hbits, &sh.hotn);
                     if (o != 0u) { wg_max(&sh.errflag, (uint32_t)BERR_TABLE); wg_max(&sh.derr, 203u); } else { inserted(k3, 0u, d); dbloom_set(bloom, k3); ++nhot; }
                 }
-                dlog_append3(dlog, &sh.logn, P.logcap, c1, PLO_DREC(k1, d, false), c2, PLO_DREC(k2, d, false), c3, PLO_DREC(k3, d, true), &sh.errflag);
+                dlog_append3(dlog, &sh.logn, logcap, c1, PLO_DREC(k1, d, false), c2, PLO_DREC(k2, d, false), c3, PLO_DREC(k3, d, true), &sh.errflag);
                 if constexpr (FAST) more_ = __builtin_amdgcn_ballot_w64(bits_ != 0u) != 0ull; else more_ = false;
               }
             }
@@ -1568,6 +1622,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
         // place to (c, that ratio) and the second pass inserts it -- the rows are not hashed a second time.
         {
             const uint32_t invr = sh.invr;
+            const uint32_t agg_dual = MODE == 2 ? 0u : PW(agg_dual); const uint32_t *const invtab = MODE == 2 ? nullptr : PW(invtab);     // (plan words of this phase)
             auto retired = [&](uint64_t k, uint32_t d, uint32_t o) {       // bookkeeping of a retirement that found frequency o
                 if (o == 0u) return;                                       // not in the table: a triple of frequency 1 (pruned)
                 if (o < d) { wg_max(&sh.errflag, (uint32_t)BERR_TABLE); return; }
@@ -1607,9 +1662,9 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                                 const uint64_t v = agg[s];
                                 if (v == AEMPTY) continue;
                                 uint64_t k = v >> acb; d = (uint32_t)(v & ((1ull << acb) - 1ull));
-                                if (P.agg_dual) { y = (uint32_t)(k & ((1ull << rb) - 1ull)); k >>= rb; }
+                                if (agg_dual) { y = (uint32_t)(k & ((1ull << rb) - 1ull)); k >>= rb; }
                                 c = (uint32_t)(k >> rb); x = (uint32_t)(k & ((1ull << rb) - 1ull));
-                                if (!P.agg_dual) y = c > a ? (P.invtab ? P.invtab[x] : binv(x, p, mu, mers)) : x;   // v_a / v_c
+                                if (!agg_dual) y = c > a ? (invtab ? invtab[x] : binv(x, p, mu, mers)) : x;   // v_a / v_c
                             }
                             const uint32_t ry = bmul(r, y, p, mu, mers);                        // v_b / v_c
                             const uint32_t x2 = c < b ? ry : bmul(x, invr, p, mu, mers);
@@ -1677,16 +1732,17 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
         if (sh.errflag) break;
         // Flush, second pass: the insertions (:132-142), after every retirement (dead-slot reuse needs that order)
         {
+            const uint32_t maxf0 = PW(maxf0), hlcap = PW(hlcap), dmcap = PW(dmcap), prune = PW(prune);       // (plan words of this phase)
             auto inserted = [&](uint64_t k, uint32_t o, uint32_t d) {
                 const uint32_t nc = o + d;
-                if (nc > P.maxf0 || nc > M) { wg_max(&sh.errflag, (uint32_t)BERR_FREQ); return; }
+                if (nc > maxf0 || nc > M) { wg_max(&sh.errflag, (uint32_t)BERR_FREQ); return; }
                 if (o > 0u) wg_sub(&hist[o], 1u);
                 wg_add(&hist[nc], 1u);
-                if (o < sh.theta && nc >= sh.theta) { uint32_t idx = wg_add(&sh.hlcount, 1u); if (idx < P.hlcap) HL[idx] = k; else sh.hlbad = 1u; }
+                if (o < sh.theta && nc >= sh.theta) { uint32_t idx = wg_add(&sh.hlcount, 1u); if (idx < hlcap) HL[idx] = k; else sh.hlbad = 1u; }
                 if (nc == M) {
                     wg_add(&cntM[(uint32_t)(k >> abits)], 1u); wg_add(&sh.cblk[(uint32_t)(k >> abits) >> 6], 1u);
                     uint32_t idx = wg_add(&sh.dmcount, 1u);
-                    if (idx < P.dmcap) DM[idx] = k; else wg_max(&sh.errflag, (uint32_t)BERR_DM);
+                    if (idx < dmcap) DM[idx] = k; else wg_max(&sh.errflag, (uint32_t)BERR_DM);
                 }
             };
             const uint32_t nent = sh.aggn, nslot = nent <= listcap ? nent : (1u << aggbits);
@@ -1714,7 +1770,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                             k = BKEY((uint32_t)(kc >> rb), lm, (uint32_t)(kc & ((1ull << rb) - 1ull)));
                         }
                     }
-                    if (d < 2u && P.prune) ok = false;                       // seen once in its only step: frequency 1 for ever, never chosen, not kept
+                    if (d < 2u && prune) ok = false;                       // seen once in its only step: frequency 1 for ever, never chosen, not kept
                     kk[u] = k; dd[u] = d; lv[u] = ok;
 #ifdef PLO_BIG_PROFILE
                     if (ok) wg_add(&sh.fl2, 1u);
@@ -1744,7 +1800,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
             if (tid == 0) { ncrptr[lm - n + 1u] = ncrptr[lm - n] + naff; clen[lm] = naff; sh.part[0] = 0; }      // (the row search wrote the rows)
         }
         BSYNC();
-        if (!P.unit) {
+        if (!PW(unit)) {
             const uint32_t rho = swap ? sh.invr : r, asgs = babs(rho, p);
             if (!babsone(asgs, p)) {
                 const uint32_t nm = sh.nmult; bool hit = false;
@@ -1752,7 +1808,7 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
                 if (hit) sh.part[0] = 1u;
                 BSYNC();
                 if (tid == 0 && !sh.part[0]) {
-                    if (nm >= P.multcap) wg_max(&sh.errflag, (uint32_t)BERR_MULT);
+                    if (nm >= PW(multcap)) wg_max(&sh.errflag, (uint32_t)BERR_MULT);
                     else { multc[nm] = l1; multv[nm] = asgs; sh.nmult = nm + 1u; ++sh.nbmul; }
                 }
             }
@@ -1786,22 +1842,23 @@ template <int MODE, bool DEFER, bool IDK> __device__ __forceinline__ uint64_t bi
 // walks, with one wave, only the columns that still hold two or more non +-1 entries
 // (after FactorOutColumns those have pairwise distinct |values|, so they are few and
 // short).  DESIGN.md 2.2 has the stamps of every pass before and after.
-__device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *ws, BigShared &sh, uint32_t *scratch, uint32_t *errw)
+template <class O> __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *ws, BigShared &sh, uint32_t *scratch, uint32_t *errw)
 {
     // (the {value, inverse} table is read from global memory here: `scratch` may overlap its LDS copy)
     const uint32_t tid = threadIdx.x, nth = blockDim.x, lane = tid & 63u, wave = tid >> 6, nwaves = nth >> 6;
     uint64_t *tab   = (uint64_t *)(ws + P.o_tab);
-    uint32_t *col   = (uint32_t *)(ws + P.o_col), *val = (uint32_t *)(ws + P.o_val), *inv = (uint32_t *)(ws + P.o_inv);
-    uint32_t *len   = (uint32_t *)(ws + P.o_len);
-    uint32_t *multc = (uint32_t *)(ws + P.o_multc), *multv = (uint32_t *)(ws + P.o_multv);
-    uint32_t *tcnt  = (uint32_t *)(ws + P.o_tcnt), *tptr2 = (uint32_t *)(ws + P.o_tptr2), *tlist = (uint32_t *)(ws + P.o_tlist), *cols2 = (uint32_t *)(ws + P.o_cols2);
-    const uint32_t p = P.p, rb = P.rb, m = P.m, ncols0 = sh.ncols, mers = P.mers;
-    const uint64_t mu = P.mu;
+    typedef WsArr<uint32_t, O> A32;
+    const A32 col{ws, ws_off<O>(P.o_col)}, val{ws, ws_off<O>(P.o_val)}, inv{ws, ws_off<O>(P.o_inv)};
+    const A32 len{ws, ws_off<O>(P.o_len)};
+    const A32 multc{ws, ws_off<O>(P.o_multc)}, multv{ws, ws_off<O>(P.o_multv)};
+    const A32 tcnt{ws, ws_off<O>(P.o_tcnt)}, tptr2{ws, ws_off<O>(P.o_tptr2)}, tlist{ws, ws_off<O>(P.o_tlist)}, cols2{ws, ws_off<O>(P.o_cols2)};
+    const uint32_t p = PW(p), rb = PW(rb), m = PW(m), ncols0 = sh.ncols, mers = PW(mers);       // (the plan's words are read here, from the kernel-argument segment: plan_word)
+    const uint64_t mu = PW(mu); const uint32_t *const rs = PW(rs); const uint2 *const vt = PW(vt);
 
     unsigned long long tpg0 = wall_clock64();
     if (tid == 0) { sh.acc0 = 0; sh.acc1 = 0; sh.errflag = 0; sh.naff = 0; for (int q = 0; q < 7; ++q) sh.tpg[q] = 0; }
     BSYNC();
-    if (P.unit) {                                                      // all +-1: len-1 additions per row (:576)
+    if (PW(unit)) {                                                      // all +-1: len-1 additions per row (:576)
         uint32_t acc = 0;
         for (uint32_t i = tid; i < m; i += nth) { uint32_t L = len[i]; acc += L > 1u ? L - 1u : 0u; }
         if (acc) wg_add(&sh.acc0, acc);
@@ -1816,7 +1873,7 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
         BSYNC();
     }
     const uint32_t live = sh.acc0 + sh.nmult;
-    uint32_t hb = 6; while ((1ull << hb) < 4ull * live + 64ull && hb < P.hbits) ++hb;
+    uint32_t hb = 6; while ((1ull << hb) < 4ull * live + 64ull && hb < PW(hbits)) ++hb;
     if ((1ull << hb) < 2ull * live + 16ull) { if (tid == 0) { atomicMax(errw, (uint32_t)BERR_PGEN); sh.errflag = BERR_PGEN; } BSYNC(); return 0; }
     {   // 16-byte stores, two slots each (the table is 256-byte aligned and holds at least 64 slots)
         uint4 *t4 = (uint4 *)tab; const uint4 E = make_uint4((uint32_t)PLO_GEMPTY, (uint32_t)(PLO_GEMPTY >> 32), (uint32_t)PLO_GEMPTY, (uint32_t)(PLO_GEMPTY >> 32));
@@ -1835,11 +1892,11 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
     // ProgramGen creates values (FactorOutRows sums, Triangle quotients): expand the packed rows to col / val / inv,
     // and count A1 the occurrences of (j,e) on the way
     {
-        const uint32_t *ent = (const uint32_t *)(ws + P.o_ent);
+        const A32 ent{ws, ws_off<O>(P.o_ent)};
         for (uint32_t i = tid; i < m; i += nth) {
-            const uint32_t base = P.rs[i], L = len[i];
+            const uint32_t base = rs[i], L = len[i];
             for (uint32_t z = 0; z < L; ++z) {
-                const uint32_t w = ent[base + z], c = PLO_ECOL(w); const uint2 V = P.vt[PLO_EVI(w)];
+                const uint32_t w = ent[base + z], c = PLO_ECOL(w); const uint2 V = vt[PLO_EVI(w)];
                 col[base + z] = c; val[base + z] = V.x; inv[base + z] = V.y;
                 const uint32_t e = babs(V.x, p);
                 if (!babsone(e, p)) if (!gtab_add(tab, ((uint64_t)c << rb) | e, 1u, hb)) wg_max(&sh.errflag, (uint32_t)BERR_TABLE);
@@ -1868,11 +1925,11 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
     // A3 repeated entries become +-1 entries of a fresh column (:358-368), B FactorOutRows (:375-420) and the count of the
     // non +-1 entries per column that Triangle starts from: all three look at one row only, in row order.  B is quadratic in
     // the row's length: rows of more than 64 entries are listed and left to whole waves below.
-    uint32_t *longrow = (uint32_t *)(ws + P.o_aff);                       // (the CSE phase's list of affected rows, idle by now: 8 m words)
+    const A32 longrow{ws, ws_off<O>(P.o_aff)};                       // (the CSE phase's list of affected rows, idle by now: 8 m words)
     {
         uint32_t addacc = 0;
         for (uint32_t i = tid; i < m; i += nth) {
-            const uint32_t base = P.rs[i], L = len[i];
+            const uint32_t base = rs[i], L = len[i];
             if (L > 64u) { longrow[wg_add(&sh.naff, 1u)] = i; continue; }
             bool any = false;
             for (uint32_t z = 0; z < L; ++z) {
@@ -1911,10 +1968,10 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
     PLO_BIG_FENCE(); BSYNC();
     {   // the long rows, one wave each: |v| values of the row in per-wave LDS scratch
         const uint32_t nlong = sh.naff;
-        uint32_t *sc = scratch + (size_t)wave * P.scr_stride;             // per-wave scratch, stride = longest input row
+        uint32_t *sc = scratch + (size_t)wave * PW(scr_stride);             // per-wave scratch, stride = longest input row
         uint32_t addacc = 0;
         for (uint32_t li = wave; li < nlong; li += nwaves) {
-            const uint32_t i = longrow[li], base = P.rs[i], L = len[i];
+            const uint32_t i = longrow[li], base = rs[i], L = len[i];
             bool any = false;
             for (uint32_t z = lane; z < L; z += 64u) {
                 const uint32_t v = val[base + z]; uint32_t e = babs(v, p);
@@ -1976,7 +2033,7 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
     if (nc2) {
         // fill the row lists, then sort each list
         for (uint32_t i = tid; i < m; i += nth) {
-            const uint32_t base = P.rs[i], L = len[i];
+            const uint32_t base = rs[i], L = len[i];
             for (uint32_t z = 0; z < L; ++z) {
                 const uint32_t c = col[base + z];
                 if (c == PLO_BFRESH || babsone(val[base + z], p)) continue;
@@ -1986,7 +2043,7 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
         }
         PLO_BIG_FENCE(); BSYNC();
         for (uint32_t x = tid; x < nc2; x += nth) {                         // insertion sort, lists are short
-            uint32_t *l = tlist + tptr2[x]; const uint32_t k = tptr2[x + 1] - tptr2[x];
+            const A32 l = tlist + tptr2[x]; const uint32_t k = tptr2[x + 1] - tptr2[x];
             for (uint32_t u = 1; u < k; ++u) { uint32_t t = l[u], w = u; while (w > 0 && l[w - 1] > t) { l[w] = l[w - 1]; --w; } l[w] = t; }
         }
         PLO_BIG_FENCE(); BSYNC();
@@ -2009,7 +2066,7 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
                     for (uint32_t r = 0; r < R; ++r) {
                         vj[r] = 0; ivj[r] = 0; bool mine = false;
                         if (row[r] != 0xFFFFFFFFu) {
-                            const uint32_t base = P.rs[row[r]], L = len[row[r]];
+                            const uint32_t base = rs[row[r]], L = len[row[r]];
                             for (uint32_t z = 0; z < L; ++z) if (col[base + z] == j) { vj[r] = val[base + z]; ivj[r] = inv[base + z]; mine = !babsone(vj[r], p); break; }
                         }
                         NU[r] = __ballot(mine); total += (uint32_t)__popcll(NU[r]);
@@ -2038,7 +2095,7 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
                                 bool hit = false;
                                 if (cand) {
                                     const uint32_t quot = bmul(vj[r], iv1, p, mu, mers), nq = p - quot;
-                                    const uint32_t base = P.rs[row[r]], L = len[row[r]];
+                                    const uint32_t base = rs[row[r]], L = len[row[r]];
                                     for (uint32_t z = 0; z < L; ++z) {
                                         const uint32_t tv = val[base + z];
                                         if (col[base + z] != j && !babsone(tv, p) && (tv == quot || tv == nq)) { hit = true; break; }
@@ -2067,11 +2124,11 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
                     for (uint32_t r = 0; r < R; ++r) { if ((uint32_t)(it >> 6) == r) rit = (uint32_t)__shfl((int)row[r], it & 63); if ((uint32_t)(nx >> 6) == r) rnx = (uint32_t)__shfl((int)row[r], nx & 63); }
                     uint32_t addone = 0;
                     if (lane == 0) {
-                        {   const uint32_t base = P.rs[rit], L = len[rit];
+                        {   const uint32_t base = rs[rit], L = len[rit];
                             for (uint32_t z = 0; z < L; ++z) if (col[base + z] == j) { col[base + z] = PLO_BFRESH; val[base + z] = 1u; inv[base + z] = 1u; break; } }
                         const uint32_t quot = bmul(vn, iv1, p, mu, mers), iquot = bmul(ivn, v1, p, mu, mers);
                         const uint32_t eq = babs(quot, p), ieq = (quot == eq) ? iquot : p - iquot;
-                        const uint32_t base = P.rs[rnx], L = len[rnx];
+                        const uint32_t base = rs[rnx], L = len[rnx];
                         uint32_t w = 0, f = 1;
                         for (uint32_t z = 0; z < L; ++z) {
                             const uint32_t cz = col[base + z], tv = val[base + z], ti = inv[base + z];
@@ -2096,7 +2153,7 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
     {
         uint32_t addacc = 0, mulacc = 0;
         for (uint32_t i = tid; i < m; i += nth) {
-            const uint32_t base = P.rs[i], L = len[i];
+            const uint32_t base = rs[i], L = len[i];
             if (L > 1u) addacc += L - 1u;
             for (uint32_t z = 0; z < L; ++z) {
                 const uint32_t e = babs(val[base + z], p), c = col[base + z];
@@ -2116,13 +2173,19 @@ __device__ __forceinline__ uint64_t big_program_gen(const BigPlan &P, uint8_t *w
 }
 
 // IDK: mode 2 with ratio IDENTIFIERS in the pair keys (big_candidate): moduli too wide for a residue in the 48-bit key
-template <int MODE, bool DEFER, bool IDK = false> __global__ __launch_bounds__(PLO_BIG_THREADS, 4) void cse_big_kernel(BigPlan P, BigJob J)
+// INVARIANT: the plan is this kernel's FIRST by-value argument, i.e. it lies at offset 0 of the kernel-argument segment -- plan_word() reads
+// its words from there, while the helpers' `P` (the same plan: they are only ever handed this kernel's argument) supplies the offsets they
+// take at their heads.  A kernel that put anything in front of the plan, or a helper called with another plan, would read the wrong words.
+// WIDE: 64-bit offsets into the workspace slice (BigPlan::wide: the slice's front region passes 4 GiB, or the test knob asks for it)
+template <int MODE, bool DEFER, bool IDK = false, bool WIDE = false> __global__ __launch_bounds__(PLO_BIG_THREADS, 4) void cse_big_kernel(BigPlan P, BigJob J)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t bigdyn[];                 // hist[maxf0+1], the value / ratio tables, then per-wave scratch (nwaves * stride)
+    extern __shared__ __attribute__((aligned(16))) uint32_t bigdyn[];                 // modes 0/1: hist[maxf0+1], the value table, (Bloom filter,) scratch; mode 2: the ratio-identifier table FIRST, then hist, ratios, inverse identifiers, (slot list | Bloom filter,) scratch (nwaves * stride)
     __shared__ BigShared sh;
     __shared__ unsigned long long cur;
-    uint32_t *hist = bigdyn;
-    uint32_t *nextw = bigdyn + ((P.maxf0 + 2u) & ~1u);
+    // Mode 2: the ratio-identifier table comes first, so that its address is a constant of the kernel (an offset field of the sweep's
+    // ds_read, not a scalar register); the sizes and their sum are as before.
+    uint32_t *hist = MODE == 2 ? bigdyn + PLO_RSTRIDE * PLO_RSTRIDE / 2u : bigdyn;
+    uint32_t *nextw = hist + ((P.maxf0 + 2u) & ~1u);
     BigTabs TB{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if constexpr (MODE == 1) {                                     // {value, inverse} per value index
         uint2 *vts = (uint2 *)nextw; nextw += 2u * ((P.nv + 1u) & ~1u);
@@ -2131,7 +2194,7 @@ template <int MODE, bool DEFER, bool IDK = false> __global__ __launch_bounds__(P
     }
     if constexpr (MODE == 2) {                                     // ratio identifiers, ratios, inverse identifiers
         uint32_t *rv = nextw; nextw += (P.nr + 1u) & ~1u;
-        uint16_t *rt = (uint16_t *)nextw; nextw += PLO_RSTRIDE * PLO_RSTRIDE / 2u;
+        uint16_t *rt = (uint16_t *)bigdyn;
         uint16_t *iv = (uint16_t *)nextw; nextw += (P.nr + 3u) / 4u * 2u;
         for (uint32_t k = threadIdx.x; k < P.nr; k += blockDim.x) { rv[k] = P.rval[k]; iv[k] = P.invid[k]; }
         for (uint32_t k = threadIdx.x; k < PLO_RSTRIDE * PLO_RSTRIDE; k += blockDim.x) rt[k] = P.rtid[k];
@@ -2152,11 +2215,12 @@ template <int MODE, bool DEFER, bool IDK = false> __global__ __launch_bounds__(P
         if (c >= J.ncand) break;
         const uint64_t seed = J.seeds ? J.seeds[c] : J.seed0 + c;
         const unsigned long long tk0 = wall_clock64();
-        uint64_t ok = big_candidate<MODE, DEFER, IDK>(P, ws, seed, sh, hist, agg, P.aggbits, TB, J.err);
+        typedef typename std::conditional<WIDE, uint64_t, uint32_t>::type O;
+        uint64_t ok = big_candidate<MODE, DEFER, IDK, O>(P, ws, seed, sh, hist, agg, sreg(P.aggbits), TB, J.err);
         uint64_t res = 0;
         __syncthreads();
         const unsigned long long tk1 = wall_clock64();
-        if (ok) res = big_program_gen(P, ws, sh, scratch, J.err);
+        if (ok) res = big_program_gen<O>(P, ws, sh, scratch, J.err);
         __syncthreads();
         const unsigned long long tk2 = wall_clock64();
         if (sh.errflag) ok = 0;
