@@ -332,6 +332,7 @@ int  plo_lin_search_multi(const plo_qcsr_t *A, uint64_t seed0, uint64_t nseeds, 
 #define PLO_ORBIT_BASE_SEED 0xFFFFFFFFFFFFFFFFull     /* U = V = W = identity: the input itself */
 #define PLO_ORBIT_DENSITY   0                          /* -s */
 #define PLO_ORBIT_CANONICAL 2                          /* -c */
+#define PLO_ORBIT_CSE       1                          /* -z: operations of the best programs found, see below */
 #define PLO_ORBIT_ACT_TRIANGULAR  0                    /* signed permutation times one triangle (the default) */
 #define PLO_ORBIT_ACT_PLUQ        1                    /* a product of two triangles */
 #define PLO_ORBIT_ACT_HOUSEHOLDER 2                    /* an orthogonal reflection, or a signed permutation */
@@ -354,6 +355,27 @@ int  plo_orbit_search_multi(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
                             uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats);
 int  plo_orbit_search_multi_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action,
                                 uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats);
+
+/* PLO_ORBIT_CSE (`-z`, reference src/orbiter.cpp:172-209): over Z_p, p an odd prime below 2^31, the transformed triple (Lj, Rg, hP)
+ * is the one the density measure counts (entries that vanish modulo p dropped; hP is mn x r) and
+ *   cost = c(Lj) + c(Rg) + c(hP),   c(M) = min(naive(M), min over j < sub of ops_j(M)),
+ * naive(M) = sum over the rows of max(len - 1, 0) + the entries that are not +-1 (naiveOps), ops_j(M) = adds + muls of
+ * Optimizer(M) with the stream of seed cse_seed0 + j: the numbers plo_cse_cost_many returns for M.  A matrix without entries
+ * costs 0.  nnz, nno, the order (cost, nnz, nno, seed) and the base seed are as above; the inner seeds are the same for every
+ * candidate and part.  The plans of plo_orbit_plan_create_cse are served by plo_orbit_cost_many, plo_orbit_search and
+ * plo_orbit_plan_destroy; plo_orbit_plan_create_q/_act refuse the measure (PLO_E_ARG: they carry no sub).
+ * PLO_E_ARG: modulus 0, even, composite or 2^31 and more, sub outside 1 .. 65536.  PLO_E_CAPACITY: r, mn, mk or kn above 64, a
+ * pair key above 51 bits, an op-count bound above 16 bits, a pair table above 65536 slots, an image that does not fit LDS with
+ * one wave.  The images are sized from a sizing launch over a sample of candidates; a candidate that outgrows them makes the
+ * launch repeat with larger ones (counted in plo_orbit_plan_info). */
+int  plo_orbit_plan_create_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int action,
+                               uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan);
+int  plo_orbit_search_multi_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int action, uint32_t sub, uint64_t cse_seed0,
+                                uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats);
+/* out[0] waves per workgroup, out[1] LDS bytes of a workgroup; of a PLO_ORBIT_CSE plan (0 otherwise): out[2..4] pair-table slots of
+ * the images of Lj, Rg, hP, out[5] the largest entry bound of the three, out[6] launches repeated for a full table so far, out[7] 1
+ * when a wave keeps a copy of the whole image between the sub runs, 0 when it keeps the entries and makes the rest again */
+int  plo_orbit_plan_info(plo_orbit_plan_t *plan, uint32_t out[8]);
 
 /* ---- Row-dependency enumeration: the search of the reference's `dependency` (src/dependency.cpp:74-101, 158-165).  M (m x n) as
  * rational CSR, `ncoef` coefficients cnum[v]/cden[v] (the caller's FCoeffs, in order), `level` the largest number of rows in a

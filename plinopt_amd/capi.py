@@ -26,6 +26,7 @@ EXPORTS = [
     "plo_tril_plan_create", "plo_tril_plan_create_x", "plo_tril_plan_create_q", "plo_tril_plan_destroy", "plo_tril_cost_many", "plo_tril_search",
     "plo_lin_plan_create_q", "plo_lin_plan_destroy", "plo_lin_cost_many", "plo_lin_search", "plo_lin_search_multi",
     "plo_orbit_plan_create_q", "plo_orbit_plan_create_act", "plo_orbit_plan_destroy", "plo_orbit_cost_many", "plo_orbit_search", "plo_orbit_search_multi", "plo_orbit_search_multi_act",
+    "plo_orbit_plan_create_cse", "plo_orbit_search_multi_cse", "plo_orbit_plan_info",
     "plo_dep_plan_create_q", "plo_dep_plan_destroy", "plo_dep_search",
     "plo_pack_cost",
 ]
@@ -178,6 +179,10 @@ def lib():
                                            ctypes.POINTER(LinBest), ctypes.POINTER(Stats)]
         L.plo_orbit_plan_create_q.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
         L.plo_orbit_plan_create_act.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+        L.plo_orbit_plan_create_cse.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
+        L.plo_orbit_search_multi_cse.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(OrbitBest), ctypes.POINTER(Stats)]
+        L.plo_orbit_plan_info.argtypes = [ctypes.c_void_p, u32p]
         L.plo_orbit_plan_destroy.argtypes = [ctypes.c_void_p]
         L.plo_orbit_plan_destroy.restype = None
         L.plo_orbit_cost_many.argtypes = [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_uint64, u32p, ctypes.POINTER(Stats)]

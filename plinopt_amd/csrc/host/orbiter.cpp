@@ -1,17 +1,20 @@
 // ==========================================================================
 // bin/orbiter -- the De Groote orbit search of a matrix-multiplication triple (reference src/orbiter.cpp):
-//   orbiter [-b bits] [-m|-q mod] [-r r e s] [-s|-c] [-O loops] [--seed s] [--gpu 0|1|N] [--action a] L.sms R.sms P.sms
+//   orbiter [-b bits] [-m|-q mod] [-r r e s] [-s|-c|-z] [--sub n] [-O loops] [--seed s] [--gpu 0|1|N] [--action a] L.sms R.sms P.sms
 // Searches the candidates (U, V, W) s .. s+O-1 (plo_orbit_*, include/plinopt_hip.h) for an equivalent triple with a smaller
 // (cost, nnz, nno); when the best one improves on the input, writes <L>.nnz.sms, <R>.nnz.sms, <P>.nnz.sms next to the inputs.
 // clog: the reference's '#' lines (Init. ops, Search(N), Rdcd. opt) and the exact matrix-multiplication checks of the input
 // (printed, then ignored, as the reference does) and of the winner; stdout: one line `winner <cost> <nnz> <nno> <seed|base>`.
-// Fields: Q (default), or Z_mod with -m/-q/-r (factors 2 removed from the modulus, 1 becomes 2; the measure is then density).
+// Fields: Q (default), or Z_mod with -m/-q/-r (factors 2 removed from the modulus, 1 becomes 2; the measure is then density, or -z).
+// -z (reference :172-209, PLO_ORBIT_CSE) scores a candidate by the operations of the best programs CSEOptimiser finds for its three
+// matrices: min(naiveOps, the best of `sub` Optimizer runs) per matrix, sub = loops >> 4 above 16 loops, else 1 (:257), or --sub n;
+// the Optimizer streams are seeds 0 .. sub-1 for every candidate.  It needs a prime modulus (-q 2147483629 stands for Q).
 // The restarts run on the GPU through plo_orbit_search[_multi] of libplinopt_hip.so; --gpu 0, or an input the device refuses
 // (a modulus of 2^31 or more, a Q input outside its int64 bound, sizes beyond its limits), uses the host loop (OpenMP) and
 // says so.  -b is accepted for the reference's command lines: the checks here are exact.
 // --action triangular|pluq|householder chooses how U, V and W are drawn (PLO_ORBIT_ACT_*; the reference's compile-time
 // ACTION_FULL_PLUQ and ACTION_HOUSEHOLDER, src/orbiter.cpp:77-123), for the search, --costs and --candidate alike.
-// Refused with status 2: -z over Q, -P/-I, shapes that are not mk, kn, mn, a denominator that is no unit modulo the modulus, a
+// Refused with status 2: -z over Q or modulo a composite number, -P/-I, shapes that are not mk, kn, mn, a denominator that is no unit modulo the modulus, a
 // modulus above 2^63.  Testing aids: --costs prints `cost nnz nno` of the base candidate, then of seeds s .. s+O-1 (host);
 // --candidate s|base DIR writes the three matrices of one candidate to DIR/{L,R,P}.sms.
 // ==========================================================================
@@ -28,11 +31,13 @@ struct HipOrbit {
     PLO_SYM(init, plo_init); PLO_SYM(last_error, plo_last_error);
     PLO_SYM(create, plo_orbit_plan_create_act); PLO_SYM(destroy, plo_orbit_plan_destroy);
     PLO_SYM(search, plo_orbit_search); PLO_SYM(search_multi, plo_orbit_search_multi_act);
+    PLO_SYM(create_cse, plo_orbit_plan_create_cse); PLO_SYM(search_multi_cse, plo_orbit_search_multi_cse);
 };
 
 struct Opts {
     size_t loops = 100; uint64_t seed0 = 0; int gpu = 1; int measure = ORBIT_DENSITY; int action = ORBIT_ACT_TRIANGULAR; bool cse = false;
     unsigned __int128 modulus = 0; bool costs = false, cand = false; uint64_t cseed = 0; std::string cdir;
+    size_t sub = 0;                                                                       // --sub; 0: the reference's loops >> 4
 };
 
 std::string nnz_name(const std::string &f) { return std::filesystem::path(f).replace_extension(".nnz.sms").string(); }
@@ -48,7 +53,7 @@ template <class F> int mm_report(const F &f, const OrbitTriple<F> &T) {
     try { ok = orbit_mm_check(f, T); } catch (const std::exception &e) { why = e.what(); }
     const std::string shape = std::to_string(T.m) + 'x' + std::to_string(T.k) + 'x' + std::to_string(T.n);
     if (ok) {
-        OrbitCount c = orbit_candidate(f, T, ORBIT_BASE, ORBIT_DENSITY, ORBIT_ACT_TRIANGULAR);
+        OrbitCount c = orbit_candidate(f, T, ORBIT_BASE, ORBIT_DENSITY, ORBIT_ACT_TRIANGULAR, OrbitCse());
         std::clog << "# \033[1;32mSUCCESS: correct " << shape << " (" << c.nnz << ',' << c.nno << ") Matrix-Multiplication over " << f.name() << " \033[0m" << std::endl;
         return 0;
     }
@@ -60,22 +65,23 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
                                  const std::vector<std::string> &files) {
     OrbitTriple<F> T;
     T.L = rebind(QL, f); T.R = rebind(QR, f); T.PT = rebind(transpose(QP), f); T.m = m; T.k = k; T.n = n;
-    const int measure = modulus ? ORBIT_DENSITY : o.measure;
+    const int measure = o.cse ? ORBIT_CSE : modulus ? ORBIT_DENSITY : o.measure;
+    const OrbitCse z{o.sub ? o.sub : (o.loops > 16 ? o.loops >> 4 : 1), 0};                // :257
     if (o.costs) {
-        auto line = [&](uint64_t s) { const OrbitCount c = orbit_candidate(f, T, s, measure, o.action); std::cout << c.cost << ' ' << c.nnz << ' ' << c.nno << '\n'; };
+        auto line = [&](uint64_t s) { const OrbitCount c = orbit_candidate(f, T, s, measure, o.action, z); std::cout << c.cost << ' ' << c.nnz << ' ' << c.nno << '\n'; };
         line(ORBIT_BASE);
         for (uint64_t j = 0; j < o.loops; ++j) line(o.seed0 + j);
         return 0;
     }
     if (o.cand) {
-        OrbitTriple<F> C; const OrbitCount c = orbit_candidate(f, T, o.cseed, measure, o.action, &C);
+        OrbitTriple<F> C; const OrbitCount c = orbit_candidate(f, T, o.cseed, measure, o.action, &C, z);
         std::filesystem::create_directories(o.cdir);
         write_triple(f, C, o.cdir + "/L.sms", o.cdir + "/R.sms", o.cdir + "/P.sms", modulus ? 'M' : 'R');
         std::clog << "# candidate " << (o.cseed == ORBIT_BASE ? std::string("base") : std::to_string(o.cseed)) << ": " << c.cost << ' ' << c.nnz << ' ' << c.nno << std::endl;
         return 0;
     }
     const int input_bad = mm_report(f, T);                                               // :263, printed then ignored
-    const OrbitCount init = orbit_candidate(f, T, ORBIT_BASE, measure, o.action);
+    const OrbitCount init = orbit_candidate(f, T, ORBIT_BASE, measure, o.action, z);
     std::clog << "# Init. ops: " << init.cost << ", (" << init.nnz << ',' << init.nno << ')' << std::endl;
     const auto t0 = std::chrono::steady_clock::now();
     using Key = std::tuple<size_t, size_t, size_t, uint64_t>;                             // (cost, nnz, nno, seed)
@@ -86,6 +92,7 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
         if (o.gpu) {
             const QCsr cl = qcsr(QL), cr = qcsr(QR), cp = qcsr(QP);
             refused = cl.wide || cr.wide || cp.wide; why = "a coefficient wider than 64 bits";
+            if (!refused && o.cse && modulus >= (1ull << 31)) { refused = true; why = "-z modulo a prime of 2^31 or more"; }
             if (!refused) {
                 HipOrbit H;
                 if (!H.ok) { std::cerr << "# \033[1;31mERROR: libplinopt_hip.so cannot be loaded or lacks plo_orbit_search\033[0m\n"; return 2; }   // no silent fallback
@@ -94,11 +101,12 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
                 int rc;
                 if (o.gpu >= 2) {
                     std::vector<int> devs((size_t)o.gpu); for (int j = 0; j < o.gpu; ++j) devs[(size_t)j] = shard_device(j);
-                    rc = H.search_multi(&l, &r, &p, modulus, measure, o.action, o.seed0, o.loops, o.gpu, devs.data(), &b, &st);
+                    rc = o.cse ? H.search_multi_cse(&l, &r, &p, modulus, o.action, (uint32_t)z.sub, z.seed0, o.seed0, o.loops, o.gpu, devs.data(), &b, &st)
+                               : H.search_multi(&l, &r, &p, modulus, measure, o.action, o.seed0, o.loops, o.gpu, devs.data(), &b, &st);
                 } else {
                     rc = H.init(0);
                     plo_orbit_plan_t *plan = nullptr;
-                    if (rc == PLO_OK) rc = H.create(&l, &r, &p, modulus, measure, o.action, &plan);
+                    if (rc == PLO_OK) rc = o.cse ? H.create_cse(&l, &r, &p, modulus, o.action, (uint32_t)z.sub, z.seed0, &plan) : H.create(&l, &r, &p, modulus, measure, o.action, &plan);
                     // (a launch takes at most 2^31-1 candidates: longer runs go in pieces, minimum under the same order)
                     for (uint64_t done = 0; rc == PLO_OK && done < o.loops;) {
                         const uint64_t piece = std::min<uint64_t>(o.loops - done, (1ull << 31) - 1ull);
@@ -130,7 +138,7 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
                 #pragma omp for schedule(dynamic, 16)
                 for (long long j = 0; j < (long long)o.loops; ++j) {
                     try {
-                        const OrbitCount c = orbit_candidate(f, T, o.seed0 + (uint64_t)j, measure, o.action);
+                        const OrbitCount c = orbit_candidate(f, T, o.seed0 + (uint64_t)j, measure, o.action, z);
                         tb = std::min(tb, Key{c.cost, c.nnz, c.nno, o.seed0 + (uint64_t)j});
                     } catch (const std::exception &e) {
                         #pragma omp critical
@@ -151,7 +159,7 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
     if (improved) {
         const uint64_t seed = std::get<3>(best);
         OrbitTriple<F> W;
-        const OrbitCount rc = orbit_candidate(f, T, seed, measure, o.action, &W);
+        const OrbitCount rc = orbit_candidate(f, T, seed, measure, o.action, &W, z);
         if (!(rc == bc)) {
             std::cerr << "# \033[1;31mERROR: replay of seed " << seed << " gives " << rc.cost << ' ' << rc.nnz << ' ' << rc.nno << ", search said " << bc.cost << ' ' << bc.nnz << ' ' << bc.nno << "\033[0m\n";
             return 3;
@@ -166,8 +174,27 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
     }
     std::clog << "# " << o.loops << " restarts on " << (on_gpu ? "GPU" : "host") << " in " << dt << " s";
     if (on_gpu) std::clog << " (kernel " << kms << " ms)";
+    if (o.cse) std::clog << ", " << o.loops * 3 * z.sub << " Optimizer runs (sub " << z.sub << ")";
     std::clog << std::endl;
     return 0;
+}
+
+// deterministic Miller-Rabin below 2^64 (the first twelve primes as bases)
+bool is_prime(uint64_t n) {
+    if (n < 2) return false;
+    static const uint64_t B[12] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37};
+    for (uint64_t q : B) { if (n == q) return true; if (n % q == 0) return false; }
+    uint64_t d = n - 1; int s = 0; while (!(d & 1)) { d >>= 1; ++s; }
+    auto mul = [&](uint64_t a, uint64_t b) { return (uint64_t)((unsigned __int128)a * b % n); };
+    for (uint64_t a : B) {
+        uint64_t x = 1, b = a % n;
+        for (uint64_t e = d; e; e >>= 1) { if (e & 1) x = mul(x, b); b = mul(b, b); }
+        if (x == 1 || x == n - 1) continue;
+        bool comp = true;
+        for (int i = 1; i < s && comp; ++i) { x = mul(x, x); if (x == n - 1) comp = false; }
+        if (comp) return false;
+    }
+    return true;
 }
 
 int refuse(const std::string &why) { std::cerr << "# \033[1;31mERROR: " << why << "\033[0m\n"; return 2; }
@@ -179,11 +206,13 @@ QMat read_file(const std::string &f) {
 }
 
 int usage(const char *prg, const Opts &o) {
-    std::clog << "Usage: " << prg << " [-b #] [-m|-q #] [-r # # #] [-s|-c] [-O #] [--seed s] [--gpu 0|1|N] [--action a] L.sms R.sms P.sms\n"
+    std::clog << "Usage: " << prg << " [-b #] [-m|-q #] [-r # # #] [-s|-c|-z] [--sub #] [-O #] [--seed s] [--gpu 0|1|N] [--action a] L.sms R.sms P.sms\n"
               << "  [-b b]: accepted (the matrix-multiplication checks are exact)\n"
               << "  [-m/-q m]: search modulo m without its factors 2 (default Q)\n"
               << "  [-r r e s]: search modulo (r^e-s) without its factors 2\n"
               << "  [-s|-c]: search sparser|canonical (default sparser; always sparser modulo a number)\n"
+              << "  [-z]: search faster: the operations of the best programs found (needs a prime modulus; -q 2147483629 stands for Q)\n"
+              << "  [--sub n]: Optimizer runs per matrix with -z (default loops/16, at least 1)\n"
               << "  [-O #]: randomized search with that many loops (default " << o.loops << " loops)\n"
               << "  [--seed s]: candidates s .. s+O-1 (default 0); [--gpu 0|1|N]: host loop, one GPU, N GPU shards (default 1)\n"
               << "  [--action triangular|pluq|householder]: how U, V and W are drawn (default triangular)\n"
@@ -222,6 +251,7 @@ int main(int argc, char **argv) {
             else if (a == "-s") { o.measure = ORBIT_DENSITY; o.cse = false; }
             else if (a == "-c") { o.measure = ORBIT_CANONICAL; o.cse = false; }
             else if (a == "-z") o.cse = true;
+            else if (a == "--sub") { need(1); o.sub = (size_t)strtoull(argv[++i], nullptr, 10); if (o.sub == 0 || o.sub > 65536) return refuse("--sub needs a number in 1 .. 65536"); }
             else if (a == "--seed") { need(1); o.seed0 = strtoull(argv[++i], nullptr, 10); }
             else if (a == "--gpu") { need(1); o.gpu = atoi(argv[++i]); }
             else if (a == "--action") {
@@ -244,6 +274,7 @@ int main(int argc, char **argv) {
         modulus = (uint64_t)o.modulus;
     }
     if (o.cse && !modulus) return refuse("-z (CSE counts per candidate) is not supported over Q");
+    if (o.cse && !is_prime(modulus)) return refuse("-z needs a prime modulus, " + std::to_string(modulus) + " is composite");
     try {
         const QMat L = read_file(files[0]), R = read_file(files[1]), P = read_file(files[2]);
         size_t m = 0, k = 0, n = 0;

@@ -14,7 +14,9 @@
 
 namespace plo {
 
-enum { ORBIT_DENSITY = 0, ORBIT_CANONICAL = 2 };
+enum { ORBIT_DENSITY = 0, ORBIT_CSE = 1, ORBIT_CANONICAL = 2 };
+// ORBIT_CSE (`-z`): every part is scored by min(naiveOps, the best of `sub` Optimizer runs with the streams seed0 .. seed0 + sub - 1)
+struct OrbitCse { size_t sub = 1; uint64_t seed0 = 0; };
 enum { ORBIT_ACT_TRIANGULAR = 0, ORBIT_ACT_PLUQ = 1, ORBIT_ACT_HOUSEHOLDER = 2 };
 constexpr uint64_t ORBIT_BASE = ~0ull;
 
@@ -172,9 +174,30 @@ template <class F> void orbit_part(const F &f, const SparseMat<typename F::Elt> 
     }
 }
 
-// counts of candidate `seed` (cost = nnz, or L.m + R.m + P.n - the rows with one non-zero for ORBIT_CANONICAL); the three
-// transformed matrices (P transposed back) when out is given
-template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &T, uint64_t seed, int measure, int action, OrbitTriple<F> *out = nullptr) {
+// c(M) of include/plinopt_hip.h (PLO_ORBIT_CSE): what CSEOptimiser leaves in nbops under the default cmpOpCount, summed
+// (reference src/orbiter.cpp:183-189)
+template <class F> size_t orbit_cse_cost(const F &f, const SparseMat<typename F::Elt> &M, const OrbitCse &z) {
+    const auto nv = naive_ops(f, M);
+    size_t best = nv.first + nv.second;
+    if (best == 0) return 0;
+    std::ostream sink(nullptr);                                                          // (no buffer: the program text goes nowhere)
+    for (size_t j = 0; j < z.sub; ++j) {
+        Replay<F> R(f, M, z.seed0 + j, sink);
+        const auto ops = R.optimizer();
+        best = std::min(best, ops.first + ops.second);
+    }
+    return best;
+}
+
+template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &T, uint64_t seed, int measure, int action, OrbitTriple<F> *out = nullptr, const OrbitCse &z = OrbitCse());
+// the same without the matrices
+template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &T, uint64_t seed, int measure, int action, const OrbitCse &z) { return orbit_candidate(f, T, seed, measure, action, (OrbitTriple<F> *)nullptr, z); }
+
+// counts of candidate `seed` (cost = nnz, or L.m + R.m + P.n - the rows with one non-zero for ORBIT_CANONICAL, or the operations
+// of the best programs found for ORBIT_CSE); the three transformed matrices (P transposed back) when out is given
+template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &T, uint64_t seed, int measure, int action, OrbitTriple<F> *out, const OrbitCse &z) {
+    OrbitTriple<F> mine;
+    if (measure == ORBIT_CSE && !out) out = &mine;
     const OrbitUVW c = orbit_uvw(f, T.m, T.k, T.n, seed, action);
     const size_t m = T.m, k = T.k, n = T.n;
     auto tr = [](const std::vector<int64_t> &M, size_t s) { std::vector<int64_t> R(s * s); for (size_t i = 0; i < s; ++i) for (size_t j = 0; j < s; ++j) R[j * s + i] = M[i * s + j]; return R; };
@@ -183,6 +206,7 @@ template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &
     orbit_part(f, T.R, n, tr(c.V.Mi, k), c.V.den, k, c.W.M, c.W.den, n, r, canon, out ? &out->R : nullptr);           // V^-1 Y W: A[b][p] = V^-1[p][b]
     orbit_part(f, T.PT, n, tr(c.U.M, m), c.U.den, m, tr(c.W.Mi, n), c.W.den, n, r, canon, out ? &out->PT : nullptr);  // U Z W^-T: A[a][p] = U[p][a], B[c][q] = W^-1[q][c]
     r.cost = measure == ORBIT_CANONICAL ? T.L.rowdim() + T.R.rowdim() + T.PT.rowdim() - canon : r.nnz;
+    if (measure == ORBIT_CSE) r.cost = orbit_cse_cost(f, out->L, z) + orbit_cse_cost(f, out->R, z) + orbit_cse_cost(f, transpose(out->PT), z);
     if (out) { out->m = m; out->k = k; out->n = n; }
     return r;
 }

@@ -15,6 +15,7 @@
 #include "plo_tril.hip"
 #include "plo_lin.hip"
 #include "plo_orbit.hip"
+#include "plo_orbit_cse.hip"
 #include "plo_dep.hip"
 #include "../../include/plinopt_hip.h"
 
@@ -2145,6 +2146,12 @@ struct plo_orbit_plan {
     uint32_t waves_per_wg = 4, lds_bytes = 0, blocks_per_cu = 1, grid_max = 1;
     uint64_t algo_bytes = 0;
     int action = PLO_ORBIT_ACT_TRIANGULAR;
+    // PLO_ORBIT_CSE (plo_orbit_cse.hip): the layouts, the sampled bounds they come from and how often they were outgrown
+    bool cse = false;
+    plo::OrbitCsePlan C{};
+    uint32_t *d_err = nullptr;
+    uint32_t cse_scale = 1, cse_relaunches = 0;        // tables: scale x the sampled size; launches repeated for a full table
+    uint32_t cse_ent[3] = {0, 0, 0}, cse_pairs[3] = {0, 0, 0};   // maxima over the sizing sample, per part
 };
 
 namespace {
@@ -2182,12 +2189,132 @@ orbit_fn_t orbit_fn(bool mod, int action) {
     }
 }
 
+// ---- PLO_ORBIT_CSE
+using orbit_cse_fn_t = void (*)(plo::OrbitPlan, plo::OrbitJob, plo::OrbitCsePlan, uint32_t *);
+orbit_cse_fn_t orbit_cse_fn(int action, bool size) {
+    switch (action) {
+    case PLO_ORBIT_ACT_PLUQ: return size ? plo::orbit_cse_kernel<1, true> : plo::orbit_cse_kernel<1, false>;
+    case PLO_ORBIT_ACT_HOUSEHOLDER: return size ? plo::orbit_cse_kernel<2, true> : plo::orbit_cse_kernel<2, false>;
+    default: return size ? plo::orbit_cse_kernel<0, true> : plo::orbit_cse_kernel<0, false>;
+    }
+}
+enum { ORBIT_AGAIN = 1 };            // orbit_launch: a table was full, the plan has larger ones now: launch again
+
+// deterministic Miller-Rabin below 2^32 (bases 2, 7, 61)
+bool is_prime32(uint64_t n) {
+    if (n < 2) return false;
+    for (uint64_t q : {2ull, 3ull, 5ull, 7ull, 61ull}) { if (n == q) return true; if (n % q == 0) return false; }
+    uint64_t d = n - 1; int s = 0; while (!(d & 1)) { d >>= 1; ++s; }
+    auto pw = [&](uint64_t b, uint64_t e) { uint64_t x = 1; b %= n; for (; e; e >>= 1) { if (e & 1) x = x * b % n; b = b * b % n; } return x; };
+    for (uint64_t a : {2ull, 7ull, 61ull}) {
+        uint64_t x = pw(a, d); if (x == 1 || x == n - 1) continue;
+        bool comp = true;
+        for (int i = 1; i < s && comp; ++i) { x = x * x % n; if (x == n - 1) comp = false; }
+        if (comp) return false;
+    }
+    return true;
+}
+
+// The three image layouts of a CSE plan from its sampled bounds and cse_scale, the wave's region, the waves per workgroup (the
+// count that puts most waves on a CU, as the other wave plans) and the per-wave words of the search.
+int orbit_cse_layout(plo_orbit_plan *pl)
+{
+    plo::OrbitPlan &Q = pl->P; plo::OrbitCsePlan &C = pl->C;
+    const uint32_t r = Q.r, mk = Q.m * Q.k, kn = Q.k * Q.n, mn = Q.m * Q.n, p = (uint32_t)Q.p;
+    const uint32_t rows[3] = {r, r, mn}, cols[3] = {mk, kn, r};
+    const auto cap0 = env_knob("PLO_ORBIT_CSE_CAP");          // test knob: the slots of the first tables (a full table repeats the launch with twice as many)
+    uint32_t region = 0, keep_all = 0, keep_ent = 0;
+    for (int i = 0; i < 3; ++i) {
+        const uint32_t hard = rows[i] * cols[i];
+        // entries: the sample + 60 % (what the kernel method's Dep images use), the hard bound once a launch has been repeated
+        const uint32_t ent = pl->cse_scale == 1 ? std::min<uint32_t>(hard, pl->cse_ent[i] + (uint32_t)((uint64_t)pl->cse_ent[i] * 60u / 100u) + 16u) : hard;
+        // table: 0.75 x the sampled pair instances (an upper bound of the distinct triples) x scale
+        uint32_t cap = 64;
+        if (cap0 && *cap0 >= 64) while (cap < (uint64_t)*cap0 * pl->cse_scale) cap <<= 1;
+        else while (cap < ((uint64_t)pl->cse_scale * pl->cse_pairs[i] * 3u) / 4u + 16u && cap < (1u << 17)) cap <<= 1;
+        if (cap > 65536u) return fail(PLO_E_CAPACITY, "CSE measure: a pair table of more than 65536 slots");
+        const uint64_t NC = (uint64_t)cols[i] + ent / 2 + 2;
+        if (NC >= 0xFFFFull || 2u * ceil_log2((uint32_t)NC) + ceil_log2(p) > 51u) return fail(PLO_E_CAPACITY, "CSE measure: pair key (col,col,ratio) does not fit 51 bits for this shape and modulus");
+        if (2ull * ent >= 65535ull) return fail(PLO_E_CAPACITY, "CSE measure: op-count may exceed 16 bits");
+        const int rc = layout_plan(C.W[i], rows[i], cols[i], ent, p, cols[i], ent, cap);
+        if (rc != PLO_OK) return rc;
+        region = std::max(region, C.W[i].region_bytes);
+        keep_all = std::max(keep_all, C.W[i].tmpl_bytes); keep_ent = std::max(keep_ent, C.W[i].off_cmask - C.W[i].off_val);
+    }
+    C.off_rs = round_up(Q.lds_per_wave, 16);
+    C.off_img = C.off_rs + round_up(66u * 2u, 16);
+    C.off_keep = C.off_img + round_up(region, 16);
+    // the kept copy: the whole template (faster) where one wave with it fits LDS, else the entries alone
+    for (;;) {
+        C.wave_bytes = C.off_keep + (C.sub > 1u ? round_up(C.keep_full ? keep_all : keep_ent, 16) : 0u);
+        pl->waves_per_wg = pick_waves([&](uint32_t w) { return (uint64_t)Q.shared_bytes + (uint64_t)w * C.wave_bytes; }, true, g_lds_max, &pl->lds_bytes);
+        if (pl->waves_per_wg || !C.keep_full || C.sub == 1u) break;
+        C.keep_full = 0;
+    }
+    if (!pl->waves_per_wg) return fail(PLO_E_CAPACITY, pl->cse_scale == 1 ? "CSE measure: the image of a candidate does not fit LDS with one wave" : "CSE measure: a pair table was full and a larger one does not fit LDS");
+    pl->blocks_per_cu = blocks_per_cu(pl->waves_per_wg, pl->lds_bytes);
+    pl->grid_max = (uint32_t)g_cus * pl->blocks_per_cu;
+    if (pl->d_best) { (void)hipFree(pl->d_best); pl->d_best = nullptr; }
+    HIPCHK(hipMalloc((void **)&pl->d_best, 16ull * pl->grid_max * pl->waves_per_wg));
+    HIPCHK(hipFuncSetAttribute((const void *)orbit_cse_fn(pl->action, false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes));
+    return PLO_OK;
+}
+
+// The sizing launch: entries and pair instances of the three parts, maxima over the base candidate and seeds 0 .. 254
+int orbit_cse_size(plo_orbit_plan *pl)
+{
+    const plo::OrbitPlan &Q = pl->P;
+    plo::OrbitCsePlan C{};
+    C.off_rs = round_up(Q.lds_per_wave, 16); C.off_img = C.off_rs + round_up(66u * 2u, 16); C.off_keep = C.off_img + 128u; C.wave_bytes = C.off_keep;
+    uint32_t lds = 0;
+    const uint32_t W = pick_waves([&](uint32_t w) { return (uint64_t)Q.shared_bytes + (uint64_t)w * C.wave_bytes; }, false, g_lds_max, &lds);
+    if (!W) return fail(PLO_E_CAPACITY, "input does not fit LDS");
+    std::vector<uint64_t> seeds(256); seeds[0] = PLO_ORBIT_BASE_SEED; for (uint64_t j = 1; j < 256; ++j) seeds[j] = j - 1;
+    DevBuf<uint64_t> d_seeds; DevBuf<uint32_t> d_sz;
+    HIPCHK(hipMalloc((void **)&d_seeds.p, 256 * 8)); HIPCHK(hipMemcpy(d_seeds, seeds.data(), 256 * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc((void **)&d_sz.p, 9 * 4)); HIPCHK(hipMemsetAsync(d_sz, 0, 9 * 4, g_stream));
+    const orbit_cse_fn_t fn = orbit_cse_fn(pl->action, true);
+    HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    plo::OrbitJob J{}; J.seeds = d_seeds; J.ncand = 256;
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * 2u, (J.ncand + W - 1) / W));
+    const int rc = timed_launch((plo_stats_t *)nullptr, nullptr, [&] { hipLaunchKernelGGL(fn, dim3((uint32_t)grid), dim3(64 * W), lds, g_stream, pl->P, J, C, d_sz.p); });
+    if (rc != PLO_OK) return rc;
+    uint32_t sz[9] = {0};
+    HIPCHK(hipMemcpy(sz, d_sz, sizeof sz, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; ++i) { pl->cse_ent[i] = sz[i]; pl->cse_pairs[i] = sz[3 + i]; }
+    return PLO_OK;
+}
+
 int orbit_launch(plo_orbit_plan *pl, plo::OrbitJob J, plo_stats_t *st) {
     const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
     const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(pl->grid_max, need));
-    return timed_launch(pl, grid, J.ncand, st, [&] {
-        hipLaunchKernelGGL(orbit_fn(pl->P.p != 0, pl->action), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+    if (!pl->cse)
+        return timed_launch(pl, grid, J.ncand, st, [&] {
+            hipLaunchKernelGGL(orbit_fn(pl->P.p != 0, pl->action), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+        });
+    HIPCHK(hipMemsetAsync(pl->d_err, 0, 4, g_stream));
+    int rc = timed_launch(pl, grid, J.ncand, st, [&] {
+        hipLaunchKernelGGL(orbit_cse_fn(pl->action, false), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J, pl->C, (uint32_t *)nullptr);
     });
+    if (rc != PLO_OK) return rc;
+    uint32_t err = 0;
+    HIPCHK(hipMemcpy(&err, pl->d_err, 4, hipMemcpyDeviceToHost));
+    if (err == plo::ERR_TABLE) {                          // a table or the entry arrays were outgrown: again with twice the slots and the hard entry bound
+        if (st) st->candidates -= J.ncand;
+        ++pl->cse_relaunches; pl->cse_scale *= 2;
+        rc = orbit_cse_layout(pl);
+        return rc != PLO_OK ? rc : (int)ORBIT_AGAIN;
+    }
+    if (err) return fail(PLO_E_INTERNAL, "device: error word " + std::to_string(err) + " in the CSE measure of the orbit search");
+#ifdef PLO_ORBIT_CSE_PROFILE
+    if (getenv("PLO_ORBIT_CSE_STATS")) {
+        unsigned long long g[8] = {0};
+        if (hipMemcpyFromSymbol(g, HIP_SYMBOL(plo::g_ocprof), sizeof g) == hipSuccess && g[5])
+            fprintf(stderr, "# orbit CSE measure, cumulative over %llu candidates: cycles per candidate: factor draw %.0f, sandwich + image build %.0f, Optimizer on Lj %.0f, on Rg %.0f, on hP %.0f\n",
+                    g[5], (double)g[0] / g[5], (double)g[1] / g[5], (double)g[2] / g[5], (double)g[3] / g[5], (double)g[4] / g[5]);
+    }
+#endif
+    return PLO_OK;
 }
 
 // |entries| of the two factors of a part, a direct one of size sd and an inverse of size si, multiplied:
@@ -2199,6 +2326,8 @@ __int128 orbit_factor_bound(int action, uint32_t sd, uint32_t si) {
 }
 } // namespace
 
+static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan);
+
 extern "C" {
 
 int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, plo_orbit_plan_t **plan)
@@ -2208,9 +2337,37 @@ int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
 
 int plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, plo_orbit_plan_t **plan)
 {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (measure == PLO_ORBIT_CSE) return fail(PLO_E_ARG, "PLO_ORBIT_CSE needs sub and cse_seed0: plo_orbit_plan_create_cse");
+    return orbit_plan_build(L, R, P, modulus, measure, action, 0, 0, plan);
+}
+
+int plo_orbit_plan_create_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int action, uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan)
+{
     if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
-    if (measure != PLO_ORBIT_DENSITY && measure != PLO_ORBIT_CANONICAL) return fail(PLO_E_ARG, "measure must be PLO_ORBIT_DENSITY or PLO_ORBIT_CANONICAL");
+    if (modulus == 0 || !(modulus & 1) || modulus >= (1ull << 31) || !is_prime32(modulus)) return fail(PLO_E_ARG, "the CSE measure needs an odd prime modulus below 2^31");
+    if (sub == 0 || sub > 65536u) return fail(PLO_E_ARG, "sub outside [1, 65536]");
+    return orbit_plan_build(L, R, P, modulus, PLO_ORBIT_CSE, action, sub, cse_seed0, plan);
+}
+
+int plo_orbit_plan_info(plo_orbit_plan_t *pl, uint32_t out[8])
+{
+    if (!pl || !out) return fail(PLO_E_ARG, "null argument");
+    out[0] = pl->waves_per_wg; out[1] = pl->lds_bytes;
+    for (int i = 0; i < 3; ++i) out[2 + i] = pl->cse ? pl->C.W[i].cap : 0u;
+    out[5] = pl->cse ? std::max(pl->C.W[0].nnz, std::max(pl->C.W[1].nnz, pl->C.W[2].nnz)) : 0u;
+    out[6] = pl->cse_relaunches; out[7] = pl->cse ? pl->C.keep_full : 0u;
+    return PLO_OK;
+}
+
+} // extern "C"
+
+// the body of the create functions; sub > 0: a PLO_ORBIT_CSE plan
+static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan)
+{
+    const bool cse = measure == PLO_ORBIT_CSE;
+    if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
+    if (!cse && measure != PLO_ORBIT_DENSITY && measure != PLO_ORBIT_CANONICAL) return fail(PLO_E_ARG, "measure must be PLO_ORBIT_DENSITY or PLO_ORBIT_CANONICAL");
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
     if (action != PLO_ORBIT_ACT_TRIANGULAR && action != PLO_ORBIT_ACT_PLUQ && action != PLO_ORBIT_ACT_HOUSEHOLDER) return fail(PLO_E_ARG, "action must be one of PLO_ORBIT_ACT_*");
     if (modulus == 1) return fail(PLO_E_ARG, "modulus 1");
     uint32_t m = 0, k = 0, n = 0;
@@ -2221,6 +2378,10 @@ int plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const pl
     const uint32_t r = L->m;
     if (r > 4096) return fail(PLO_E_CAPACITY, "more than 4096 rows");
     if ((uint64_t)r * (m * k + k * n + m * n) >= (1ull << 21)) return fail(PLO_E_CAPACITY, "2^21 transformed entries or more (21-bit counts in the key)");
+    if (cse) {
+        if (r > 64 || m * n > 64) return fail(PLO_E_CAPACITY, "CSE measure: r or mn above 64 (ProgramGen of the wave kernel keeps one row per lane)");
+        if (m * k > 64 || k * n > 64) return fail(PLO_E_CAPACITY, "CSE measure: mk or kn above 64 (a transformed row of more than 64 entries)");
+    }
     // the rows of L, of R and of P^T, each as (position, value) lists
     std::vector<std::vector<std::pair<uint16_t, std::pair<int64_t, int64_t>>>> rows(3u * r);
     for (uint32_t i = 0; i < r; ++i) {
@@ -2272,7 +2433,7 @@ int plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const pl
     plo::OrbitPlan &Q = pl->P;
     Q.m = m; Q.k = k; Q.n = n; Q.r = r; Q.nnz = nnz; Q.p = modulus;
     // modulo a number every run scores by density, whatever `measure` says (reference src/orbiter.cpp:425)
-    Q.measure = modulus ? (uint32_t)PLO_ORBIT_DENSITY : (uint32_t)measure;
+    Q.measure = modulus ? (uint32_t)PLO_ORBIT_DENSITY : (uint32_t)measure;      // (a CSE plan has a modulus; its kernel does not read this)
     // shared LDS: values, scales, row pointers, positions
     Q.off_scale = round_up(8u * nnz, 16); Q.off_rp = Q.off_scale + round_up(8u * nrows, 16); Q.off_pos = Q.off_rp + round_up(4u * (nrows + 1u), 16);
     Q.shared_bytes = Q.off_pos + round_up(2u * nnz, 16);
@@ -2293,10 +2454,12 @@ int plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const pl
     Q.lds_per_wave = off;
     pl->algo_bytes = 10ull * nnz + 12ull * nrows;
     pl->action = action;
-    pl->waves_per_wg = pick_waves([&](uint32_t w) { return Q.shared_bytes + w * Q.lds_per_wave; }, false, std::min<size_t>(g_lds_max, 64u * 1024u), &pl->lds_bytes);
-    if (!pl->waves_per_wg) { delete pl; return fail(PLO_E_CAPACITY, "input does not fit LDS"); }
-    pl->blocks_per_cu = blocks_per_cu(pl->waves_per_wg, pl->lds_bytes);
-    pl->grid_max = (uint32_t)g_cus * pl->blocks_per_cu;
+    if (!cse) {
+        pl->waves_per_wg = pick_waves([&](uint32_t w) { return Q.shared_bytes + w * Q.lds_per_wave; }, false, std::min<size_t>(g_lds_max, 64u * 1024u), &pl->lds_bytes);
+        if (!pl->waves_per_wg) { delete pl; return fail(PLO_E_CAPACITY, "input does not fit LDS"); }
+        pl->blocks_per_cu = blocks_per_cu(pl->waves_per_wg, pl->lds_bytes);
+        pl->grid_max = (uint32_t)g_cus * pl->blocks_per_cu;
+    }
     // the device image: values, scales, row pointers, positions
     const size_t bytes = (size_t)Q.shared_bytes;
     std::vector<uint8_t> img(bytes, 0);
@@ -2307,22 +2470,37 @@ int plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const pl
     memcpy(img.data() + Q.off_rp, rp.data(), 4u * (nrows + 1u)); memcpy(img.data() + Q.off_pos, pos.data(), 2u * nnz);
     const void *fn = (const void *)orbit_fn(modulus != 0, action);
     if (hipMalloc(&pl->d_img, bytes) != hipSuccess || hipMemcpy(pl->d_img, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc((void **)&pl->d_best, 16ull * pl->grid_max * pl->waves_per_wg) != hipSuccess ||
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes) != hipSuccess) {
+        (!cse && (hipMalloc((void **)&pl->d_best, 16ull * pl->grid_max * pl->waves_per_wg) != hipSuccess ||
+                  hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes) != hipSuccess))) {
         plo_orbit_plan_destroy(pl); return fail(PLO_E_HIP, "device setup of the orbiter plan failed");
     }
     uint8_t *d = (uint8_t *)pl->d_img;
     Q.val = (const int64_t *)d; Q.scale = (const int64_t *)(d + Q.off_scale); Q.rp = (const uint32_t *)(d + Q.off_rp); Q.pos = (const uint16_t *)(d + Q.off_pos);
     if (table) Q.dinv = (const uint32_t *)(d + Q.off_dinv);
+    if (cse) {
+        // bounds from a sizing launch over a sample of the candidates, then the layouts; a copy of the whole template per wave
+        // unless it does not fit, or PLO_ORBIT_CSE_KEEP=0 asks for the entries alone (measured both ways)
+        pl->cse = true;
+        pl->C.sub = sub; pl->C.seed0 = cse_seed0;
+        pl->C.keep_full = env_knob("PLO_ORBIT_CSE_KEEP").value_or(1) != 0 ? 1u : 0u;
+        int rc = hipMalloc((void **)&pl->d_err, 4) == hipSuccess ? PLO_OK : fail(PLO_E_HIP, "hipMalloc");
+        pl->C.err = pl->d_err;
+        if (rc == PLO_OK) rc = orbit_cse_size(pl);
+        if (rc == PLO_OK) rc = orbit_cse_layout(pl);
+        if (rc != PLO_OK) { const std::string why = g_err; plo_orbit_plan_destroy(pl); return fail(rc, why); }
+    }
     *plan = pl;
     return PLO_OK;
 }
+
+extern "C" {
 
 void plo_orbit_plan_destroy(plo_orbit_plan_t *pl)
 {
     if (!pl) return;
     if (pl->d_img) (void)hipFree(pl->d_img);
     if (pl->d_best) (void)hipFree(pl->d_best);
+    if (pl->d_err) (void)hipFree(pl->d_err);
     delete pl;
 }
 
@@ -2330,7 +2508,9 @@ int plo_orbit_cost_many(plo_orbit_plan_t *pl, const uint64_t *seeds, uint64_t se
 {
     return cost_many_run(pl, seeds, n, 3, out3, stats, [&](uint32_t *d_out, const uint64_t *d_seeds, plo_stats_t *st) {
         plo::OrbitJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.out3 = d_out; J.best = nullptr;
-        return orbit_launch(pl, J, st);
+        int rc;
+        do rc = orbit_launch(pl, J, st); while (rc == ORBIT_AGAIN);
+        return rc;
     });
 }
 
@@ -2341,10 +2521,14 @@ int plo_orbit_search(plo_orbit_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_
     if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
     plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
     const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t slots = (uint64_t)pl->grid_max * pl->waves_per_wg;
-    HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, 16 * slots, g_stream));
-    plo::OrbitJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.out3 = nullptr; J.best = pl->d_best;
-    int rc = orbit_launch(pl, J, st);
+    uint64_t slots;
+    int rc;
+    do {                                                  // (a CSE plan that outgrew a table has other per-wave words afterwards)
+        slots = (uint64_t)pl->grid_max * pl->waves_per_wg;
+        HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, 16 * slots, g_stream));
+        plo::OrbitJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.out3 = nullptr; J.best = pl->d_best;
+        rc = orbit_launch(pl, J, st);
+    } while (rc == ORBIT_AGAIN);
     if (rc != PLO_OK) return rc;
     std::vector<uint64_t> w(2 * slots);
     HIPCHK(hipMemcpy(w.data(), pl->d_best, 16 * slots, hipMemcpyDeviceToHost));
@@ -2370,6 +2554,15 @@ int plo_orbit_search_multi_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const p
     return sharded_search(seed0, nseeds, ndev, devices, best, stats,
         [&](plo_orbit_plan_t **plan) { return plo_orbit_plan_create_act(L, R, P, modulus, measure, action, plan); }, plo_orbit_search, plo_orbit_plan_destroy,
         [&](const plo_orbit_best_t &pb) { return std::make_pair(((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, pb.seed - seed0); });   // (cost, nnz, nno), then seed
+}
+
+int plo_orbit_search_multi_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int action, uint32_t sub, uint64_t cse_seed0,
+                               uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_best_t *best, plo_stats_t *stats)
+{
+    if (!L || !R || !P || !best) return fail(PLO_E_ARG, "null argument");
+    return sharded_search(seed0, nseeds, ndev, devices, best, stats,
+        [&](plo_orbit_plan_t **plan) { return plo_orbit_plan_create_cse(L, R, P, modulus, action, sub, cse_seed0, plan); }, plo_orbit_search, plo_orbit_plan_destroy,
+        [&](const plo_orbit_best_t &pb) { return std::make_pair(((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, pb.seed - seed0); });
 }
 
 } // extern "C"

@@ -380,7 +380,7 @@ def lin_search_multi(m, n, rowptr, col, num, den, seed0, nseeds, devices):
 
 
 ORBIT_BASE_SEED = (1 << 64) - 1
-ORBIT_DENSITY, ORBIT_CANONICAL = 0, 2
+ORBIT_DENSITY, ORBIT_CSE, ORBIT_CANONICAL = 0, 1, 2
 ORBIT_ACT_TRIANGULAR, ORBIT_ACT_PLUQ, ORBIT_ACT_HOUSEHOLDER = 0, 1, 2
 
 
@@ -389,16 +389,22 @@ class OrbitPlan:
     R (r x kn), P (mn x r), each as a rational CSR (m, n, rowptr, col, num[, den]), over Q (modulus 0) or Z_modulus
     (< 2^31), scored by `measure` (ORBIT_DENSITY or ORBIT_CANONICAL).  `cost_many` returns (cost, nnz, nno) per seed;
     `search` the best ((cost, nnz, nno), seed), ties to the smaller seed.  ORBIT_BASE_SEED is the input itself.  `action`
-    (ORBIT_ACT_TRIANGULAR, ORBIT_ACT_PLUQ or ORBIT_ACT_HOUSEHOLDER) is how U, V and W are drawn."""
+    (ORBIT_ACT_TRIANGULAR, ORBIT_ACT_PLUQ or ORBIT_ACT_HOUSEHOLDER) is how U, V and W are drawn.  measure=ORBIT_CSE
+    (`plo_orbit_plan_create_cse`, bin/orbiter -z; an odd prime modulus) scores a candidate by the operations of the best
+    programs found for its three matrices: per matrix the minimum of naiveOps and of `sub` Optimizer runs with the streams
+    cse_seed0 .. cse_seed0 + sub - 1.  `info()` is `plo_orbit_plan_info`."""
 
-    def __init__(self, L, R, P, modulus=0, measure=ORBIT_DENSITY, device=None, action=ORBIT_ACT_TRIANGULAR):
+    def __init__(self, L, R, P, modulus=0, measure=ORBIT_DENSITY, device=None, action=ORBIT_ACT_TRIANGULAR, sub=1, cse_seed0=0):
         lib = capi.lib()
         if device is not None:
             capi.check(lib.plo_init(device))
         self._h = None
         self._csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
         h = ctypes.c_void_p()
-        capi.check(lib.plo_orbit_plan_create_act(*[ctypes.byref(c) for c, _ in self._csr], modulus, measure, action, ctypes.byref(h)))
+        if measure == ORBIT_CSE:
+            capi.check(lib.plo_orbit_plan_create_cse(*[ctypes.byref(c) for c, _ in self._csr], modulus, action, sub, cse_seed0, ctypes.byref(h)))
+        else:
+            capi.check(lib.plo_orbit_plan_create_act(*[ctypes.byref(c) for c, _ in self._csr], modulus, measure, action, ctypes.byref(h)))
         self._h = h
         self.last_stats = None
 
@@ -427,15 +433,23 @@ class OrbitPlan:
         self.last_stats = st.as_dict()
         return (b.cost, b.nnz, b.nno), b.seed
 
+    def info(self):
+        out = (ctypes.c_uint32 * 8)()
+        capi.check(capi.lib().plo_orbit_plan_info(self._h, out))
+        return {"waves_per_wg": out[0], "lds_bytes": out[1], "table_slots": tuple(out[2:5]), "entry_bound": out[5], "relaunches": out[6], "keeps_whole_image": bool(out[7])}
 
-def orbit_search_multi(L, R, P, modulus, measure, seed0, nseeds, devices, action=ORBIT_ACT_TRIANGULAR):
-    """`plo_orbit_search_multi_act`: the orbit search over the listed devices from this process (L, R, P as for OrbitPlan).
-    Returns (((cost, nnz, nno), seed), stats)."""
+
+def orbit_search_multi(L, R, P, modulus, measure, seed0, nseeds, devices, action=ORBIT_ACT_TRIANGULAR, sub=1, cse_seed0=0):
+    """`plo_orbit_search_multi_act` (`plo_orbit_search_multi_cse` for measure=ORBIT_CSE): the orbit search over the listed devices
+    from this process (L, R, P as for OrbitPlan).  Returns (((cost, nnz, nno), seed), stats)."""
     lib = capi.lib()
     csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
     dv = (ctypes.c_int * len(devices))(*devices)
     b, st = capi.OrbitBest(), capi.Stats()
-    capi.check(lib.plo_orbit_search_multi_act(*[ctypes.byref(c) for c, _ in csr], modulus, measure, action, seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
+    if measure == ORBIT_CSE:
+        capi.check(lib.plo_orbit_search_multi_cse(*[ctypes.byref(c) for c, _ in csr], modulus, action, sub, cse_seed0, seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
+    else:
+        capi.check(lib.plo_orbit_search_multi_act(*[ctypes.byref(c) for c, _ in csr], modulus, measure, action, seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
     del csr
     return ((b.cost, b.nnz, b.nno), b.seed), st.as_dict()
 
