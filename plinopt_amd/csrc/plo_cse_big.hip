@@ -42,6 +42,15 @@
 //              share one LDS entry because v_b = r v_a in every affected row.  With at
 //              most 32 distinct values (mode 2) an entry is a 25-bit (column, ratio
 //              identifier) key + 16-bit count and the slot list covers every slot.
+//   records    the row search leaves one record per rewritten row: the two positions, the row start, the row, and what the sweep
+//              needs of the two removed entries.  Mode 2: 16 bytes, third word PLO_RW_* = length | the +-1 flag and value index
+//              of the entry that the new column's entry inherits (chosen by the +-1 counts, :70-88, ONCE per row), placed as in a
+//              packed entry | the value indices of both removed entries.  Other modes: 32 bytes with the two packed entries.
+//   sweep      a wave owns every 8th rewritten row; modes 0/1 and the eager mode 2 take two rows per trip, a 64-lane chunk each;
+//              mode 2 with deferred updates takes the entries of its next 64 rows as ONE sequence, 64 per trip (the flat sweep:
+//              the lane's row from mark words, the row's record by four ds_bpermute, entries requested two trips ahead, two
+//              unconditional stores, one ratio-identifier lookup indexed by position (left or right of the a entry), one
+//              aligned-pair probe of the aggregation table: agg_add_rid_bm, a single-exit loop over pair indices).
 //   flush      pass 1 (retirements): every lane walks its share of the slot list on
 //              its own (next entry as soon as both keys are settled); every table slot
 //              has ONE writer in this pass, so the new frequency is a plain store of
@@ -454,25 +463,34 @@ __device__ __forceinline__ bool agg_add_rid(uint32_t *aggk, uint32_t *aggc32, ui
 
 // The same probe loop for the staged sweep (mode 2 with deferred updates): a claimed slot sets its bit in a bitmap with a
 // fire-and-forget atomic -- no counter with a returned value, no slot list (two LDS round trips less on the claim path).
-// hshift = 32 - aggbits: the sweep hands it over in a vector register (below).
+// hshift = 33 - aggbits, the shift that turns the hash into a PAIR index: the sweep hands it over in a vector register (below).
 __device__ __forceinline__ bool agg_add_rid_bm(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, uint32_t *bm, uint32_t hshift, uint32_t *iters = nullptr) {
-    // aligned pairs of slots (one ds_read_b64, the two counts share a word); the hash is a 24-bit product (full rate)
-    const uint32_t mask = (1u << aggbits) - 1u;
-    uint32_t s = ((uint32_t)__umul24(key, 0x9E3779u) >> hshift) & ~1u;      // (__umul24 returns int: an arithmetic shift without the cast)
-    for (uint32_t pr = 0; pr < PLO_AGG_PROBES;) {
+    // aligned pairs of slots (one ds_read_b64, the two counts share a word); the hash is a 24-bit product (full rate).
+    // ONE slot of the pair matters: the first when it holds the key or is empty (slots of a pair fill in order, so an empty first slot rules
+    // the second one out), else the second.  Hit and claim end in the same count update, the loop has one exit, and all it carries is the
+    // pair's index (pair, count word and bitmap bit are each one shift-and-add from it) and the probes left.  Written as "hit: return /
+    // claim: return or again / next pair" the compiler kept a state word and a copy of every carried value per exit: 43 vector and 50
+    // scalar instructions a round with every block visited -- which most trips do, some lane always claims -- against 23 and 28.
+    const uint32_t pmask = (1u << (aggbits - 1u)) - 1u;
+    uint32_t pi = (uint32_t)__umul24(key, 0x9E3779u) >> hshift;      // (__umul24 returns int: an arithmetic shift without the cast)
+    for (uint32_t left = PLO_AGG_PROBES / 2u;;) {
         if (iters) ++*iters;
-        const unsigned long long kk = __hip_atomic_load((unsigned long long *)(aggk + s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const unsigned long long kk = __hip_atomic_load((unsigned long long *)aggk + pi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         const uint32_t k0 = (uint32_t)kk, k1 = (uint32_t)(kk >> 32);
-        if (k0 == key || k1 == key) { wg_add(&aggc32[s >> 1], k0 == key ? 1u : 0x10000u); return true; }      // (an empty first slot rules the second one out)
-        if (k0 == 0xFFFFFFFFu || k1 == 0xFFFFFFFFu) {
-            const uint32_t sec = k0 == 0xFFFFFFFFu ? 0u : 1u, t = s + sec;
-            const uint32_t old = wg_cas(&aggk[t], 0xFFFFFFFFu, key);
-            if (old == 0xFFFFFFFFu || old == key) { if (old != key) wg_or(&bm[t >> 5], 1u << (t & 31u)); wg_add(&aggc32[s >> 1], sec ? 0x10000u : 1u); return true; }
-            continue;                      // somebody took the slot for another key: look at both again
+        const bool first = k0 == key || k0 == 0xFFFFFFFFu;
+        const uint32_t kt = first ? k0 : k1;
+        bool mine = kt == key;
+        const uint32_t next = !mine && kt != 0xFFFFFFFFu ? 1u : 0u;      // both slots hold other keys: the next pair
+        if (kt == 0xFFFFFFFFu) {
+            const uint32_t sec = first ? 0u : 1u;
+            const uint32_t old = wg_cas((uint32_t *)((unsigned long long *)aggk + pi) + sec, 0xFFFFFFFFu, key);
+            if (old == 0xFFFFFFFFu) { const uint32_t t = 2u * pi + sec; wg_or(&bm[t >> 5], 1u << (t & 31u)); }
+            mine = old == 0xFFFFFFFFu || old == key;       // (else somebody took the slot for another key: look at both again)
         }
-        s = (s + 2u) & mask; pr += 2u;
+        if (mine) wg_add(&aggc32[pi], first ? 1u : 0x10000u);
+        pi = (pi + next) & pmask; left -= next;
+        if (mine || left == 0u) return mine;
     }
-    return false;
 }
 
 #ifdef PLO_BIG_PROFILE
@@ -503,6 +521,15 @@ __device__ __forceinline__ bool agg_add_rid_first_prof(uint32_t *aggk, uint32_t 
 #define PLO_ECOL(e_) ((e_) & 0x7FFFu)
 #define PLO_EUNIT(e_) (((e_) >> 15) & 1u)
 #define PLO_EVI(e_) ((e_) >> 16)
+// Third word of a mode-2 row record (the row search's emit() writes it, every sweep reads it):
+//   bits 0-13  row length L (<= 8192)                  bit 14, bit 21: clear
+//   bits 15-20 +-1 flag and value index of the row's l0 entry, AS IN A PACKED ENTRY (PLO_RW_NEW): the new column's entry is (word & PLO_RW_NEW) | column
+//   bits 22-26 vib, bits 27-31 via: value indices of the removed entries.  via is on top: the sweep's straight path gets it with one shift and
+//              no mask (vib is read on the direct-retirement fallback only)
+#define PLO_RW_LEN 0x3FFFu
+#define PLO_RW_NEW 0x1F8000u
+#define PLO_RW_VIB 22u
+#define PLO_RW_VIA 27u
 // position of column c in row [base, base+L) (sorted by column), or -1
 template <class ENT> __device__ __forceinline__ int row_find(ENT ent, uint32_t base, uint32_t L, uint32_t c) {
     uint32_t lo = 0, hi = L;
@@ -1183,11 +1210,12 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                 atomicAdd(&sh.tb2[1], 100ull * L);
 #endif
                 if constexpr (MODE == 2) {
-                    // 16-byte record (value indices have 5 bits): positions, row start, length (<= 8192: 14 bits) | value index and +-1 flag of
-                    // the a and b entries, row -- 32 bytes in round 2: 48 MB less written and read per candidate on config 5.  Bits 26-30 are set and
-                    // bit 31 is clear, always: no reader looks at them (each masks its field).  They stay because without them cse_big_kernel<2, false, true>
-                    // spills two more scalar registers (the register allocation here is on a knife edge)
-                    *(uint4 *)(aff + 4u * idx) = make_uint4(pa | (pb << 16), base, L | (PLO_EUNIT(ea) << 14) | (PLO_EVI(ea) << 15) | (PLO_EUNIT(eb) << 20) | (PLO_EVI(eb) << 21) | 0x7C000000u, i);
+                    // 16-byte record (value indices have 5 bits): positions, row start, the word PLO_RW_* below, row -- 32 bytes in round 2: 48 MB
+                    // less written and read per candidate on config 5.  What is constant per row or per step is decided HERE, once per row, not per
+                    // swept entry (a row serves ~100 of them): the new column's entry carries the +-1 flag and the value index of the l0 entry
+                    // (:96-110), so those six bits sit where a packed entry has them and the sweep's new entry is (word & PLO_RW_NEW) | lm;
+                    // via is the top field, read by one shift and no mask (retire_entry).
+                    *(uint4 *)(aff + 4u * idx) = make_uint4(pa | (pb << 16), base, L | ((swap ? eb : ea) & PLO_RW_NEW) | (PLO_EVI(eb) << PLO_RW_VIB) | (PLO_EVI(ea) << PLO_RW_VIA), i);
                 } else {
                 uint32_t *rec = &aff[8u * idx];                             // record: row, positions (16 bits each), row start and length; the two packed entries
                 *(uint4 *)rec = make_uint4(i, pa | (pb << 16), base, L);
@@ -1250,26 +1278,27 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
         // pair with a has ratio x, the pair with b has ratio r x (c < a), r/x (a < c < b) or x/r (b < c).  One LDS entry
         // per (c, x) therefore carries both retirements; the flush derives the two table keys.
         {
-            // via, vib: value indices of the row's two removed entries (they name v_a and v_b)
+            // rw (mode 2): the row's record word, PLO_RW_*: via and vib, the value indices of the row's two removed entries (they name v_a and v_b);
+            // above: the entry lies right of the a entry (c > a) -- the sweeps know that from the positions, no column compare
 #ifdef PLO_BIG_PROFILE
             uint32_t probe_iters = 0; unsigned long long pq[3] = {0, 0, 0}, prt = 0;
 #endif
             // The hash's shift count lives in a vector register through the sweep: it is the one scalar of the trip's straight path
             // that found no scalar register (a v_readlane per trip), and the kernel has vector registers to spare for one word.
-            uint32_t aggsh = 32u - aggbits; asm("" : "+v"(aggsh));
+            uint32_t aggsh = 33u - aggbits; asm("" : "+v"(aggsh));
             const uint32_t agg_dual = MODE == 2 ? 0u : PW(agg_dual), logcap = DEFER ? PW(logcap) : 0u;       // (plan words of this phase; none is read inside the trip:
             // the kernel-argument pointer would have to be at hand there, and it is a spilled pair)
-            auto retire_entry = [&](uint32_t e, uint32_t via, uint32_t vib, uint2 VA, uint2 VB, bool noagg = false) {      // noagg: the LDS table had no room for it (already tried)
+            auto retire_entry = [&](uint32_t e, uint32_t rw, bool above, uint2 VA, uint2 VB, bool noagg = false) {      // noagg: the LDS table had no room for it (already tried)
                 const uint32_t c = PLO_ECOL(e);
                 // x = v_a/v_c (c < a) or v_c/v_a (c > a) names both retired pairs; y = v_a/v_c names the pair with the new column
                 // (x itself, or 1/x: kept beside x in the entry when the bits allow, so that the flush needs no inversion)
                 uint32_t x, y, q2, ins;                                        // q2: ratio of the pair with b; ins: ratio of the pair with the new column (both only on the fallback path)
                 if constexpr (MODE == 2) {
-                    const uint32_t vi = PLO_EVI(e);
+                    const uint32_t vi = PLO_EVI(e), via = rw >> PLO_RW_VIA;
 #ifdef PLO_BIG_PROFILE
                     const unsigned long long cr0 = clock64();
 #endif
-                    const uint32_t xid = rtid[c < a ? (via * PLO_RSTRIDE) | vi : (vi * PLO_RSTRIDE) | via];      // one lookup, no branch
+                    const uint32_t xid = rtid[((above ? vi : via) * PLO_RSTRIDE) | (above ? via : vi)];      // one lookup, no branch
 #ifdef PLO_BIG_PROFILE
                     if constexpr (FAST) {
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); prt += clock64() - cr0;
@@ -1281,6 +1310,7 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                     if constexpr (FAST) { if (!noagg) { if (__builtin_expect(agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm, aggsh), 1)) return; } }
 #endif
                     else if (agg_add_rid(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, &sh.aggn, agglist, listcap)) return;
+                    const uint32_t vib = (rw >> PLO_RW_VIB) & 31u;
                     const uint32_t bc = rval[rtid[vib * PLO_RSTRIDE + vi]];                                  // v_b / v_c
                     x = rval[xid]; y = rval[rtid[via * PLO_RSTRIDE + vi]];
                     q2 = c < b ? bc : rval[rtid[vi * PLO_RSTRIDE + vib]];
@@ -1336,7 +1366,7 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                 if (idx < spillcap) spill[idx] = BKEY(c, lm, ins); else wg_max(&sh.errflag, (uint32_t)BERR_TABLE);
             };
             // The sweep proper.  A wave owns the rows wave, wave + nwaves, ... of the step and first loads the records of its
-            // next 64 rows, ONE PER LANE (a record = row start, length, the two positions, the two removed entries), reading
+            // next 64 rows, ONE PER LANE (a record = row start, the two positions, and the two removed entries or, in mode 2, the word PLO_RW_*), reading
             // them back with v_readlane: no trip waits for a record -> row dependency.  Prefetches are unconditional
             // (clamped index, length 0 past the end): no branch around a load.  In-place rewrite: a chunk's stores reach back
             // at most two positions and never forward, the chunks of a row are worked on in order by one wave, and a chunk
@@ -1357,12 +1387,12 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
             uint64_t *fm = sh.sel + 256u + 32u * wave;                  // (the bitmap of claimed slots takes at most the first 2 KB)
             const uint32_t FW = PW(fwin);
             const uint32_t dump = PW(nnz) + 64u + lane;                   // (the entry array has 128 spare words)
-            const uint32_t selsh = l0 == a ? 14u : 20u;                 // the new column's entry carries the +-1 flag and the value index of the l0 entry
             for (uint32_t k0 = 0; k0 < nrw; k0 += 64u) {
                 const bool have = k0 + lane < nrw;
                 const uint32_t qq = have ? wave + (k0 + lane) * nwaves : wave;
                 const uint4 R0 = *(const uint4 *)(aff + 4u * qq);
-                const uint32_t Lr = have ? (R0.z & 0x3FFFu) : 0u;
+                const uint32_t Lr = have ? (R0.z & PLO_RW_LEN) : 0u;
+                const uint32_t RZ = R0.z - 1u;                          // the record word with the row's LAST POSITION in the length field (L >= 2: no borrow), once per row instead of an add per entry
                 const uint32_t E = wave_incl_scan(Lr), S = E - Lr, T = RL(E, 63);
                 const uint32_t safe = RL(R0.y, 0);
                 uint32_t qlo = 0;
@@ -1380,12 +1410,13 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                     // before position i": rows ended at or below a lane = bit 0 + v_mbcnt of the mask shifted right by one.
                     auto prep = [&](uint32_t t_, uint32_t &ad_, uint32_t &z_, uint32_t &pp_, uint32_t &rz_, uint32_t &e_) {
                         const bool ok = t_ < ntw;                          // (the trip after the window's last one is requested nowhere and marks nothing)
-                        const uint32_t ml = ok ? RL(mrl, t_ & 31u) : 0u, mh = ok ? RL(mrh, t_ & 31u) : 0u;
+                        const uint32_t ml_ = RL(mrl, t_ & 31u), mh_ = RL(mrh, t_ & 31u);      // (read unconditionally, then selected: behind `ok ?` each readlane sat in a branch of its own)
+                        const uint32_t ml = ok ? ml_ : 0u, mh = ok ? mh_ : 0u;
                         const uint32_t m1l = (ml >> 1) | (mh << 31), m1h = mh >> 1;
                         const int qa = (int)((qlo + (ml & 1u) + __builtin_amdgcn_mbcnt_hi(m1h, __builtin_amdgcn_mbcnt_lo(m1l, 0u))) << 2);
                         qlo += (uint32_t)__builtin_popcount(ml) + (uint32_t)__builtin_popcount(mh);
                         const uint32_t rb_ = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)R0.y), S_ = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)S);
-                        pp_ = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)R0.x); rz_ = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)R0.z);
+                        pp_ = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)R0.x); rz_ = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)RZ);
                         const uint32_t f_ = w0 + (t_ << 6) + lane;
                         z_ = f_ - S_; ad_ = rb_ + z_;
                         e_ = ent[ok && f_ < T ? ad_ : safe];
@@ -1404,8 +1435,8 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                         const bool in = w0 + (t << 6) + lane < T, act = in && zc != pa && zc != pb;
                         // (the two UNCONDITIONAL stores: see the one-ahead loop below)
                         ent[act && zc > pa ? adc - 1u - (zc > pb ? 1u : 0u) : dump] = ec;
-                        ent[in && zc + 1u == (rzc & 0x3FFFu) ? adc - 1u : dump] = (((rzc >> selsh) & 63u) << 15) | lm;
-                        if (act) retire_entry(ec, (rzc >> 15) & 31u, (rzc >> 21) & 31u, make_uint2(0, 0), make_uint2(0, 0));
+                        ent[in && zc == (rzc & PLO_RW_LEN) ? adc - 1u : dump] = (rzc & PLO_RW_NEW) | lm;
+                        if (act) retire_entry(ec, rzc, zc > pa, make_uint2(0, 0), make_uint2(0, 0));
                     };
                     uint32_t a0_, z0_, p0_, r0_, e0_, a1_, z1_, p1_, r1_, e1_, a2_, z2_, p2_, r2_, e2_;
                     prep(0u, a0_, z0_, p0_, r0_, e0_); prep(1u, a1_, z1_, p1_, r1_, e1_);
@@ -1432,11 +1463,11 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                         // UNCONDITIONAL (idle lanes write to a dump word behind the entries): behind a branch the compiler cannot
                         // count them and waits for every store of the trip (vmcnt(0)) before it uses the entry requested a trip ahead.
                         ent[act && zc > pa ? adc - 1u - (zc > pb ? 1u : 0u) : dump] = ec;
-                        ent[in && zc + 1u == (rzc & 0x3FFFu) ? adc - 1u : dump] = (((rzc >> selsh) & 63u) << 15) | lm;
+                        ent[in && zc == (rzc & PLO_RW_LEN) ? adc - 1u : dump] = (rzc & PLO_RW_NEW) | lm;
 #ifdef PLO_BIG_PROFILE
                         __builtin_amdgcn_wave_barrier(); const unsigned long long t1_ = clock64(); probe_iters = 0;
 #endif
-                        if (act) retire_entry(ec, (rzc >> 15) & 31u, (rzc >> 21) & 31u, make_uint2(0, 0), make_uint2(0, 0));
+                        if (act) retire_entry(ec, rzc, zc > pa, make_uint2(0, 0), make_uint2(0, 0));
 #ifdef PLO_BIG_PROFILE
                         {   __builtin_amdgcn_wave_barrier(); const unsigned long long t2_ = clock64(); pw0 += t1_ - t0_; pw1 += t2_ - t1_; pw2 += t0_ - tl_; tl_ = t2_; ++ptr;
                             uint32_t mx = probe_iters; for (int o = 1; o < 64; o <<= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)mx, o); mx = u > mx ? u : mx; }
@@ -1455,8 +1486,8 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                 uint32_t Rpp, Rbase, RL_, Rea, Reb;
                 if constexpr (MODE == 2) {
                     const uint4 R0 = *(const uint4 *)(aff + 4u * qq);
-                    Rpp = R0.x; Rbase = R0.y; RL_ = have ? (R0.z & 0x3FFFu) : 0u;
-                    Rea = ((R0.z >> 14) & 63u) << 15; Reb = ((R0.z >> 20) & 63u) << 15;   // value index and +-1 flag: all the sweep needs of the two entries
+                    Rpp = R0.x; Rbase = R0.y; RL_ = have ? (R0.z & PLO_RW_LEN) : 0u;
+                    Rea = Reb = R0.z;                                                      // the record word (PLO_RW_*) holds all the sweep needs of the two entries
                 } else {
                     const uint4 R0 = *(const uint4 *)(aff + 8u * qq); const uint2 R1 = *(const uint2 *)(aff + 8u * qq + 4u);
                     Rpp = R0.y; Rbase = R0.z; RL_ = have ? R0.w : 0u; Rea = R1.x; Reb = R1.y;
@@ -1493,8 +1524,8 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
 #ifdef PLO_BIG_PROFILE
                         const unsigned long long t1_ = clock64();
 #endif
-                        if (actA) retire_entry(eA, PLO_EVI(eaA), PLO_EVI(ebA), VaA, VbA);
-                        if (actB) retire_entry(eB, PLO_EVI(eaB), PLO_EVI(ebB), VaB, VbB);
+                        if (actA) retire_entry(eA, eaA, z > paA, VaA, VbA);
+                        if (actB) retire_entry(eB, eaB, z > paB, VaB, VbB);
                         __builtin_amdgcn_wave_barrier();
 #ifdef PLO_BIG_PROFILE
                         { const unsigned long long t2_ = clock64(); pw0 += t1_ - t0_; pw1 += t2_ - t1_; pw2 += t0_ - tl_; tl_ = t2_; ++ptr; }
@@ -1502,8 +1533,8 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                         if (morez) { eA = neA; eB = neB; }
                     }
                     if (lane == 0) {                       // the new column's entry goes last (len and the +-1 counters were updated by the search)
-                        if (LA) ent[baseA + LA - 2u] = (((l0 == a) ? eaA : ebA) & 0xFFFF8000u) | lm;
-                        if (LB) ent[baseB + LB - 2u] = (((l0 == a) ? eaB : ebB) & 0xFFFF8000u) | lm;
+                        if (LA) ent[baseA + LA - 2u] = (MODE == 2 ? eaA & PLO_RW_NEW : ((l0 == a) ? eaA : ebA) & 0xFFFF8000u) | lm;
+                        if (LB) ent[baseB + LB - 2u] = (MODE == 2 ? eaB & PLO_RW_NEW : ((l0 == a) ? eaB : ebB) & 0xFFFF8000u) | lm;
                     }
                     baseA = nbaseA; LA = nLA; baseB = nbaseB; LB = nLB; eA = nfA; eB = nfB;
                 }
