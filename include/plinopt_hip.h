@@ -377,6 +377,34 @@ int  plo_orbit_search_multi_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const 
  * when a wave keeps a copy of the whole image between the sub runs, 0 when it keeps the entries and makes the rest again */
 int  plo_orbit_plan_info(plo_orbit_plan_t *plan, uint32_t out[8]);
 
+/* PLO_ORBIT_GROWTH (`-g`): the 2-norm growth factor of the transformed triple, the reference's G2 (src/growthfactor.cpp:117-125),
+ * over Q only.  For candidate `seed` the transformed triple is the one the density measure counts: same stream, same actions,
+ * same base seed.  With the rows of L and R and the columns of P scaled to integers as above (scale c_g for row g of the 3r
+ * rows: the lcm of its denominators) let S_g = sum of acc^2 over the outputs of row g, the acc being the exact integers of the
+ * sandwich.  Then
+ *   n_g = sqrt(double(S_g)) / double(c_g),      cost = sum_{i=0}^{r-1} (n_i * n_{r+i}) * n_{2r+i},
+ * every operation (two conversions, square root, division, two products, one addition per i) rounded to nearest on its own, no
+ * fused multiply-add, the sum starting from 0.0 with one addition per i in increasing i.  nnz and nno are as above.
+ * Order: the lexicographic minimum of (cost, nnz, nno, seed); the cost is compared as its 64-bit pattern, which for a
+ * non-negative finite double is the numeric order.  The tool's winner improves on the input iff its (cost, nnz, nno) is smaller.
+ * plo_orbit_plan_create_growth takes the limits and refusals of the Q plans above (m, k, n <= 16, r <= 4096, LDS with 24 r more
+ * bytes per wave) and proves in addition E_g B_g^2 < 2^53 for every row (E_g the outputs of the row, B_g the bound on |acc| above:
+ * the row's L1 norm times the action's factor bounds) and every scale below 2^53, so that double(S_g) and double(c_g) are exact:
+ * PLO_E_UNSUPPORTED otherwise (the host computes S_g in 128 bits and rounds once).  PLO_E_ARG: PLO_ORBIT_ACT_HOUSEHOLDER (an
+ * orthogonal action preserves G2: there is nothing to search) or an unknown action.  There is no modulus: a norm modulo p means
+ * nothing.  The other create functions refuse the measure (PLO_E_ARG).  plo_orbit_plan_destroy and plo_orbit_plan_info serve these
+ * plans; plo_orbit_cost_many and plo_orbit_search return PLO_E_ARG on them (their outputs cannot carry a double). */
+#define PLO_ORBIT_GROWTH    3                          /* -g */
+typedef struct { double cost; uint32_t nnz, nno; uint64_t seed; } plo_orbit_gbest_t;
+int  plo_orbit_plan_create_growth(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, int action, plo_orbit_plan_t **plan);
+/* cost[k], nnz_nno[2k], nnz_nno[2k+1] of candidate k (seeds[k], or seed0+k when seeds==NULL) */
+int  plo_orbit_growth_many(plo_orbit_plan_t *plan, const uint64_t *seeds, uint64_t seed0, uint64_t n,
+                           double *cost, uint32_t *nnz_nno /* 2 per seed */, plo_stats_t *stats);
+int  plo_orbit_growth_search(plo_orbit_plan_t *plan, uint64_t seed0, uint64_t nseeds, plo_orbit_gbest_t *best, plo_stats_t *stats);
+/* contiguous shards over `ndev` devices and the minimum under the order above, as plo_orbit_search_multi */
+int  plo_orbit_growth_search_multi(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, int action,
+                                   uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_gbest_t *best, plo_stats_t *stats);
+
 /* ---- Row-dependency enumeration: the search of the reference's `dependency` (src/dependency.cpp:74-101, 158-165).  M (m x n) as
  * rational CSR, `ncoef` coefficients cnum[v]/cden[v] (the caller's FCoeffs, in order), `level` the largest number of rows in a
  * combination (1 .. PLO_DEP_MAX_LEVEL).  A combination is a top row i with coefficient 1 and rows i < q1 < q2 < ... with

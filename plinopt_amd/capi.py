@@ -27,6 +27,7 @@ EXPORTS = [
     "plo_lin_plan_create_q", "plo_lin_plan_destroy", "plo_lin_cost_many", "plo_lin_search", "plo_lin_search_multi",
     "plo_orbit_plan_create_q", "plo_orbit_plan_create_act", "plo_orbit_plan_destroy", "plo_orbit_cost_many", "plo_orbit_search", "plo_orbit_search_multi", "plo_orbit_search_multi_act",
     "plo_orbit_plan_create_cse", "plo_orbit_search_multi_cse", "plo_orbit_plan_info",
+    "plo_orbit_plan_create_growth", "plo_orbit_growth_many", "plo_orbit_growth_search", "plo_orbit_growth_search_multi",
     "plo_dep_plan_create_q", "plo_dep_plan_destroy", "plo_dep_search",
     "plo_pack_cost",
 ]
@@ -84,6 +85,11 @@ class LinBest(ctypes.Structure):
 
 class OrbitBest(ctypes.Structure):
     _fields_ = [("cost", ctypes.c_uint32), ("nnz", ctypes.c_uint32), ("nno", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
+
+
+class OrbitGBest(ctypes.Structure):
+    """plo_orbit_gbest_t of include/plinopt_hip.h"""
+    _fields_ = [("cost", ctypes.c_double), ("nnz", ctypes.c_uint32), ("nno", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
 
 
 DEP_MAX_LEVEL = 8
@@ -191,6 +197,12 @@ def lib():
                                              ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(OrbitBest), ctypes.POINTER(Stats)]
         L.plo_orbit_search_multi_act.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                                  ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(OrbitBest), ctypes.POINTER(Stats)]
+        if hasattr(L, "plo_orbit_plan_create_growth"):    # (an older build named by PLO_HIP_LIB, as above)
+            L.plo_orbit_plan_create_growth.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+            L.plo_orbit_growth_many.argtypes = [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double), u32p, ctypes.POINTER(Stats)]
+            L.plo_orbit_growth_search.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(OrbitGBest), ctypes.POINTER(Stats)]
+            L.plo_orbit_growth_search_multi.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                                        ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(OrbitGBest), ctypes.POINTER(Stats)]
         L.plo_dep_plan_create_q.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                             ctypes.POINTER(ctypes.c_void_p)]
         L.plo_dep_plan_destroy.argtypes = [ctypes.c_void_p]

@@ -1,6 +1,6 @@
 // ==========================================================================
 // bin/orbiter -- the De Groote orbit search of a matrix-multiplication triple (reference src/orbiter.cpp):
-//   orbiter [-b bits] [-m|-q mod] [-r r e s] [-s|-c|-z] [--sub n] [-O loops] [--seed s] [--gpu 0|1|N] [--action a] L.sms R.sms P.sms
+//   orbiter [-b bits] [-m|-q mod] [-r r e s] [-s|-c|-z|-g] [--sub n] [-O loops] [--seed s] [--gpu 0|1|N] [--action a] L.sms R.sms P.sms
 // Searches the candidates (U, V, W) s .. s+O-1 (plo_orbit_*, include/plinopt_hip.h) for an equivalent triple with a smaller
 // (cost, nnz, nno); when the best one improves on the input, writes <L>.nnz.sms, <R>.nnz.sms, <P>.nnz.sms next to the inputs.
 // clog: the reference's '#' lines (Init. ops, Search(N), Rdcd. opt) and the exact matrix-multiplication checks of the input
@@ -9,12 +9,15 @@
 // -z (reference :172-209, PLO_ORBIT_CSE) scores a candidate by the operations of the best programs CSEOptimiser finds for its three
 // matrices: min(naiveOps, the best of `sub` Optimizer runs) per matrix, sub = loops >> 4 above 16 loops, else 1 (:257), or --sub n;
 // the Optimizer streams are seeds 0 .. sub-1 for every candidate.  It needs a prime modulus (-q 2147483629 stands for Q).
+// -g (PLO_ORBIT_GROWTH) scores a candidate by the 2-norm growth factor of its triple, the G2 of bin/growthfactor, over Q with the
+// triangular or the PLUQ action (Householder matrices are orthogonal and keep it): the search for a more accurate equivalent algorithm.
+// Its cost is a double: six decimals on the '#' lines, 17 significant digits on stdout (`winner`, --costs), which determine its bits.
 // The restarts run on the GPU through plo_orbit_search[_multi] of libplinopt_hip.so; --gpu 0, or an input the device refuses
 // (a modulus of 2^31 or more, a Q input outside its int64 bound, sizes beyond its limits), uses the host loop (OpenMP) and
 // says so.  -b is accepted for the reference's command lines: the checks here are exact.
 // --action triangular|pluq|householder chooses how U, V and W are drawn (PLO_ORBIT_ACT_*; the reference's compile-time
 // ACTION_FULL_PLUQ and ACTION_HOUSEHOLDER, src/orbiter.cpp:77-123), for the search, --costs and --candidate alike.
-// Refused with status 2: -z over Q or modulo a composite number, -P/-I, shapes that are not mk, kn, mn, a denominator that is no unit modulo the modulus, a
+// Refused with status 2: -g with a modulus, with -z or with --action householder, -z over Q or modulo a composite number, -P/-I, shapes that are not mk, kn, mn, a denominator that is no unit modulo the modulus, a
 // modulus above 2^63.  Testing aids: --costs prints `cost nnz nno` of the base candidate, then of seeds s .. s+O-1 (host);
 // --candidate s|base DIR writes the three matrices of one candidate to DIR/{L,R,P}.sms.
 // ==========================================================================
@@ -32,13 +35,21 @@ struct HipOrbit {
     PLO_SYM(create, plo_orbit_plan_create_act); PLO_SYM(destroy, plo_orbit_plan_destroy);
     PLO_SYM(search, plo_orbit_search); PLO_SYM(search_multi, plo_orbit_search_multi_act);
     PLO_SYM(create_cse, plo_orbit_plan_create_cse); PLO_SYM(search_multi_cse, plo_orbit_search_multi_cse);
+    PLO_SYM(create_growth, plo_orbit_plan_create_growth); PLO_SYM(search_growth, plo_orbit_growth_search); PLO_SYM(search_multi_growth, plo_orbit_growth_search_multi);
 };
 
 struct Opts {
-    size_t loops = 100; uint64_t seed0 = 0; int gpu = 1; int measure = ORBIT_DENSITY; int action = ORBIT_ACT_TRIANGULAR; bool cse = false;
+    size_t loops = 100; uint64_t seed0 = 0; int gpu = 1; int measure = ORBIT_DENSITY; int action = ORBIT_ACT_TRIANGULAR; bool cse = false, growth = false;
     unsigned __int128 modulus = 0; bool costs = false, cand = false; uint64_t cseed = 0; std::string cdir;
     size_t sub = 0;                                                                       // --sub; 0: the reference's loops >> 4
 };
+
+// a cost as the tool prints it: a count, or with -g the growth factor held as its bits (six decimals, or 17 significant digits)
+std::string cost_text(int measure, size_t cost, bool exact = false) {
+    if (measure != ORBIT_GROWTH) return std::to_string(cost);
+    char t[64]; snprintf(t, sizeof t, exact ? "%.17g" : "%.6f", growth_value(cost));
+    return t;
+}
 
 std::string nnz_name(const std::string &f) { return std::filesystem::path(f).replace_extension(".nnz.sms").string(); }
 
@@ -65,10 +76,10 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
                                  const std::vector<std::string> &files) {
     OrbitTriple<F> T;
     T.L = rebind(QL, f); T.R = rebind(QR, f); T.PT = rebind(transpose(QP), f); T.m = m; T.k = k; T.n = n;
-    const int measure = o.cse ? ORBIT_CSE : modulus ? ORBIT_DENSITY : o.measure;
+    const int measure = o.cse ? ORBIT_CSE : o.growth ? ORBIT_GROWTH : modulus ? ORBIT_DENSITY : o.measure;
     const OrbitCse z{o.sub ? o.sub : (o.loops > 16 ? o.loops >> 4 : 1), 0};                // :257
     if (o.costs) {
-        auto line = [&](uint64_t s) { const OrbitCount c = orbit_candidate(f, T, s, measure, o.action, z); std::cout << c.cost << ' ' << c.nnz << ' ' << c.nno << '\n'; };
+        auto line = [&](uint64_t s) { const OrbitCount c = orbit_candidate(f, T, s, measure, o.action, z); std::cout << cost_text(measure, c.cost, true) << ' ' << c.nnz << ' ' << c.nno << '\n'; };
         line(ORBIT_BASE);
         for (uint64_t j = 0; j < o.loops; ++j) line(o.seed0 + j);
         return 0;
@@ -77,12 +88,12 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
         OrbitTriple<F> C; const OrbitCount c = orbit_candidate(f, T, o.cseed, measure, o.action, &C, z);
         std::filesystem::create_directories(o.cdir);
         write_triple(f, C, o.cdir + "/L.sms", o.cdir + "/R.sms", o.cdir + "/P.sms", modulus ? 'M' : 'R');
-        std::clog << "# candidate " << (o.cseed == ORBIT_BASE ? std::string("base") : std::to_string(o.cseed)) << ": " << c.cost << ' ' << c.nnz << ' ' << c.nno << std::endl;
+        std::clog << "# candidate " << (o.cseed == ORBIT_BASE ? std::string("base") : std::to_string(o.cseed)) << ": " << cost_text(measure, c.cost, true) << ' ' << c.nnz << ' ' << c.nno << std::endl;
         return 0;
     }
     const int input_bad = mm_report(f, T);                                               // :263, printed then ignored
     const OrbitCount init = orbit_candidate(f, T, ORBIT_BASE, measure, o.action, z);
-    std::clog << "# Init. ops: " << init.cost << ", (" << init.nnz << ',' << init.nno << ')' << std::endl;
+    std::clog << "# Init. ops: " << cost_text(measure, init.cost) << ", (" << init.nnz << ',' << init.nno << ')' << std::endl;
     const auto t0 = std::chrono::steady_clock::now();
     using Key = std::tuple<size_t, size_t, size_t, uint64_t>;                             // (cost, nnz, nno, seed)
     Key best{~(size_t)0, 0, 0, 0};
@@ -97,34 +108,50 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
                 HipOrbit H;
                 if (!H.ok) { std::cerr << "# \033[1;31mERROR: libplinopt_hip.so cannot be loaded or lacks plo_orbit_search\033[0m\n"; return 2; }   // no silent fallback
                 const plo_qcsr_t l = cl.view(), r = cr.view(), p = cp.view();
-                plo_orbit_best_t b{}; plo_stats_t st{};
-                int rc;
-                if (o.gpu >= 2) {
-                    std::vector<int> devs((size_t)o.gpu); for (int j = 0; j < o.gpu; ++j) devs[(size_t)j] = shard_device(j);
-                    rc = o.cse ? H.search_multi_cse(&l, &r, &p, modulus, o.action, (uint32_t)z.sub, z.seed0, o.seed0, o.loops, o.gpu, devs.data(), &b, &st)
-                               : H.search_multi(&l, &r, &p, modulus, measure, o.action, o.seed0, o.loops, o.gpu, devs.data(), &b, &st);
-                } else {
-                    rc = H.init(0);
-                    plo_orbit_plan_t *plan = nullptr;
-                    if (rc == PLO_OK) rc = o.cse ? H.create_cse(&l, &r, &p, modulus, o.action, (uint32_t)z.sub, z.seed0, &plan) : H.create(&l, &r, &p, modulus, measure, o.action, &plan);
-                    // (a launch takes at most 2^31-1 candidates: longer runs go in pieces, minimum under the same order)
-                    for (uint64_t done = 0; rc == PLO_OK && done < o.loops;) {
-                        const uint64_t piece = std::min<uint64_t>(o.loops - done, (1ull << 31) - 1ull);
-                        plo_orbit_best_t pb{}; plo_stats_t ps{};
-                        rc = H.search(plan, o.seed0 + done, piece, &pb, &ps);
-                        if (rc != PLO_OK) break;
-                        if (done == 0 || std::tie(pb.cost, pb.nnz, pb.nno) < std::tie(b.cost, b.nnz, b.nno)) b = pb;
-                        st.kernel_ms += ps.kernel_ms;
-                        done += piece;
+                plo_stats_t st{}; Key dbest{};
+                // The device search of one measure, whose best is a Best and whose order is keyof(best), then the seed: `multi` over o.gpu
+                // shards, or one plan of `create` searched in pieces (a launch takes at most 2^31-1 candidates; minimum under the same order)
+                auto device = [&](auto zero, auto multi, auto create, auto search, auto keyof) {
+                    decltype(zero) b{};
+                    int rc;
+                    if (o.gpu >= 2) {
+                        std::vector<int> devs((size_t)o.gpu); for (int j = 0; j < o.gpu; ++j) devs[(size_t)j] = shard_device(j);
+                        rc = multi(devs.data(), &b, &st);
+                    } else {
+                        rc = H.init(0);
+                        plo_orbit_plan_t *plan = nullptr;
+                        if (rc == PLO_OK) rc = create(&plan);
+                        for (uint64_t done = 0; rc == PLO_OK && done < o.loops;) {
+                            const uint64_t piece = std::min<uint64_t>(o.loops - done, (1ull << 31) - 1ull);
+                            decltype(zero) pb{}; plo_stats_t ps{};
+                            rc = search(plan, o.seed0 + done, piece, &pb, &ps);
+                            if (rc != PLO_OK) break;
+                            if (done == 0 || keyof(pb) < keyof(b)) b = pb;
+                            st.kernel_ms += ps.kernel_ms;
+                            done += piece;
+                        }
+                        if (plan) H.destroy(plan);
                     }
-                    if (plan) H.destroy(plan);
-                }
+                    if (rc == PLO_OK) dbest = std::tuple_cat(keyof(b), std::make_tuple((uint64_t)b.seed));
+                    return rc;
+                };
+                const int rc = o.growth
+                    ? device(plo_orbit_gbest_t{},
+                             [&](const int *devs, plo_orbit_gbest_t *b, plo_stats_t *s) { return H.search_multi_growth(&l, &r, &p, o.action, o.seed0, o.loops, o.gpu, devs, b, s); },
+                             [&](plo_orbit_plan_t **plan) { return H.create_growth(&l, &r, &p, o.action, plan); }, H.search_growth,
+                             [](const plo_orbit_gbest_t &x) { return std::make_tuple(growth_bits(x.cost), (size_t)x.nnz, (size_t)x.nno); })
+                    : device(plo_orbit_best_t{},
+                             [&](const int *devs, plo_orbit_best_t *b, plo_stats_t *s) {
+                                 return o.cse ? H.search_multi_cse(&l, &r, &p, modulus, o.action, (uint32_t)z.sub, z.seed0, o.seed0, o.loops, o.gpu, devs, b, s)
+                                              : H.search_multi(&l, &r, &p, modulus, measure, o.action, o.seed0, o.loops, o.gpu, devs, b, s); },
+                             [&](plo_orbit_plan_t **plan) { return o.cse ? H.create_cse(&l, &r, &p, modulus, o.action, (uint32_t)z.sub, z.seed0, plan) : H.create(&l, &r, &p, modulus, measure, o.action, plan); },
+                             H.search, [](const plo_orbit_best_t &x) { return std::make_tuple((size_t)x.cost, (size_t)x.nnz, (size_t)x.nno); });
                 if (rc == PLO_E_UNSUPPORTED || rc == PLO_E_CAPACITY) { refused = true; why = H.last_error(); }
                 else if (rc != PLO_OK) { std::cerr << "# \033[1;31mERROR: " << H.last_error() << "\033[0m\n"; return 2; }
                 else {
                     on_gpu = true; kms = st.kernel_ms; have = true;
                     if (o.gpu >= 2) std::clog << "# " << o.gpu << " shards (one GPU and one host thread each, one process)" << std::endl;
-                    best = Key{b.cost, b.nnz, b.nno, b.seed};
+                    best = dbest;
                 }
             }
         }
@@ -161,16 +188,16 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
         OrbitTriple<F> W;
         const OrbitCount rc = orbit_candidate(f, T, seed, measure, o.action, &W, z);
         if (!(rc == bc)) {
-            std::cerr << "# \033[1;31mERROR: replay of seed " << seed << " gives " << rc.cost << ' ' << rc.nnz << ' ' << rc.nno << ", search said " << bc.cost << ' ' << bc.nnz << ' ' << bc.nno << "\033[0m\n";
+            std::cerr << "# \033[1;31mERROR: replay of seed " << seed << " gives " << cost_text(measure, rc.cost, true) << ' ' << rc.nnz << ' ' << rc.nno << ", search said " << cost_text(measure, bc.cost, true) << ' ' << bc.nnz << ' ' << bc.nno << "\033[0m\n";
             return 3;
         }
-        std::clog << "# \033[1;36mRdcd. opt: " << bc.cost << '<' << init.cost << "\t(" << bc.nnz << ',' << bc.nno << ")\033[0m" << std::endl;
+        std::clog << "# \033[1;36mRdcd. opt: " << cost_text(measure, bc.cost) << '<' << cost_text(measure, init.cost) << "\t(" << bc.nnz << ',' << bc.nno << ")\033[0m" << std::endl;
         const int winner_bad = mm_report(f, W);
         if (winner_bad && !input_bad) { std::cerr << "# \033[1;31mERROR: the winner of a correct input fails the check: nothing written\033[0m\n"; return 3; }
         write_triple(f, W, nnz_name(files[0]), nnz_name(files[1]), nnz_name(files[2]), modulus ? 'M' : 'R');
-        std::cout << "winner " << bc.cost << ' ' << bc.nnz << ' ' << bc.nno << ' ' << seed << std::endl;
+        std::cout << "winner " << cost_text(measure, bc.cost, true) << ' ' << bc.nnz << ' ' << bc.nno << ' ' << seed << std::endl;
     } else {
-        std::cout << "winner " << init.cost << ' ' << init.nnz << ' ' << init.nno << " base" << std::endl;
+        std::cout << "winner " << cost_text(measure, init.cost, true) << ' ' << init.nnz << ' ' << init.nno << " base" << std::endl;
     }
     std::clog << "# " << o.loops << " restarts on " << (on_gpu ? "GPU" : "host") << " in " << dt << " s";
     if (on_gpu) std::clog << " (kernel " << kms << " ms)";
@@ -206,12 +233,13 @@ QMat read_file(const std::string &f) {
 }
 
 int usage(const char *prg, const Opts &o) {
-    std::clog << "Usage: " << prg << " [-b #] [-m|-q #] [-r # # #] [-s|-c|-z] [--sub #] [-O #] [--seed s] [--gpu 0|1|N] [--action a] L.sms R.sms P.sms\n"
+    std::clog << "Usage: " << prg << " [-b #] [-m|-q #] [-r # # #] [-s|-c|-z|-g] [--sub #] [-O #] [--seed s] [--gpu 0|1|N] [--action a] L.sms R.sms P.sms\n"
               << "  [-b b]: accepted (the matrix-multiplication checks are exact)\n"
               << "  [-m/-q m]: search modulo m without its factors 2 (default Q)\n"
               << "  [-r r e s]: search modulo (r^e-s) without its factors 2\n"
               << "  [-s|-c]: search sparser|canonical (default sparser; always sparser modulo a number)\n"
               << "  [-z]: search faster: the operations of the best programs found (needs a prime modulus; -q 2147483629 stands for Q)\n"
+              << "  [-g]: search more accurate: the 2-norm growth factor (over Q; triangular or pluq action)\n"
               << "  [--sub n]: Optimizer runs per matrix with -z (default loops/16, at least 1)\n"
               << "  [-O #]: randomized search with that many loops (default " << o.loops << " loops)\n"
               << "  [--seed s]: candidates s .. s+O-1 (default 0); [--gpu 0|1|N]: host loop, one GPU, N GPU shards (default 1)\n"
@@ -251,6 +279,7 @@ int main(int argc, char **argv) {
             else if (a == "-s") { o.measure = ORBIT_DENSITY; o.cse = false; }
             else if (a == "-c") { o.measure = ORBIT_CANONICAL; o.cse = false; }
             else if (a == "-z") o.cse = true;
+            else if (a == "-g") o.growth = true;
             else if (a == "--sub") { need(1); o.sub = (size_t)strtoull(argv[++i], nullptr, 10); if (o.sub == 0 || o.sub > 65536) return refuse("--sub needs a number in 1 .. 65536"); }
             else if (a == "--seed") { need(1); o.seed0 = strtoull(argv[++i], nullptr, 10); }
             else if (a == "--gpu") { need(1); o.gpu = atoi(argv[++i]); }
@@ -273,6 +302,9 @@ int main(int argc, char **argv) {
         if (o.modulus > ((unsigned __int128)1 << 63)) return refuse("modulus above 2^63");
         modulus = (uint64_t)o.modulus;
     }
+    if (o.growth && o.modulus > 0) return refuse("-g (the 2-norm growth factor) is defined over Q only: not with -m, -q or -r");
+    if (o.growth && o.cse) return refuse("-g and -z are two measures: choose one");
+    if (o.growth && o.action == ORBIT_ACT_HOUSEHOLDER) return refuse("-g with --action householder: an orthogonal action preserves the 2-norm growth factor, there is nothing to search");
     if (o.cse && !modulus) return refuse("-z (CSE counts per candidate) is not supported over Q");
     if (o.cse && !is_prime(modulus)) return refuse("-z needs a prime modulus, " + std::to_string(modulus) + " is composite");
     try {

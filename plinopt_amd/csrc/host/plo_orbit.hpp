@@ -11,10 +11,11 @@
 // ==========================================================================
 #pragma once
 #include "plo_host.hpp"
+#include <cmath>
 
 namespace plo {
 
-enum { ORBIT_DENSITY = 0, ORBIT_CSE = 1, ORBIT_CANONICAL = 2 };
+enum { ORBIT_DENSITY = 0, ORBIT_CSE = 1, ORBIT_CANONICAL = 2, ORBIT_GROWTH = 3 };
 // ORBIT_CSE (`-z`): every part is scored by min(naiveOps, the best of `sub` Optimizer runs with the streams seed0 .. seed0 + sub - 1)
 struct OrbitCse { size_t sub = 1; uint64_t seed0 = 0; };
 enum { ORBIT_ACT_TRIANGULAR = 0, ORBIT_ACT_PLUQ = 1, ORBIT_ACT_HOUSEHOLDER = 2 };
@@ -136,18 +137,42 @@ inline bool orbit_shape(size_t lm, size_t ln, size_t rm, size_t rn, size_t pm, s
     return m * k == ln && k * n == rn && m * n == pm;
 }
 
+// (ORBIT_GROWTH: cost holds the 64-bit pattern of the growth factor, a non-negative finite double: the orders below are the numeric ones)
 struct OrbitCount { size_t cost = 0, nnz = 0, nno = 0; };
+static_assert(sizeof(size_t) == 8 && sizeof(double) == 8, "the growth factor travels as its bits in OrbitCount::cost");
+inline size_t growth_bits(double g) { uint64_t b; memcpy(&b, &g, 8); return (size_t)b; }
+inline double growth_value(size_t bits) { const uint64_t b = bits; double g; memcpy(&g, &b, 8); return g; }
 inline bool operator<(const OrbitCount &a, const OrbitCount &b) { return std::tie(a.cost, a.nnz, a.nno) < std::tie(b.cost, b.nnz, b.nno); }
 inline bool operator==(const OrbitCount &a, const OrbitCount &b) { return std::tie(a.cost, a.nnz, a.nno) == std::tie(b.cost, b.nnz, b.nno); }
 
 // The triple over F, P kept as its transpose (the columns of P are what the sandwich transforms)
 template <class F> struct OrbitTriple { SparseMat<typename F::Elt> L, R, PT; size_t m = 0, k = 0, n = 0; };
 
+// n_g of PLO_ORBIT_GROWTH (include/plinopt_hip.h) for one transformed row: `in` is the input row, whose denominators give the
+// scale c_g, `acc` its outputs.  S_g = sum (acc c_g)^2 as an exact 128-bit integer, then sqrt(double(S_g)) / double(c_g): the
+// device's operations in the device's order (it takes the inputs whose S_g and c_g stay below 2^53, where both conversions are
+// exact; beyond that each is one rounding to nearest here).  A sum that leaves 128 bits is an overflow.
+inline double orbit_row_norm(const QField &, const SparseMat<Rat>::Row &in, const std::vector<Rat> &acc) {
+    __int128 l = 1;
+    for (const auto &e : in) l = Rat::mulck(l / Rat::gcd(l, e.second.d), e.second.d);
+    unsigned __int128 S = 0;
+    for (const Rat &a : acc) {
+        if (a.n == 0) continue;
+        if (l % a.d) throw std::logic_error("growth measure: an output is no multiple of 1/scale");
+        const __int128 v = Rat::mulck(a.n, l / a.d);
+        const unsigned __int128 u = v < 0 ? (unsigned __int128)(-v) : (unsigned __int128)v;
+        if (u >> 63 || __builtin_add_overflow(S, u * u, &S)) throw std::overflow_error("growth measure: sum of squares beyond 128 bits");
+    }
+    const double s = std::sqrt((double)S), c = (double)l;
+    return s / c;
+}
+template <class F, class Row, class Acc> double orbit_row_norm(const F &, const Row &, const Acc &) { throw std::logic_error("the growth measure is defined over Q only"); }
+
 // one part of the sandwich: out_i(p, q) = sum over the entries (a, b, x) of row i of A[a][p] x B[b][q], for the rows of X
 // (columns a * cb + b; output pr x qc); A is sa x sa over the denominator da, B is sb x sb over db (row-major); Out gets the
-// rows when asked
+// rows when asked, norms the rows' 2-norms (ORBIT_GROWTH)
 template <class F> void orbit_part(const F &f, const SparseMat<typename F::Elt> &X, size_t cb, const std::vector<int64_t> &A, int64_t da, size_t sa,
-                                   const std::vector<int64_t> &B, int64_t db, size_t sb, OrbitCount &c, size_t &canon, SparseMat<typename F::Elt> *Out) {
+                                   const std::vector<int64_t> &B, int64_t db, size_t sb, OrbitCount &c, size_t &canon, SparseMat<typename F::Elt> *Out, std::vector<double> *norms = nullptr) {
     using E = typename F::Elt;
     std::vector<E> acc(sa * sb);
     std::vector<E> Af(A.size()), Bf(B.size());
@@ -171,6 +196,7 @@ template <class F> void orbit_part(const F &f, const SparseMat<typename F::Elt> 
             if (Out) Out->rows[i].emplace_back(t, acc[t]);
         }
         c.nnz += nz; canon += nz == 1;
+        if (norms) norms->push_back(orbit_row_norm(f, X.rows[i], acc));
     }
 }
 
@@ -194,7 +220,7 @@ template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &
 template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &T, uint64_t seed, int measure, int action, const OrbitCse &z) { return orbit_candidate(f, T, seed, measure, action, (OrbitTriple<F> *)nullptr, z); }
 
 // counts of candidate `seed` (cost = nnz, or L.m + R.m + P.n - the rows with one non-zero for ORBIT_CANONICAL, or the operations
-// of the best programs found for ORBIT_CSE); the three transformed matrices (P transposed back) when out is given
+// of the best programs found for ORBIT_CSE, or the bits of the 2-norm growth factor for ORBIT_GROWTH, over Q); the three transformed matrices (P transposed back) when out is given
 template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &T, uint64_t seed, int measure, int action, OrbitTriple<F> *out, const OrbitCse &z) {
     OrbitTriple<F> mine;
     if (measure == ORBIT_CSE && !out) out = &mine;
@@ -202,11 +228,18 @@ template <class F> OrbitCount orbit_candidate(const F &f, const OrbitTriple<F> &
     const size_t m = T.m, k = T.k, n = T.n;
     auto tr = [](const std::vector<int64_t> &M, size_t s) { std::vector<int64_t> R(s * s); for (size_t i = 0; i < s; ++i) for (size_t j = 0; j < s; ++j) R[j * s + i] = M[i * s + j]; return R; };
     OrbitCount r; size_t canon = 0;
-    orbit_part(f, T.L, k, c.U.Mi, c.U.den, m, c.V.M, c.V.den, k, r, canon, out ? &out->L : nullptr);                  // U^-T X V: A[a][p] = U^-1[a][p]
-    orbit_part(f, T.R, n, tr(c.V.Mi, k), c.V.den, k, c.W.M, c.W.den, n, r, canon, out ? &out->R : nullptr);           // V^-1 Y W: A[b][p] = V^-1[p][b]
-    orbit_part(f, T.PT, n, tr(c.U.M, m), c.U.den, m, tr(c.W.Mi, n), c.W.den, n, r, canon, out ? &out->PT : nullptr);  // U Z W^-T: A[a][p] = U[p][a], B[c][q] = W^-1[q][c]
+    std::vector<double> nl, nr, np;                                                        // ORBIT_GROWTH: the 2-norms of the transformed rows
+    const bool growth = measure == ORBIT_GROWTH;
+    orbit_part(f, T.L, k, c.U.Mi, c.U.den, m, c.V.M, c.V.den, k, r, canon, out ? &out->L : nullptr, growth ? &nl : nullptr);                  // U^-T X V: A[a][p] = U^-1[a][p]
+    orbit_part(f, T.R, n, tr(c.V.Mi, k), c.V.den, k, c.W.M, c.W.den, n, r, canon, out ? &out->R : nullptr, growth ? &nr : nullptr);           // V^-1 Y W: A[b][p] = V^-1[p][b]
+    orbit_part(f, T.PT, n, tr(c.U.M, m), c.U.den, m, tr(c.W.Mi, n), c.W.den, n, r, canon, out ? &out->PT : nullptr, growth ? &np : nullptr);  // U Z W^-T: A[a][p] = U[p][a], B[c][q] = W^-1[q][c]
     r.cost = measure == ORBIT_CANONICAL ? T.L.rowdim() + T.R.rowdim() + T.PT.rowdim() - canon : r.nnz;
     if (measure == ORBIT_CSE) r.cost = orbit_cse_cost(f, out->L, z) + orbit_cse_cost(f, out->R, z) + orbit_cse_cost(f, transpose(out->PT), z);
+    if (growth) {                                                                          // one product pair and one addition per i, in increasing i
+        double g = 0.0;
+        for (size_t i = 0; i < nl.size(); ++i) { const double lr = nl[i] * nr[i], t = lr * np[i]; g = g + t; }
+        r.cost = growth_bits(g);
+    }
     if (out) { out->m = m; out->k = k; out->n = n; }
     return r;
 }

@@ -16,6 +16,7 @@
 #include "plo_lin.hip"
 #include "plo_orbit.hip"
 #include "plo_orbit_cse.hip"
+#include "plo_orbit_growth.hip"
 #include "plo_dep.hip"
 #include "../../include/plinopt_hip.h"
 
@@ -2152,6 +2153,9 @@ struct plo_orbit_plan {
     uint32_t *d_err = nullptr;
     uint32_t cse_scale = 1, cse_relaunches = 0;        // tables: scale x the sampled size; launches repeated for a full table
     uint32_t cse_ent[3] = {0, 0, 0}, cse_pairs[3] = {0, 0, 0};   // maxima over the sizing sample, per part
+    // PLO_ORBIT_GROWTH (plo_orbit_growth.hip): the 3r sums behind a wave's region (zero on the other plans); d_best then has three words per wave slot
+    bool growth = false;
+    uint32_t g_off_sum = 0, g_wave_bytes = 0;
 };
 
 namespace {
@@ -2198,6 +2202,8 @@ orbit_cse_fn_t orbit_cse_fn(int action, bool size) {
     default: return size ? plo::orbit_cse_kernel<0, true> : plo::orbit_cse_kernel<0, false>;
     }
 }
+using orbit_growth_fn_t = void (*)(plo::OrbitPlan, plo::OrbitGrowthJob);
+orbit_growth_fn_t orbit_growth_fn(int action) { return action == PLO_ORBIT_ACT_PLUQ ? plo::orbit_growth_kernel<1> : plo::orbit_growth_kernel<0>; }
 enum { ORBIT_AGAIN = 1 };            // orbit_launch: a table was full, the plan has larger ones now: launch again
 
 // deterministic Miller-Rabin below 2^32 (bases 2, 7, 61)
@@ -2317,6 +2323,15 @@ int orbit_launch(plo_orbit_plan *pl, plo::OrbitJob J, plo_stats_t *st) {
     return PLO_OK;
 }
 
+int orbit_growth_launch(plo_orbit_plan *pl, plo::OrbitGrowthJob J, plo_stats_t *st) {
+    const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(pl->grid_max, need));
+    J.off_sum = pl->g_off_sum; J.wave_bytes = pl->g_wave_bytes;
+    return timed_launch(pl, grid, J.ncand, st, [&] {
+        hipLaunchKernelGGL(orbit_growth_fn(pl->action), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+    });
+}
+
 // |entries| of the two factors of a part, a direct one of size sd and an inverse of size si, multiplied:
 // triangular 1 x 2^(si-2); PLUQ sd x si 4^(si-2); Householder (numerators over d <= s) sd x si
 __int128 orbit_factor_bound(int action, uint32_t sd, uint32_t si) {
@@ -2338,6 +2353,8 @@ int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
 int plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, plo_orbit_plan_t **plan)
 {
     if (measure == PLO_ORBIT_CSE) return fail(PLO_E_ARG, "PLO_ORBIT_CSE needs sub and cse_seed0: plo_orbit_plan_create_cse");
+    // (the growth factor has its own create function; here the measure is refused with the words every unknown measure gets)
+    if (measure == PLO_ORBIT_GROWTH) return fail(PLO_E_ARG, !L || !R || !P || !plan ? "null argument" : "measure must be PLO_ORBIT_DENSITY or PLO_ORBIT_CANONICAL");
     return orbit_plan_build(L, R, P, modulus, measure, action, 0, 0, plan);
 }
 
@@ -2347,6 +2364,13 @@ int plo_orbit_plan_create_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const pl
     if (modulus == 0 || !(modulus & 1) || modulus >= (1ull << 31) || !is_prime32(modulus)) return fail(PLO_E_ARG, "the CSE measure needs an odd prime modulus below 2^31");
     if (sub == 0 || sub > 65536u) return fail(PLO_E_ARG, "sub outside [1, 65536]");
     return orbit_plan_build(L, R, P, modulus, PLO_ORBIT_CSE, action, sub, cse_seed0, plan);
+}
+
+int plo_orbit_plan_create_growth(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, int action, plo_orbit_plan_t **plan)
+{
+    if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
+    if (action == PLO_ORBIT_ACT_HOUSEHOLDER) return fail(PLO_E_ARG, "the Householder action is orthogonal and preserves the 2-norm growth factor: there is nothing to search");
+    return orbit_plan_build(L, R, P, 0, PLO_ORBIT_GROWTH, action, 0, 0, plan);
 }
 
 int plo_orbit_plan_info(plo_orbit_plan_t *pl, uint32_t out[8])
@@ -2364,9 +2388,9 @@ int plo_orbit_plan_info(plo_orbit_plan_t *pl, uint32_t out[8])
 // the body of the create functions; sub > 0: a PLO_ORBIT_CSE plan
 static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan)
 {
-    const bool cse = measure == PLO_ORBIT_CSE;
+    const bool cse = measure == PLO_ORBIT_CSE, growth = measure == PLO_ORBIT_GROWTH;
     if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
-    if (!cse && measure != PLO_ORBIT_DENSITY && measure != PLO_ORBIT_CANONICAL) return fail(PLO_E_ARG, "measure must be PLO_ORBIT_DENSITY or PLO_ORBIT_CANONICAL");
+    if (!cse && !growth && measure != PLO_ORBIT_DENSITY && measure != PLO_ORBIT_CANONICAL) return fail(PLO_E_ARG, "measure must be PLO_ORBIT_DENSITY or PLO_ORBIT_CANONICAL");
     if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
     if (action != PLO_ORBIT_ACT_TRIANGULAR && action != PLO_ORBIT_ACT_PLUQ && action != PLO_ORBIT_ACT_HOUSEHOLDER) return fail(PLO_E_ARG, "action must be one of PLO_ORBIT_ACT_*");
     if (modulus == 1) return fail(PLO_E_ARG, "modulus 1");
@@ -2424,6 +2448,14 @@ static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
                 if (l1 * fb >= ((__int128)1 << 62)) return fail(PLO_E_UNSUPPORTED, "row L1 norm times the entry bounds of the action's factors reaches 2^62 (int64 bound): host path only");
                 if (action == PLO_ORBIT_ACT_HOUSEHOLDER && l * fb >= ((__int128)1 << 62)) return fail(PLO_E_UNSUPPORTED, "row scale times the Householder denominators reaches 2^62 (int64 bound): host path only");
             }
+            if (growth) {
+                // S_g <= E_g B_g^2 < 2^53 and c_g < 2^53: double(S_g) and double(c_g) are exact (B_g: the bound on |acc| checked above)
+                const __int128 B = action == PLO_ORBIT_ACT_TRIANGULAR ? l1 << (s >= 2 ? s - 2 : 0) : l1 * orbit_factor_bound(action, dir_size[g / r], s);
+                const uint32_t E = inv_size[g / r] * dir_size[g / r];
+                if (B >= ((__int128)1 << 27) || (__int128)E * B * B >= ((__int128)1 << 53))
+                    return fail(PLO_E_UNSUPPORTED, "growth measure: a row's outputs times its squared entry bound reach 2^53 (exact double sums): host path only");
+                if (l >= ((__int128)1 << 53)) return fail(PLO_E_UNSUPPORTED, "growth measure: a row scale of 2^53 or more: host path only");
+            }
             scale[g] = (int64_t)l;
         }
         rp.push_back((uint32_t)val.size());
@@ -2450,12 +2482,14 @@ static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
         Q.off_t2 = off; off += round_up(smax * smax, 16);
     }
     Q.off_perm = off; off += 32;
-    Q.off_cnt = off; off += round_up(2u * nrows + 2u, 16);
+    Q.off_cnt = off; if (!growth) off += round_up(2u * nrows + 2u, 16);      // (the growth kernel counts no rows)
     Q.lds_per_wave = off;
     pl->algo_bytes = 10ull * nnz + 12ull * nrows;
     pl->action = action;
+    pl->growth = growth;
+    if (growth) { pl->g_off_sum = round_up(Q.lds_per_wave, 16); pl->g_wave_bytes = pl->g_off_sum + round_up(24u * r, 16); }       // the 3r sums of squares
     if (!cse) {
-        pl->waves_per_wg = pick_waves([&](uint32_t w) { return Q.shared_bytes + w * Q.lds_per_wave; }, false, std::min<size_t>(g_lds_max, 64u * 1024u), &pl->lds_bytes);
+        pl->waves_per_wg = pick_waves([&](uint32_t w) { return Q.shared_bytes + w * (growth ? pl->g_wave_bytes : Q.lds_per_wave); }, false, std::min<size_t>(g_lds_max, 64u * 1024u), &pl->lds_bytes);
         if (!pl->waves_per_wg) { delete pl; return fail(PLO_E_CAPACITY, "input does not fit LDS"); }
         pl->blocks_per_cu = blocks_per_cu(pl->waves_per_wg, pl->lds_bytes);
         pl->grid_max = (uint32_t)g_cus * pl->blocks_per_cu;
@@ -2468,9 +2502,9 @@ static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
             if (gcd64((int64_t)d, (int64_t)modulus) == 1) { const uint32_t v = inv_mod((uint32_t)(d % modulus), (uint32_t)modulus); memcpy(img.data() + Q.off_dinv + 4u * d, &v, 4); }
     memcpy(img.data(), val.data(), 8u * nnz); memcpy(img.data() + Q.off_scale, scale.data(), 8u * nrows);
     memcpy(img.data() + Q.off_rp, rp.data(), 4u * (nrows + 1u)); memcpy(img.data() + Q.off_pos, pos.data(), 2u * nnz);
-    const void *fn = (const void *)orbit_fn(modulus != 0, action);
+    const void *fn = growth ? (const void *)orbit_growth_fn(action) : (const void *)orbit_fn(modulus != 0, action);
     if (hipMalloc(&pl->d_img, bytes) != hipSuccess || hipMemcpy(pl->d_img, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
-        (!cse && (hipMalloc((void **)&pl->d_best, 16ull * pl->grid_max * pl->waves_per_wg) != hipSuccess ||
+        (!cse && (hipMalloc((void **)&pl->d_best, (growth ? 24ull : 16ull) * pl->grid_max * pl->waves_per_wg) != hipSuccess ||
                   hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes) != hipSuccess))) {
         plo_orbit_plan_destroy(pl); return fail(PLO_E_HIP, "device setup of the orbiter plan failed");
     }
@@ -2506,6 +2540,7 @@ void plo_orbit_plan_destroy(plo_orbit_plan_t *pl)
 
 int plo_orbit_cost_many(plo_orbit_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *out3, plo_stats_t *stats)
 {
+    if (pl && pl->growth) return fail(PLO_E_ARG, "a growth plan: its cost is a double, plo_orbit_growth_many returns it");
     return cost_many_run(pl, seeds, n, 3, out3, stats, [&](uint32_t *d_out, const uint64_t *d_seeds, plo_stats_t *st) {
         plo::OrbitJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.out3 = d_out; J.best = nullptr;
         int rc;
@@ -2518,6 +2553,7 @@ int plo_orbit_search(plo_orbit_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_
 {
     if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
     if (!pl || !best) return fail(PLO_E_ARG, "null argument");
+    if (pl->growth) return fail(PLO_E_ARG, "a growth plan: its cost is a double, plo_orbit_growth_search returns it");
     if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
     plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
     const auto t0 = std::chrono::steady_clock::now();
@@ -2563,6 +2599,57 @@ int plo_orbit_search_multi_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const p
     return sharded_search(seed0, nseeds, ndev, devices, best, stats,
         [&](plo_orbit_plan_t **plan) { return plo_orbit_plan_create_cse(L, R, P, modulus, action, sub, cse_seed0, plan); }, plo_orbit_search, plo_orbit_plan_destroy,
         [&](const plo_orbit_best_t &pb) { return std::make_pair(((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, pb.seed - seed0); });
+}
+
+int plo_orbit_growth_many(plo_orbit_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, double *cost, uint32_t *nnz_nno, plo_stats_t *stats)
+{
+    if (!pl || !cost || !nnz_nno) return fail(PLO_E_ARG, "null argument");
+    if (!pl->growth) return fail(PLO_E_ARG, "not a plan of plo_orbit_plan_create_growth");
+    if (n >= (1ull << 31)) return fail(PLO_E_ARG, "at most 2^31-1 candidates per call");
+    std::vector<uint32_t> w(4u * n + 1u);                 // the device buffer of the shared helper: n doubles, then 2n counts
+    const int rc = cost_many_run(pl, seeds, n, 4, w.data(), stats, [&](uint32_t *d_out, const uint64_t *d_seeds, plo_stats_t *st) {
+        plo::OrbitGrowthJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.cost = (double *)d_out; J.cnt2 = d_out + 2u * n; J.best = nullptr;
+        return orbit_growth_launch(pl, J, st);
+    });
+    if (rc == PLO_OK && n) { memcpy(cost, w.data(), 8u * n); memcpy(nnz_nno, w.data() + 2u * n, 8u * n); }
+    return rc;
+}
+
+int plo_orbit_growth_search(plo_orbit_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_orbit_gbest_t *best, plo_stats_t *stats)
+{
+    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (!pl || !best) return fail(PLO_E_ARG, "null argument");
+    if (!pl->growth) return fail(PLO_E_ARG, "not a plan of plo_orbit_plan_create_growth");
+    if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
+    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t slots = (uint64_t)pl->grid_max * pl->waves_per_wg;
+    HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, 24 * slots, g_stream));
+    plo::OrbitGrowthJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.cost = nullptr; J.cnt2 = nullptr; J.best = pl->d_best;
+    const int rc = orbit_growth_launch(pl, J, st);
+    if (rc != PLO_OK) return rc;
+    std::vector<uint64_t> w(3 * slots);
+    HIPCHK(hipMemcpy(w.data(), pl->d_best, 24 * slots, hipMemcpyDeviceToHost));
+    std::array<uint64_t, 3> b{~0ull, ~0ull, ~0ull};       // (bits of the cost, nnz << 21 | nno, candidate): the lexicographic minimum
+    for (uint64_t s = 0; s < slots; ++s) {
+        const std::array<uint64_t, 3> c{w[3 * s], w[3 * s + 1], w[3 * s + 2]};
+        if (c[2] != ~0ull && c < b) b = c;
+    }
+    if (b[2] == ~0ull) return fail(PLO_E_INTERNAL, "no candidate reported");
+    memcpy(&best->cost, &b[0], 8); best->nnz = (uint32_t)(b[1] >> 21) & 0x1FFFFFu; best->nno = (uint32_t)b[1] & 0x1FFFFFu;
+    best->seed = seed0 + b[2];
+    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return PLO_OK;
+}
+
+int plo_orbit_growth_search_multi(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, int action,
+                                  uint64_t seed0, uint64_t nseeds, int ndev, const int *devices, plo_orbit_gbest_t *best, plo_stats_t *stats)
+{
+    if (!L || !R || !P || !best) return fail(PLO_E_ARG, "null argument");
+    // (cost bits, nnz, nno); the shards are blocks of increasing seeds and equal words keep the lower shard: the smaller seed
+    return sharded_search(seed0, nseeds, ndev, devices, best, stats,
+        [&](plo_orbit_plan_t **plan) { return plo_orbit_plan_create_growth(L, R, P, action, plan); }, plo_orbit_growth_search, plo_orbit_plan_destroy,
+        [&](const plo_orbit_gbest_t &pb) { unsigned long long bits; memcpy(&bits, &pb.cost, 8); return std::make_pair(bits, ((unsigned long long)pb.nnz << 21) | pb.nno); });
 }
 
 } // extern "C"

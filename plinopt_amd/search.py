@@ -380,7 +380,7 @@ def lin_search_multi(m, n, rowptr, col, num, den, seed0, nseeds, devices):
 
 
 ORBIT_BASE_SEED = (1 << 64) - 1
-ORBIT_DENSITY, ORBIT_CSE, ORBIT_CANONICAL = 0, 1, 2
+ORBIT_DENSITY, ORBIT_CSE, ORBIT_CANONICAL, ORBIT_GROWTH = 0, 1, 2, 3
 ORBIT_ACT_TRIANGULAR, ORBIT_ACT_PLUQ, ORBIT_ACT_HOUSEHOLDER = 0, 1, 2
 
 
@@ -450,6 +450,55 @@ def orbit_search_multi(L, R, P, modulus, measure, seed0, nseeds, devices, action
         capi.check(lib.plo_orbit_search_multi_cse(*[ctypes.byref(c) for c, _ in csr], modulus, action, sub, cse_seed0, seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
     else:
         capi.check(lib.plo_orbit_search_multi_act(*[ctypes.byref(c) for c, _ in csr], modulus, measure, action, seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
+    del csr
+    return ((b.cost, b.nnz, b.nno), b.seed), st.as_dict()
+
+
+class OrbitGrowthPlan(OrbitPlan):
+    """The orbit search scored by the 2-norm growth factor (`plo_orbit_plan_create_growth`, bin/orbiter -g; PLO_ORBIT_GROWTH of
+    include/plinopt_hip.h): over Q, action ORBIT_ACT_TRIANGULAR or ORBIT_ACT_PLUQ.  `growth_many` returns (cost, nnz, nno) per
+    seed, the cost a float whose bits are part of the definition; `growth_search` the best ((cost, nnz, nno), seed) under
+    (bits of the cost, nnz, nno, seed).  `cost_many` and `search` of the parent raise PLO_E_ARG on such a plan."""
+
+    def __init__(self, L, R, P, device=None, action=ORBIT_ACT_TRIANGULAR):
+        lib = capi.lib()
+        if device is not None:
+            capi.check(lib.plo_init(device))
+        self._h = None
+        self._csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
+        h = ctypes.c_void_p()
+        capi.check(lib.plo_orbit_plan_create_growth(*[ctypes.byref(c) for c, _ in self._csr], action, ctypes.byref(h)))
+        self._h = h
+        self.last_stats = None
+
+    def growth_many(self, seeds=None, seed0=0, n=0):
+        lib = capi.lib()
+        if seeds is not None:
+            n = len(seeds); sp = (ctypes.c_uint64 * max(n, 1))(*seeds)
+        else:
+            sp = None
+        cost = (ctypes.c_double * max(n, 1))()
+        cnt = (ctypes.c_uint32 * (2 * max(n, 1)))()
+        st = capi.Stats()
+        capi.check(lib.plo_orbit_growth_many(self._h, sp, seed0, n, cost, cnt, ctypes.byref(st)))
+        self.last_stats = st.as_dict()
+        return [(cost[k], cnt[2 * k], cnt[2 * k + 1]) for k in range(n)]
+
+    def growth_search(self, seed0, nseeds):
+        b, st = capi.OrbitGBest(), capi.Stats()
+        capi.check(capi.lib().plo_orbit_growth_search(self._h, seed0, nseeds, ctypes.byref(b), ctypes.byref(st)))
+        self.last_stats = st.as_dict()
+        return (b.cost, b.nnz, b.nno), b.seed
+
+
+def orbit_growth_search_multi(L, R, P, seed0, nseeds, devices, action=ORBIT_ACT_TRIANGULAR):
+    """`plo_orbit_growth_search_multi`: the growth-factor orbit search over the listed devices from this process.
+    Returns (((cost, nnz, nno), seed), stats)."""
+    lib = capi.lib()
+    csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
+    dv = (ctypes.c_int * len(devices))(*devices)
+    b, st = capi.OrbitGBest(), capi.Stats()
+    capi.check(lib.plo_orbit_growth_search_multi(*[ctypes.byref(c) for c, _ in csr], action, seed0, nseeds, len(devices), dv, ctypes.byref(b), ctypes.byref(st)))
     del csr
     return ((b.cost, b.nnz, b.nno), b.seed), st.as_dict()
 
