@@ -308,6 +308,11 @@ int build_plan(plo_plan *pl, std::vector<uint8_t> *img_out = nullptr)
     pl->algo_bytes = 8ull * nnz + 12ull * pairs0 + 8ull;   // B_cand, SURVEY.md 8(d)
     uint32_t cap = 64;
     while (cap < (pl->cap_scale * (uint32_t)pm.size() * 3u) / 4u + 16u) cap <<= 1;   // 1.5x the initial triples (cap_scale starts at 2); a full table is detected on the device and the launch repeated with more
+    if (env_knob("PLO_WAVE_CAP_TIGHT")) {   // test knob: the first table just holds the initial triples and one empty slot (the insertion loop below ends), so that
+        cap = 64;                           // a candidate whose live triples grow takes the repeat path; 64 slots at least, the kernel scans the table a wave at a time
+        while (cap < (uint32_t)pm.size() + 1u) cap <<= 1;
+        cap *= pl->cap_scale / 2u;          // cap_scale doubles per repeat as above
+    }
     const uint32_t hbits = ceil_log2(cap);
 
     P.m = m; P.n = n; P.nnz = nnz; P.p = p; P.NC = (uint32_t)NC; P.cap = cap; P.hbits = hbits;
@@ -783,6 +788,20 @@ int device_error(int err) {
     }
 }
 
+// Twice the slots for a plan whose launch met a full table.  A table that no longer fits (LDS, 65536 slots) is refused with
+// PLO_E_CAPACITY and the plan stays as it was: build_plan clears the plan it fails on, and the next call would launch that.
+int grow_plan(plo_plan *pl)
+{
+    pl->cap_scale *= 2;
+    const int rc = build_plan(pl);
+    if (rc != PLO_E_CAPACITY) return rc;
+    const std::string why = g_err;
+    pl->cap_scale /= 2;
+    const int back = build_plan(pl);
+    if (back != PLO_OK) return back;
+    return fail(PLO_E_CAPACITY, "pair table full, and with twice the slots: " + why);
+}
+
 // run a job, growing the pair table when the device reports it full
 int run_job(plo_plan *pl, plo::WaveJob J, plo_stats_t *st)
 {
@@ -791,8 +810,7 @@ int run_job(plo_plan *pl, plo::WaveJob J, plo_stats_t *st)
         if (err < 0) return err;
         if (err == 0) return PLO_OK;
         if (err != plo::ERR_TABLE) return device_error(err);
-        pl->cap_scale *= 2;                       // table full: re-plan with twice the slots and retry
-        int rc = build_plan(pl);
+        int rc = grow_plan(pl);                   // table full: re-plan with twice the slots and retry
         if (rc != PLO_OK) return rc;
         if (J.best) HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, sizeof(unsigned long long), g_stream));
     }
@@ -836,6 +854,7 @@ int chain_config(plo_chain *ch)
 int run_chain(plo_chain *ch, plo::WaveJob J, plo_stats_t *st)
 {
     plo_plan *p0 = ch->st[0];
+    bool stuck = false;                           // one of the two tables could not be doubled
     for (int attempt = 0; attempt < 4; ++attempt) {
         const uint64_t need = (J.ncand + ch->W - 1) / ch->W;
         const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * ch->blocks_per_cu, need));
@@ -848,10 +867,25 @@ int run_chain(plo_chain *ch, plo::WaveJob J, plo_stats_t *st)
         HIPCHK(hipMemcpy(&err, p0->d_err, sizeof err, hipMemcpyDeviceToHost));
         if (err == 0) return PLO_OK;
         if (err != plo::ERR_TABLE) return device_error((int)err);
-        for (int k = 0; k < 2; ++k) { ch->st[k]->cap_scale *= 2; int rc = build_plan(ch->st[k]); if (rc != PLO_OK) return rc; }
-        int rc = chain_config(ch); if (rc != PLO_OK) return rc;
+        // the error word does not say whose table was full: both get twice the slots; one that no longer fits then keeps its
+        // table (the full one may be the other's), and the launch is refused only when neither can grow or the table stays full
+        bool grew[2] = {false, false};
+        for (int k = 0; k < 2; ++k) {
+            const int rc = grow_plan(ch->st[k]);
+            if (rc == PLO_OK) grew[k] = true; else if (rc == PLO_E_CAPACITY) stuck = true; else return rc;
+        }
+        if (!grew[0] && !grew[1]) return PLO_E_CAPACITY;
+        int rc = chain_config(ch);
+        if (rc != PLO_OK) {                       // the grown images do not fit together: back to the tables that ran, the chain stays usable
+            const std::string why = g_err;
+            for (int k = 0; k < 2; ++k)
+                if (grew[k]) { ch->st[k]->cap_scale /= 2; const int back = build_plan(ch->st[k]); if (back != PLO_OK) return back; }
+            const int back = chain_config(ch); if (back != PLO_OK) return back;
+            return fail(rc, "pair table full, and with twice the slots: " + why);
+        }
         if (J.best) HIPCHK(hipMemsetAsync(p0->d_best, 0xFF, sizeof(unsigned long long), g_stream));
     }
+    if (stuck) return fail(PLO_E_CAPACITY, "pair table full, and twice the slots do not fit the LDS-resident wave kernel");
     return device_error(plo::ERR_TABLE);
 }
 
@@ -1367,6 +1401,7 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
     plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
     const auto t0 = std::chrono::steady_clock::now();
     if (best) { best->adds = best->muls = 0xFFFFFFFFu; best->seed = ~0ull; }
+    std::atomic<bool> stuck{false};                  // some plan could not take twice the slots
     for (uint32_t cap_scale = 2; cap_scale <= 16; cap_scale *= 2) {
         // host part of all plans (OpenMP), one device buffer for all images
         std::vector<plo::WavePlan> plans(2ull * npairs);
@@ -1379,11 +1414,19 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
                     const long long k = next.fetch_add(1);
                     if (k >= 2ll * npairs) break;
                     const plo_csr_t *A = (k & 1) ? &seconds[k >> 1] : &firsts[k >> 1];
-                    plo_plan tmp; tmp.cap_scale = cap_scale;
+                    plo_plan tmp;
                     if (!A->rowptr || (A->rowptr[A->m] && (!A->col || !A->val))) { rcs[k] = PLO_E_ARG; errs[k] = "null matrix arrays"; continue; }
                     set_matrix(&tmp, A, p);
-                    rcs[k] = build_plan(&tmp, &imgs[k]);
-                    if (rcs[k] != PLO_OK) errs[k] = g_err; else plans[k] = tmp.P;
+                    // the error word does not say whose table was full: a plan that no longer fits with this many slots keeps the
+                    // largest table that does (the full one may be another pair's); with the first scale the refusal is the matrix's
+                    for (uint32_t s = cap_scale; s >= 2u; s /= 2u) {
+                        tmp.cap_scale = s;
+                        rcs[k] = build_plan(&tmp, &imgs[k]);
+                        if (rcs[k] != PLO_E_CAPACITY) break;
+                        if (s == cap_scale) errs[k] = g_err;
+                        if (s > 2u) stuck = true;
+                    }
+                    if (rcs[k] == PLO_OK) plans[k] = tmp.P; else if (rcs[k] != PLO_E_CAPACITY) errs[k] = g_err;
                 }
             };
             const unsigned nt = std::max(1u, std::min<unsigned>(std::thread::hardware_concurrency(), std::min<unsigned>(64u, npairs)));
@@ -1434,6 +1477,7 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
         st->seconds = seconds_since(t0);
         return PLO_OK;
     }
+    if (stuck) return fail(PLO_E_CAPACITY, "pair table full, and twice the slots do not fit the LDS-resident wave kernel");
     return device_error(plo::ERR_TABLE);
 }
 

@@ -755,3 +755,205 @@ def tril_tie_cases():
     _tril_case(out, "2x2_unit", "tie", 2, [(2, _rows(rng, 2, [2, 1], UNIT)), (2, _rows(rng, 2, [1, 2], UNIT)), (2, _rows(rng, 2, [2, 2], UNIT))], False)
     _tril_case(out, "3x3_rat_e", "tie", 3, [(3, _rows(rng, 3, [2, 1, 2], TRIL_RATS)), (2, _rows(rng, 2, [1, 2, 1], TRIL_RATS)), (3, _rows(rng, 3, [2, 2, 1], TRIL_RATS))], True)
     return out
+
+
+# ======================================================================================================================
+# Edge-shape cases for the chained-candidate kernels (plo_cse_wave.hip cse_chain_kernel through plo_cse_chain_*, and
+# cse_chain_batch_kernel through plo_cse_chain_batch): two matrices per candidate, one random stream.  No golden file: the
+# oracle (oracle/plo_oracle.c plo_oracle_chain) scores them in milliseconds, tests/test_chain_cases_host.py holds the family
+# to what it is meant to distinguish and tests/test_gpu_chain_synth.py the kernels to the oracle.
+#
+# wave_plan() restates the admission rules and the LDS layout of build_plan / layout_wave_image (plo_capi.hip), so that
+# every case is checked HERE to be taken or refused as it says, and to have the layout property it is there for.
+# ======================================================================================================================
+CHAIN_PRIME = 131071
+CHAIN_MODULI = [3, 7, 101, 2147483629, 2147483647]
+CHAIN_RUN = (0, 8)                                               # scored as one (seed0, n) run ...
+CHAIN_SEEDS = [2 ** 40, 2 ** 63, 2 ** 64 - 1, 5, 5]              # ... and as one explicit list: above 2^32, and one seed twice
+
+
+def wave_plan(m, n, rows, p, cap_scale=2, tight=False):
+    """The name of the header's code when build_plan refuses the matrix for the LDS-resident wave kernel, else its plan: mw,
+    unit, NC, distinct initial triples, cap, and tmpl_bytes / region_bytes / rs_bytes of layout_wave_image.  tight: the
+    table of the PLO_WAVE_CAP_TIGHT knob."""
+    rows = [{j: v % p for j, v in r.items() if v % p} for r in rows]
+    nnz, maxlen = sum(len(r) for r in rows), max([len(r) for r in rows] + [0])
+    unit = all(v in (1 % p, p - 1) for r in rows for v in r.values())
+    if maxlen > 64 or m == 0 or m > 31 * 64:
+        return "PLO_E_CAPACITY"
+    mw = (m + 63) // 64
+    if not unit and mw > 1:
+        return "PLO_E_CAPACITY"
+    naive = sum(max(len(r) - 1, 0) for r in rows)
+    NC = n + naive // 2 + 2
+    if NC >= 0xFFFF or 2 * _clog2(NC) + _clog2(p) > 51 or 2 * nnz >= 65535:
+        return "PLO_E_CAPACITY"
+    triples = {}
+    for r in rows:
+        e = sorted(r.items())
+        for x in range(len(e)):
+            for y in range(x + 1, len(e)):
+                k = (e[x][0], e[y][0], e[y][1] * pow(e[x][1], -1, p) % p)
+                triples[k] = triples.get(k, 0) + 1
+    cap = 64
+    if tight:
+        while cap < len(triples) + 1:
+            cap *= 2
+        cap *= cap_scale // 2
+    else:
+        while cap < cap_scale * len(triples) * 3 // 4 + 16:
+            cap *= 2
+    if cap > 65536:
+        return "PLO_E_CAPACITY"
+    multcap = 0 if unit else naive // 2 + 8
+    off = _ru(cap * 8 + nnz * (6 if unit else 10) + m * 2, 8)
+    tmpl = off + n * 2 * mw * 8
+    off += NC * 2 * mw * 8 + (2 * mw + 1) * 8 + cap * 2
+    region = _ru(_ru(off, 8) + multcap * 8, 16)
+    rs = _ru((m + 1) * 2, 16)
+    if rs + region > LDS_MAX:
+        return "PLO_E_CAPACITY"
+    return SimpleNamespace(mw=mw, unit=unit, NC=NC, distinct=len(triples), maxfreq=max(list(triples.values()) + [0]), cap=cap,
+                           tmpl_bytes=tmpl, region_bytes=region, rs_bytes=rs)
+
+
+def pick_waves(lds, limit=LDS_MAX):
+    """(waves per workgroup, LDS bytes) as pick_waves(most_per_cu = true) of plo_capi.hip chooses among 4, 2 and 1"""
+    W = best = got = 0
+    for w in (4, 2, 1):
+        if lds(w) > limit:
+            continue
+        waves = min(32, limit // lds(w) * w)
+        if W and waves <= best:
+            continue
+        W, best, got = w, waves, lds(w)
+    return W, got
+
+
+def chain_layout(A, B):
+    """(waves per workgroup, LDS bytes) of chain_config for two admitted plans"""
+    return pick_waves(lambda w: A.rs_bytes + B.rs_bytes + w * max(A.region_bytes, B.region_bytes))
+
+
+def _chain_case(out, name, family, A, B, p=CHAIN_PRIME, refusal=None, run=CHAIN_RUN, seeds=CHAIN_SEEDS):
+    """A, B: (columns, rows) with rows as {column: signed value}; the case holds the residues"""
+    mats, plans = [], []
+    for n, rows in (A, B):
+        assert all(0 <= j < n and v % p for r in rows for j, v in r.items()), name
+        rows = [{j: v % p for j, v in r.items()} for r in rows]
+        assert sum(len(r) for r in rows) <= 1100 or family == "onewave" or refusal, name        # (the oracle's time; it never sees a refused pair)
+        mats.append(SimpleNamespace(m=len(rows), n=n, rows=rows, csr=(len(rows), n) + to_csr(rows, p)))
+        plans.append(wave_plan(len(rows), n, rows, p))
+    got = next((x for x in plans if isinstance(x, str)), None)
+    if got is None and chain_layout(*plans)[0] == 0:
+        got = "PLO_E_CAPACITY"
+    assert got == refusal, (name, got)
+    c = SimpleNamespace(name="chain_%s_%s" % (family, name), family=family, A=mats[0], B=mats[1], p=p, refusal=refusal, run=run, seeds=list(seeds),
+                        plans=plans, silent_first=not refusal and plans[0].maxfreq <= 1, relaunch=False,
+                        waves=None if refusal else chain_layout(*plans)[0], lds=None if refusal else chain_layout(*plans)[1])
+    assert c.name not in [x.name for x in out], c.name
+    out.append(c)
+    return c
+
+
+def _dense(rng, m, n, vals, density=1.0):
+    return n, [{j: _pick(rng, vals) for j in range(n) if density >= 1.0 or rng.random() < density} for _ in range(m)]
+
+
+CHAIN_ORDER_A = (6, [{0: 1, 1: -1, 2: 1, 3: 1, 4: -1, 5: 1}, {0: 1, 1: 1, 2: -1, 3: 1, 4: 1, 5: -1}, {0: -1, 1: 1, 2: 1, 3: -1, 4: 1, 5: 1},
+                     {0: 1, 1: 1, 2: 1, 3: 1, 4: 1, 5: 1}, {0: 1, 1: -1, 2: -1, 3: 1, 4: -1, 5: -1}, {0: -1, 1: -1, 2: 1, 3: 1, 4: 1, 5: -1},
+                     {0: 1, 1: 1, 2: -1, 3: -1, 4: 1, 5: 1}, {0: -1, 1: 1, 2: -1, 3: 1, 4: -1, 5: 1}])
+
+
+def chain_cases():
+    """About 50 pairs of matrices at the edges of cse_chain_kernel and cse_chain_batch_kernel: what the second run_candidate
+    finds in the LDS region the first one left, the four unit/general dispatches, first matrices that draw nothing from the
+    random stream, more than 64 rows, rows of 64 entries, moduli from 3 to 2^31 - 1, one wave per workgroup, and four pairs
+    the chain refuses.  The table of the 150 x 6 matrix (30 initial triples, 64 slots) fills up under the usual sizing: its two
+    pairs take the table-full relaunch without any knob (c.relaunch)."""
+    rng = random.Random(0xC4A15)
+    out = []
+    GEN = [1, -1, 2, 3]
+    tiny = (3, [{0: 1, 1: 2, 2: 1}, {0: 1, 1: 2}, {1: -1, 2: 3}])
+    # order: the same two matrices both ways round; every tie of the first moves the stream the second sees
+    gen7x5 = _dense(rng, 7, 5, GEN)
+    gen9x6 = _dense(rng, 9, 6, [1, -1, 2, -2, 3], 0.8)
+    gen8x7 = _dense(rng, 8, 7, GEN, 0.8)
+    for name, A, B in (("u8x6_g7x5", CHAIN_ORDER_A, gen7x5), ("g9x6_g8x7", gen9x6, gen8x7)):
+        _chain_case(out, name, "order", A, B)
+        _chain_case(out, name + "_rev", "order", B, A)
+    # dispatch: P.unit is read per matrix at run time, all four combinations at 6 and at 12 rows
+    for m in (6, 12):
+        for fa, va in (("unit", [1, -1]), ("gen", GEN)):
+            for fb, vb in (("unit", [1, -1]), ("gen", GEN)):
+                c = _chain_case(out, "%s_%s_%d" % (fa, fb, m), "dispatch", _dense(rng, m, 5 + m // 6, va, 0.85), _dense(rng, m - 1, 4 + m // 6, vb, 0.85))
+                assert [x.unit for x in c.plans] == [fa == "unit", fb == "unit"]
+    # silent first: matrices that draw nothing from the stream (no pair at all, or no pair of frequency 2), and the -K host
+    # decomposition's emptied rows (which does draw), each before and after a matrix that draws
+    draws = _dense(rng, 8, 6, GEN)
+    freq1 = (5, [{0: 1, 1: 2, 2: 3}, {0: 1, 1: 5, 3: 7}, {1: 1, 2: 11, 4: 13}, {0: 2, 3: 17, 4: 19}, {2: 1, 3: 23}])
+    holes = _dense(rng, 11, 6, GEN)
+    for i in (0, 4, 5, 10):
+        holes[1][i] = {}
+    for name, S, silent in (("empty3x2", (2, [{}, {}, {}]), True), ("1x1", (1, [{0: 2}]), True), ("freq1", freq1, True), ("emptied_rows", holes, False)):
+        c = _chain_case(out, name + "_first", "silent", S, draws)
+        assert c.silent_first == silent and c.plans[1].maxfreq > 1
+        c = _chain_case(out, name + "_second", "silent", draws, S)
+        assert not c.silent_first
+    # region dominance: the region is max(region_bytes), and only tmpl_bytes of the second image are rewritten
+    big = _dense(rng, 40, 32, [1, -1, 2], 0.8)
+    c = _chain_case(out, "big_tiny", "region", big, tiny)
+    assert c.plans[0].region_bytes > 8 * c.plans[1].region_bytes
+    _chain_case(out, "tiny_big", "region", tiny, big)
+    pool = [0, 1, 2, 650, 651, 1297, 1298, 1299]
+    wide = (1300, [{j: _pick(rng, [1, -1]) for j in _sample(rng, pool, 3)} for _ in range(16)])              # 1300 columns, 128 slots
+    deep = _dense(rng, 30, 8, list(range(2, 40)))                                                            # 8 columns, some 800 triples
+    for name, A, B in (("wide_deep", wide, deep), ("deep_wide", deep, wide)):
+        c = _chain_case(out, name, "region", A, B)
+        w, d = c.plans if A is wide else c.plans[::-1]
+        assert w.tmpl_bytes > d.tmpl_bytes and w.region_bytes < d.region_bytes and w.cap < d.cap
+    # mw > 1 (more than 64 rows, +-1 only) next to a general matrix, and mw 2 next to mw 3
+    gen20 = _dense(rng, 20, 6, GEN, 0.7)
+    for m, n in ((65, 3), (150, 6)):
+        U = _dense(rng, m, n, [1, -1], 0.9)
+        c = _chain_case(out, "%dx%d_gen" % (m, n), "mw", U, gen20)
+        assert [x.mw for x in c.plans] == [(m + 63) // 64, 1]
+        c.relaunch = m == 150
+        _chain_case(out, "gen_%dx%d" % (m, n), "mw", gen20, U).relaunch = m == 150
+    c = _chain_case(out, "128x4_129x4", "mw", _dense(rng, 128, 4, [1, -1], 0.9), _dense(rng, 129, 4, [1, -1], 0.9))
+    assert [x.mw for x in c.plans] == [2, 3]
+    # row length: rows of 64 entries (lpr_log2 = 6: one row per wave trip)
+    u2x64, u6x64 = _dense(rng, 2, 64, [1, -1]), _dense(rng, 6, 64, [1, -1])
+    _chain_case(out, "2x64_gen", "rowlen", u2x64, gen20)
+    _chain_case(out, "6x64_2x64", "rowlen", u6x64, u2x64)
+    _chain_case(out, "gen_6x64", "rowlen", gen20, u6x64)
+    g3x64 = _dense(rng, 3, 64, [1, -1, 2, 3, 4])
+    for p in (3, 7):
+        fix = (64, [{j: (v if v % p else 1) for j, v in r.items()} for r in g3x64[1]])
+        c = _chain_case(out, "3x64_mod%d" % p, "rowlen", fix, (6, [{j: (v if v % p else 1) for j, v in r.items()} for r in gen20[1]]), p=p)
+        assert c.plans[0].unit == (p == 3)                       # at p = 3 every residue is +-1
+    _chain_case(out, "gen2x64_tiny", "rowlen", (64, g3x64[1][:2]), tiny)     # (three such rows at this modulus: 6048 triples, past the LDS)
+    # moduli: rb and the key layout of both plans, one unit/general pair both ways round
+    mu, mg = _dense(rng, 10, 7, [1, -1], 0.8), _dense(rng, 9, 6, [1, -1, 2, 3, 5, 6], 0.8)
+    for p in CHAIN_MODULI:
+        g = (mg[0], [{j: (v if v % p else 1) for j, v in r.items()} for r in mg[1]])
+        _chain_case(out, "unit_gen_mod%d" % p, "moduli", mu, g, p=p)
+        _chain_case(out, "gen_unit_mod%d" % p, "moduli", g, mu, p=p)
+    # one wave per workgroup: the largest dense +-1 square that runs with one wave, 60 x 60 (3540 triples, 8192 slots, 130 KB of the
+    # 160 KiB).  The live triples of such a matrix grow to 2.2 times the initial ones: 64 x 64 and 62 x 62 fill the 8192 slots, which
+    # cannot be doubled inside the LDS, 61 x 61 comes within 2 % of them, 52 x 52 and smaller have 4096 slots and two waves.  The
+    # oracle takes most of a second per seed: three seeds, the list repeats them
+    c = _chain_case(out, "60x60_tiny", "onewave", _dense(rng, 60, 60, [1, -1]), tiny, run=(0, 3), seeds=[2, 0, 2])
+    assert c.waves == 1 and c.plans[0].cap == 8192 and 128 * 1024 < c.lds <= LDS_MAX
+    assert all(c.waves == 4 for c in out if c.family in ("order", "dispatch", "silent", "moduli"))
+    # refusals: plans of the HBM family (a +-1 matrix of 1984 rows whose masks alone pass 160 KiB; more than 64 rows with another
+    # coefficient than +-1), as first and as second matrix
+    C = "PLO_E_CAPACITY"
+    u1984 = _dense(rng, 1984, 2, [1, -1])
+    g65 = (2, [{0: 1, 1: 2}] + [{0: _pick(rng, [1, -1]), 1: _pick(rng, [1, -1])} for _ in range(64)])
+    assert wave_plan(1984, 2, u1984[1], CHAIN_PRIME) == C and wave_plan(65, 2, g65[1], CHAIN_PRIME) == C
+    _chain_case(out, "1984x2_first", "refuse", u1984, tiny, refusal=C)
+    _chain_case(out, "1984x2_second", "refuse", tiny, u1984, refusal=C)
+    _chain_case(out, "gen65x2_first", "refuse", g65, tiny, refusal=C)
+    _chain_case(out, "gen65x2_second", "refuse", tiny, g65, refusal=C)
+    return out

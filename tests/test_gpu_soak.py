@@ -18,6 +18,9 @@ against the product's host engines.
                         rows, moduli 3 to 2^31 - 1, 4/2/1 waves per workgroup) x 11 restarts, against the C oracle  (test_gpu_kmethod_tril_synth.py)
   in-place trilinear   64 edge-shape triples (1 to 1200 rows, 64-entry rows, the row forms of `-e`, variable 16381,
                         the 64 KiB switch, 130 KiB of LDS) x 11 seeds (3 near 160 KiB), against the C oracle  (test_gpu_kmethod_tril_synth.py)
+  chained kernels      150 random pairs of up to 200 x 64 over five moduli, 8 seeds each through a chain plan, then four
+                        pairs per batch launch with 5 candidates each, against plo_oracle_chain; the edge shapes and the
+                        table-full relaunch are in test_gpu_chain_synth.py
 
 A refusal the header documents (PLO_E_CAPACITY / PLO_E_UNSUPPORTED) is counted and bounded, anything else fails."""
 import os
@@ -69,6 +72,59 @@ def test_wave_kernel_on_random_matrices(hip):
         assert got == tuple(OracleMatrix(m, n, rp, c, v, p).cost_many(seed0=s, nseeds=8, nthreads=8)), (s - 1, m, n, p)
         ran += 1
     assert refused <= 20
+
+
+def test_chained_kernels_on_random_pairs(hip):
+    """cse_chain_kernel and cse_chain_batch_kernel: the shapes and moduli of the wave kernel's slice, two matrices of at most
+    300 entries per candidate and one random stream, against plo_oracle_chain; then the same pairs four at a time by modulus
+    through one batch launch each.  synth.wave_plan (build_plan's admission rules) says which pairs the device may refuse."""
+    from plinopt_amd import CSEChain, chain_batch
+    from plo_testlib import oracle_chain
+    pairs, refused, s = [], 0, 0
+    while len(pairs) < 150:
+        rng = random.Random(15000 + s)
+        s += 1
+        p = rng.choice([7, 101, 131071, 2147483629, 2147483647])
+        two = []
+        for _ in range(2):
+            unit = rng.random() < 0.4
+            m, n = rng.randint(2, 200 if unit else 64), rng.randint(2, 64)
+            dens = rng.choice([0.1, 0.3, 0.6, 0.9])
+            vals = [1, p - 1] if unit else [1, p - 1] + [rng.randint(2, p - 2) % p or 1 for _ in range(rng.choice([1, 3, 30]))]
+            rows = [{j: rng.choice(vals) for j in range(n) if rng.random() < dens} for _ in range(m)]
+            two.append((m, n, [r if r else {0: 1} for r in rows]))
+        if max(sum(len(r) for r in rows) for _, _, rows in two) > 300:
+            continue
+        plans = [synth.wave_plan(m, n, rows, p) for m, n, rows in two]
+        admitted = not any(isinstance(x, str) for x in plans) and synth.chain_layout(*plans)[0] > 0
+        csr = [(m, n) + synth.to_csr(rows, p) for m, n, rows in two]
+        try:
+            ch = CSEChain(csr[0], csr[1], p)
+        except Exception as e:
+            assert _refusal(e) and not admitted, (s - 1, str(e))
+            refused += 1
+            continue
+        assert admitted, s - 1
+        pairs.append((s - 1, p, csr, [OracleMatrix(*(x + (p,))) for x in csr], ch))
+    assert refused <= 15
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        exp = list(ex.map(lambda c: [oracle_chain(c[3][0], c[3][1], c[0] + k) for k in range(8)], pairs))
+    for (s, p, csr, _, ch), e in zip(pairs, exp):
+        ga, gm = ch.cost_many(seed0=s, n=8)
+        ch.close()
+        assert list(zip(ga, gm)) == e, (s, p, csr[0][:2], csr[1][:2])
+    groups = []
+    for p in sorted({c[1] for c in pairs}):
+        same = [c for c in pairs if c[1] == p]
+        groups += [same[k:k + 4] for k in range(0, len(same), 4)]
+    per, seed0 = 5, 1 << 33
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        exp = list(ex.map(lambda g: [oracle_chain(g[k // per][3][0], g[k // per][3][1], seed0 + k) for k in range(len(g) * per)], groups))
+    for g, e in zip(groups, exp):
+        ga, gm, best, st = chain_batch([tuple(c[2]) for c in g], g[0][1], seed0, per)
+        assert list(zip(ga, gm)) == e, [c[0] for c in g]
+        b = min(range(len(e)), key=lambda k: (e[k][0] + e[k][1], e[k][0], k))
+        assert best == (e[b][0], e[b][1], seed0 + b)
 
 
 def _hbm_cases():
