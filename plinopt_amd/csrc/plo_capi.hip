@@ -1,10 +1,8 @@
 // ===========================================================================
 // plo_capi.hip -- host side of libplinopt_hip.so: the C-ABI declared in
-// include/plinopt_hip.h.  Prepares a matrix once (row image, modular inverses,
-// initial pair table and column bit-masks: the state OneSub builds at
-// reference include/plinopt_optimize.inl:214-225 is identical for every
-// restart, so it is computed once on the host and kept resident in HBM), then
-// launches the per-candidate wave kernel over a seed range.
+// include/plinopt_hip.h, for all nine kernel families (CSE wave, CSE HBM, chained
+// CSE, kernel method, change of basis, trilplacer and inplacer, orbit, dependency),
+// each under its banner comment below; what they share comes first.
 // There is NO CPU fallback in this file: without a HIP device every compute
 // entry point fails with PLO_E_HIP.
 // ===========================================================================
@@ -74,6 +72,23 @@ uint32_t ceil_log2(uint32_t x) { uint32_t l = 0; while ((1u << l) < x) ++l; retu
 uint32_t round_up(uint32_t x, uint32_t a) { return (x + a - 1) / a * a; }
 double seconds_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 
+// The statistics and the clock of one call: the caller's plo_stats_t or a local one, cleared, and the start time.  done(rc) sets
+// `seconds` and hands rc on; an entry that returns without it leaves `seconds` at zero.
+struct CallScope {
+    plo_stats_t local{}, *st;
+    std::chrono::steady_clock::time_point t0;
+    explicit CallScope(plo_stats_t *stats) : st(stats ? stats : &local) { *st = plo_stats_t{}; t0 = std::chrono::steady_clock::now(); }
+    int done(int rc) { st->seconds = seconds_since(t0); return rc; }
+};
+// A call before plo_init.  The CSE family refuses in few words, the families after it in more, and the entries that the tools call
+// without plo_init (CSE plan creation, change of basis) take device 0 themselves.  The tools print these texts.
+enum NoInit { NOINIT_CSE, NOINIT_PLAN, NOINIT_DEVICE0 };
+int require_device(NoInit how) {
+    if (g_device >= 0) return PLO_OK;
+    if (how == NOINIT_DEVICE0) return plo_init(0);
+    return fail(PLO_E_HIP, how == NOINIT_CSE ? "plo_init not called" : "plo_init was not called (or found no HIP device)");
+}
+
 // An integer environment knob: unset, or the number strtol reads from it (a flag counts as soon as it is set, whatever it holds)
 std::optional<long> env_knob(const char *name) { const char *e = getenv(name); if (!e) return std::nullopt; return strtol(e, nullptr, 10); }
 
@@ -85,18 +100,23 @@ template <class T> struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
     operator T *() const { return p; }
 };
+// hipFree of those of a plan's device buffers that exist
+template <class... P> void dev_free(P *...p) { for (void *q : {(void *)p...}) if (q) (void)hipFree(q); }
 
-// The event pair around one launch on g_stream: launch() enqueues the kernel, *ms gets its time
-template <class Launch> int timed(float *ms, Launch launch)
-{
-    struct Events { hipEvent_t e0 = nullptr, e1 = nullptr; ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); } } ev;
-    HIPCHK(hipEventCreate(&ev.e0)); HIPCHK(hipEventCreate(&ev.e1));
-    HIPCHK(hipEventRecord(ev.e0, g_stream));
+// One launch on g_stream between two events: launch() enqueues the kernel, *ms gets its time
+template <class Launch> int timed_between(hipEvent_t e0, hipEvent_t e1, float *ms, Launch launch) {
+    HIPCHK(hipEventRecord(e0, g_stream));
     launch();
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev.e1, g_stream)); HIPCHK(hipEventSynchronize(ev.e1));
-    HIPCHK(hipEventElapsedTime(ms, ev.e0, ev.e1));
+    HIPCHK(hipEventRecord(e1, g_stream)); HIPCHK(hipEventSynchronize(e1));
+    HIPCHK(hipEventElapsedTime(ms, e0, e1));
     return PLO_OK;
+}
+// the same with an event pair of its own
+template <class Launch> int timed(float *ms, Launch launch) {
+    struct Events { hipEvent_t e0 = nullptr, e1 = nullptr; ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); } } ev;
+    HIPCHK(hipEventCreate(&ev.e0)); HIPCHK(hipEventCreate(&ev.e1));
+    return timed_between(ev.e0, ev.e1, ms, launch);
 }
 
 // One timed launch and its statistics: time and count add up over the launches of a call, the shape is the latest launch's.
@@ -120,6 +140,27 @@ template <class Plan, class Launch> int timed_launch(Plan *pl, uint64_t grid, ui
     if (rc == PLO_OK && st) st->candidates += ncand;
     return rc;
 }
+
+// One launch of a kernel that reports through an error word: the word cleared, the timed launch, the word read back.
+// Negative: a refusal of the host side; otherwise the device's word (0 = none).  The job's err field points at d_err already.
+template <class Launch> int checked_launch(uint32_t *d_err, plo_stats_t *st, const LaunchShape &shape, Launch launch) {
+    HIPCHK(hipMemsetAsync(d_err, 0, sizeof(uint32_t), g_stream));
+    const int trc = timed_launch(st, &shape, launch);
+    if (trc != PLO_OK) return trc;
+    uint32_t err = 0;
+    HIPCHK(hipMemcpy(&err, d_err, sizeof err, hipMemcpyDeviceToHost));
+    return (int)err;
+}
+// The dynamic-LDS limit of kernel `fn` raised to `lds` bytes; *per_cu: the workgroups of W waves a CU then holds by the runtime's count, 1 at least
+int occupancy_for(const void *fn, uint32_t W, uint32_t lds, uint32_t *per_cu) {
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nb = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)(W * 64), lds));
+    *per_cu = (uint32_t)std::max(nb, 1);
+    return PLO_OK;
+}
+// Workgroups of a launch over `ncand` candidates, W to a workgroup: no more than the device holds at once (`resident`), never none
+uint64_t grid_for(uint64_t ncand, uint32_t W, uint64_t resident) { return std::max<uint64_t>(1, std::min<uint64_t>(resident, (ncand + W - 1) / W)); }
 
 // Waves (= candidates) per workgroup, 4, 2 or 1, for a kernel that needs lds(w) bytes with w waves: the first count that fits
 // `limit`, or with most_per_cu the count that puts most waves on a CU (32 at most; the larger workgroup on a tie).
@@ -363,11 +404,7 @@ int build_plan(plo_plan *pl, std::vector<uint8_t> *img_out = nullptr)
     if (!pl->d_best) HIPCHK(hipMalloc((void **)&pl->d_best, sizeof(unsigned long long)));
 
     const void *fn = unit ? (const void *)plo::cse_wave_kernel<true> : (const void *)plo::cse_wave_kernel<false>;
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->lds_bytes));
-    int nb = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)(W * 64), pl->lds_bytes));
-    pl->blocks_per_cu = (uint32_t)std::max(nb, 1);
-    return PLO_OK;
+    return occupancy_for(fn, W, pl->lds_bytes, &pl->blocks_per_cu);
 }
 
 
@@ -712,16 +749,13 @@ int launch_big(plo_plan *pl, plo::BigJob J, plo_stats_t *st)
     }
     const uint64_t grid = std::min<uint64_t>(pl->ws_slices, want);
     pl->B.ws = (uint8_t *)pl->d_ws;
-    HIPCHK(hipMemsetAsync(pl->d_err, 0, sizeof(uint32_t), g_stream));
     HIPCHK(hipMemsetAsync(pl->d_next, 0, sizeof(unsigned long long), g_stream));
     HIPCHK(hipMemsetAsync(pl->d_stats, 0, plo::BS_COUNT * sizeof(uint32_t), g_stream));
     J.err = pl->d_err; J.next = pl->d_next; J.stats = pl->d_stats;
-    const LaunchShape shape{grid, pl->lds_bytes, pl->waves_per_wg, pl->algo_bytes};
     void *args[] = {&pl->B, &J};
-    const int trc = timed_launch(st, &shape, [&] { (void)hipLaunchKernel(big_kernel_fn(pl->B), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), args, pl->big_lds, g_stream); });
-    if (trc != PLO_OK) return trc;
-    uint32_t err = 0;
-    HIPCHK(hipMemcpy(&err, pl->d_err, sizeof err, hipMemcpyDeviceToHost));
+    const int err = checked_launch(pl->d_err, st, LaunchShape{grid, pl->lds_bytes, pl->waves_per_wg, pl->algo_bytes},
+                                   [&] { (void)hipLaunchKernel(big_kernel_fn(pl->B), dim3((uint32_t)grid), dim3(PLO_BIG_THREADS), args, pl->big_lds, g_stream); });
+    if (err < 0) return err;
     if (K.stats) print_big_stats(pl);
     if (err == plo::BERR_TABLE && !pl->B.defer && pl->big_cap_scale < 256u) {
         // eager table full: the live triples of frequency >= 2 can outnumber the input's (new columns pair with every column of the rows
@@ -754,28 +788,21 @@ int launch_big(plo_plan *pl, plo::BigJob J, plo_stats_t *st)
 int launch(plo_plan *pl, plo::WaveJob J, plo_stats_t *st)
 {
     const uint32_t W = pl->waves_per_wg;
-    uint64_t need = (J.ncand + W - 1) / W;
-    uint64_t grid = std::min<uint64_t>((uint64_t)g_cus * pl->blocks_per_cu, need);
-    if (grid == 0) grid = 1;
-    HIPCHK(hipMemsetAsync(pl->d_err, 0, sizeof(uint32_t), g_stream));
+    const uint64_t grid = grid_for(J.ncand, W, (uint64_t)g_cus * pl->blocks_per_cu);
     J.err = pl->d_err;
-    const LaunchShape shape{grid, pl->lds_bytes, W, pl->algo_bytes};
-    const int trc = timed_launch(st, &shape, [&] {
+    const int err = checked_launch(pl->d_err, st, LaunchShape{grid, pl->lds_bytes, W, pl->algo_bytes}, [&] {
         if (pl->P.unit) hipLaunchKernelGGL(plo::cse_wave_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), pl->lds_bytes, g_stream, pl->P, J);
         else hipLaunchKernelGGL(plo::cse_wave_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), pl->lds_bytes, g_stream, pl->P, J);
     });
-    if (trc != PLO_OK) return trc;
-    uint32_t err = 0;
-    HIPCHK(hipMemcpy(&err, pl->d_err, sizeof err, hipMemcpyDeviceToHost));
 #ifdef PLO_WAVE_PROFILE
-    if (getenv("PLO_WAVE_STATS")) {
+    if (err >= 0 && getenv("PLO_WAVE_STATS")) {
         unsigned long long g[12] = {0};
         if (hipMemcpyFromSymbol(g, HIP_SYMBOL(plo::g_wprof), sizeof g) == hipSuccess && g[9])
             fprintf(stderr, "# wave kernel, cumulative: %llu candidates, %.1f steps each; cycles per step: max scan %.0f, tie list %.0f, tie pick %.0f, sweep 1 %.0f, sweep 2 %.0f, tail %.0f; sweep 1 trips per step %.2f, per trip: loads + ballots + broadcasts %.0f, retirements %.0f\n",
                     g[9], (double)g[8] / g[9], (double)g[0] / g[8], (double)g[1] / g[8], (double)g[2] / g[8], (double)g[3] / g[8], (double)g[4] / g[8], (double)g[5] / g[8], (double)g[11] / g[8], g[11] ? (double)g[6] / g[11] : 0.0, g[11] ? (double)g[7] / g[11] : 0.0);
     }
 #endif
-    return (int)err;   // >0: device error word
+    return err;        // >0: device error word
 }
 
 int device_error(int err) {
@@ -788,8 +815,8 @@ int device_error(int err) {
     }
 }
 
-// Twice the slots for a plan whose launch met a full table.  A table that no longer fits (LDS, 65536 slots) is refused with
-// PLO_E_CAPACITY and the plan stays as it was: build_plan clears the plan it fails on, and the next call would launch that.
+// Twice the slots for a plan whose launch met a full table.  The rule of every repeat: a table that no longer fits (LDS, 65536 slots) is refused with PLO_E_CAPACITY
+// and the plan KEEPS THE TABLE THAT RAN -- build_plan clears the plan it fails on, and the next call would launch that, so the plan is built again with the slots it had.
 int grow_plan(plo_plan *pl)
 {
     pl->cap_scale *= 2;
@@ -802,17 +829,21 @@ int grow_plan(plo_plan *pl)
     return fail(PLO_E_CAPACITY, "pair table full, and with twice the slots: " + why);
 }
 
+// Before a launch is repeated with larger tables: the candidates that the refused launch finished have left their words in the job's best word, and the repeat evaluates them again
+int reset_best(const plo::WaveJob &J, unsigned long long *d_best) {
+    if (J.best) HIPCHK(hipMemsetAsync(d_best, 0xFF, sizeof(unsigned long long), g_stream));
+    return PLO_OK;
+}
 // run a job, growing the pair table when the device reports it full
 int run_job(plo_plan *pl, plo::WaveJob J, plo_stats_t *st)
 {
     for (int attempt = 0; attempt < 4; ++attempt) {
-        int err = launch(pl, J, st);
-        if (err < 0) return err;
-        if (err == 0) return PLO_OK;
+        const int err = launch(pl, J, st);
+        if (err <= 0) return err;
         if (err != plo::ERR_TABLE) return device_error(err);
         int rc = grow_plan(pl);                   // table full: re-plan with twice the slots and retry
         if (rc != PLO_OK) return rc;
-        if (J.best) HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, sizeof(unsigned long long), g_stream));
+        if ((rc = reset_best(J, pl->d_best)) != PLO_OK) return rc;
     }
     return device_error(plo::ERR_TABLE);
 }
@@ -828,6 +859,16 @@ int run_plan_job(plo_plan *pl, uint64_t seed0, const uint64_t *seeds, uint64_t n
     return run_job(pl, J, st);
 }
 
+// the entries that take a matrix: a plan for the one call
+template <class Call> int with_plan(const plo_csr_t *A, uint32_t p, Call call) {
+    plo_plan_t *pl = nullptr;
+    int rc = plo_cse_plan_create(A, p, &pl);
+    if (rc != PLO_OK) return rc;
+    rc = call(pl);
+    plo_cse_plan_destroy(pl);
+    return rc;
+}
+
 } // namespace
 
 // Two prepared matrices evaluated back to back per candidate with one random stream (LU method)
@@ -837,38 +878,29 @@ struct plo_chain {
 };
 
 namespace {
-
 int chain_config(plo_chain *ch)
 {
     const plo::WavePlan &A = ch->st[0]->P, &B = ch->st[1]->P;
     const uint32_t region = std::max(A.region_bytes, B.region_bytes), fixed = A.rs_bytes + B.rs_bytes;
     if (fixed + region > g_lds_max) return fail(PLO_E_CAPACITY, "chained candidate state does not fit LDS");
-    const uint32_t W = ch->W = pick_waves([&](uint32_t w) { return fixed + w * region; }, true, g_lds_max, &ch->lds);
-    HIPCHK(hipFuncSetAttribute((const void *)plo::cse_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ch->lds));
-    int nb = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)plo::cse_chain_kernel, (int)(W * 64), ch->lds));
-    ch->blocks_per_cu = (uint32_t)std::max(nb, 1);
-    return PLO_OK;
+    ch->W = pick_waves([&](uint32_t w) { return fixed + w * region; }, true, g_lds_max, &ch->lds);
+    return occupancy_for((const void *)plo::cse_chain_kernel, ch->W, ch->lds, &ch->blocks_per_cu);
 }
 
+// run a job, growing the pair tables when the device reports one full (run_job for two plans)
 int run_chain(plo_chain *ch, plo::WaveJob J, plo_stats_t *st)
 {
     plo_plan *p0 = ch->st[0];
     bool stuck = false;                           // one of the two tables could not be doubled
+    J.err = p0->d_err;
     for (int attempt = 0; attempt < 4; ++attempt) {
-        const uint64_t need = (J.ncand + ch->W - 1) / ch->W;
-        const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * ch->blocks_per_cu, need));
-        HIPCHK(hipMemsetAsync(p0->d_err, 0, sizeof(uint32_t), g_stream));
-        J.err = p0->d_err;
-        const LaunchShape shape{grid, ch->lds, ch->W, ch->st[0]->algo_bytes + ch->st[1]->algo_bytes};
-        const int trc = timed_launch(st, &shape, [&] { hipLaunchKernelGGL(plo::cse_chain_kernel, dim3((uint32_t)grid), dim3(ch->W * 64), ch->lds, g_stream, ch->st[0]->P, ch->st[1]->P, J); });
-        if (trc != PLO_OK) return trc;
-        uint32_t err = 0;
-        HIPCHK(hipMemcpy(&err, p0->d_err, sizeof err, hipMemcpyDeviceToHost));
-        if (err == 0) return PLO_OK;
-        if (err != plo::ERR_TABLE) return device_error((int)err);
-        // the error word does not say whose table was full: both get twice the slots; one that no longer fits then keeps its
-        // table (the full one may be the other's), and the launch is refused only when neither can grow or the table stays full
+        const uint64_t grid = grid_for(J.ncand, ch->W, (uint64_t)g_cus * ch->blocks_per_cu);
+        const int err = checked_launch(p0->d_err, st, LaunchShape{grid, ch->lds, ch->W, ch->st[0]->algo_bytes + ch->st[1]->algo_bytes},
+                                       [&] { hipLaunchKernelGGL(plo::cse_chain_kernel, dim3((uint32_t)grid), dim3(ch->W * 64), ch->lds, g_stream, ch->st[0]->P, ch->st[1]->P, J); });
+        if (err <= 0) return err;
+        if (err != plo::ERR_TABLE) return device_error(err);
+        // The rule of a chain: the error word does not say whose table was full, so BOTH get twice the slots (grow_plan); one that no longer fits then
+        // keeps its table (the full one may be the other's), and the launch is refused only when neither can grow or the table stays full
         bool grew[2] = {false, false};
         for (int k = 0; k < 2; ++k) {
             const int rc = grow_plan(ch->st[k]);
@@ -883,12 +915,42 @@ int run_chain(plo_chain *ch, plo::WaveJob J, plo_stats_t *st)
             const int back = chain_config(ch); if (back != PLO_OK) return back;
             return fail(rc, "pair table full, and with twice the slots: " + why);
         }
-        if (J.best) HIPCHK(hipMemsetAsync(p0->d_best, 0xFF, sizeof(unsigned long long), g_stream));
+        if ((rc = reset_best(J, p0->d_best)) != PLO_OK) return rc;
     }
     if (stuck) return fail(PLO_E_CAPACITY, "pair table full, and twice the slots do not fit the LDS-resident wave kernel");
     return device_error(plo::ERR_TABLE);
 }
 
+// One attempt of a one-shot wave search (plo_cse_chain_batch, plo_kernel_search): the error and best words and, where the caller wants them, adds and muls of every candidate;
+// occupancy and grid of kernel `fn` with W waves and `lds` bytes; launch(grid, J); then the results copied back, the best word decoded as a sum-only key may be (the sum in
+// .adds).  *again: a pair table was full and nothing was copied -- the caller builds larger tables and calls again.
+template <class Launch> int one_shot_search(const void *fn, uint32_t W, uint32_t lds, uint64_t seed0, uint64_t ncand, int cost_mode,
+                                            uint32_t *adds, uint32_t *muls, plo_best_t *best, plo_stats_t *st, bool *again, Launch launch) {
+    DevBuf<uint32_t> d_adds, d_muls, d_err; DevBuf<unsigned long long> d_best;
+    HIPCHK(hipMalloc((void **)&d_err.p, 4));
+    HIPCHK(hipMalloc((void **)&d_best.p, 8)); HIPCHK(hipMemsetAsync(d_best, 0xFF, 8, g_stream));
+    if (adds) HIPCHK(hipMalloc((void **)&d_adds.p, ncand * 4));
+    if (muls) HIPCHK(hipMalloc((void **)&d_muls.p, ncand * 4));
+    uint32_t per_cu = 1;
+    if (const int rc = occupancy_for(fn, W, lds, &per_cu)) return rc;
+    const uint64_t grid = grid_for(ncand, W, (uint64_t)g_cus * per_cu);
+    plo::WaveJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = ncand; J.adds = d_adds; J.muls = d_muls; J.best = best ? d_best.p : nullptr; J.cost_mode = (uint32_t)cost_mode; J.err = d_err;
+    const int err = checked_launch(d_err, st, LaunchShape{grid, lds, W, 0}, [&] { launch(grid, J); });
+    if (err < 0) return err;
+    st->candidates = ncand;
+    *again = err == plo::ERR_TABLE;
+    if (*again) return PLO_OK;
+    if (err) return device_error(err);
+    if (adds) HIPCHK(hipMemcpy(adds, d_adds, ncand * 4, hipMemcpyDeviceToHost));
+    if (muls) HIPCHK(hipMemcpy(muls, d_muls, ncand * 4, hipMemcpyDeviceToHost));
+    if (best) {
+        unsigned long long w = 0;
+        HIPCHK(hipMemcpy(&w, d_best, 8, hipMemcpyDeviceToHost));
+        decode_key(w >> 32, cost_mode, 16u, &best->adds, &best->muls);
+        best->seed = seed0 + (w & 0xFFFFFFFFull);
+    }
+    return PLO_OK;
+}
 } // namespace
 
 extern "C" {
@@ -932,11 +994,12 @@ int plo_cse_plan_create_ex(const plo_csr_t *A, uint32_t p, uint32_t flags, plo_p
 {
     if (!A || !out || !A->rowptr || (A->rowptr[A->m] && (!A->col || !A->val))) return fail(PLO_E_ARG, "null argument");
     if (p < 3 || p >= 0x80000000u || !(p & 1u)) return fail(PLO_E_ARG, "modulus must be an odd prime below 2^31");
-    if (g_device < 0) { int rc = plo_init(0); if (rc != PLO_OK) return rc; }
+    int rc = require_device(NOINIT_DEVICE0);
+    if (rc != PLO_OK) return rc;
     if (const char *bad = csr_defect(A, p)) return fail(PLO_E_ARG, bad);
     plo_plan *pl = new plo_plan();
     set_matrix(pl, A, p);
-    int rc = (flags & PLO_PLAN_HBM) ? PLO_E_CAPACITY : build_plan(pl);
+    rc = (flags & PLO_PLAN_HBM) ? PLO_E_CAPACITY : build_plan(pl);
     if (rc == PLO_E_CAPACITY) rc = build_big_plan(pl);       // does not fit LDS: HBM-resident kernel family
     if (rc != PLO_OK) { plo_cse_plan_destroy(pl); return rc; }
     *out = pl;
@@ -987,13 +1050,8 @@ int plo_cse_plan_hbm_counters_ex(const plo_plan_t *pl, uint32_t *out, uint32_t n
 int plo_cse_plan_destroy(plo_plan_t *pl)
 {
     if (!pl) return PLO_OK;
-    if (pl->d_tmpl) (void)hipFree(pl->d_tmpl);
-    if (pl->d_err) (void)hipFree(pl->d_err);
-    if (pl->d_best) (void)hipFree(pl->d_best);
+    dev_free(pl->d_tmpl, pl->d_err, pl->d_best, pl->d_ws, pl->d_next, pl->d_stats);
     for (void *d : pl->big_bufs) (void)hipFree(d);
-    if (pl->d_ws) (void)hipFree(pl->d_ws);
-    if (pl->d_next) (void)hipFree(pl->d_next);
-    if (pl->d_stats) (void)hipFree(pl->d_stats);
     delete pl;
     return PLO_OK;
 }
@@ -1013,26 +1071,17 @@ int plo_cse_cost_many_plan(plo_plan_t *pl, const uint64_t *seeds, uint64_t seed0
                            uint32_t *adds, uint32_t *muls, plo_stats_t *st)
 {
     if (!pl || !adds || !muls) return fail(PLO_E_ARG, "null argument");
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init not called");
-    plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
-    auto t0 = std::chrono::steady_clock::now();
-    if (n == 0) return PLO_OK;
-    const int rc = cse_cost_many_run(n, seeds, adds, muls, nullptr, st, [&](uint32_t *d_adds, uint32_t *d_muls, uint64_t *d_seeds) {
+    if (const int rc = require_device(NOINIT_CSE)) return rc;
+    CallScope call(st); st = call.st;
+    if (n == 0) return PLO_OK;                                                   // (`seconds` stays 0)
+    return call.done(cse_cost_many_run(n, seeds, adds, muls, nullptr, st, [&](uint32_t *d_adds, uint32_t *d_muls, uint64_t *d_seeds) {
         return run_plan_job(pl, seed0, d_seeds, n, d_adds, d_muls, nullptr, 0, st);
-    });
-    st->seconds = seconds_since(t0);
-    return rc;
+    }));
 }
 
-int plo_cse_cost_many(const plo_csr_t *A, uint32_t p, const uint64_t *seeds, uint64_t seed0, uint64_t n,
-                      uint32_t *adds, uint32_t *muls)
+int plo_cse_cost_many(const plo_csr_t *A, uint32_t p, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *adds, uint32_t *muls)
 {
-    plo_plan_t *pl = nullptr;
-    int rc = plo_cse_plan_create(A, p, &pl);
-    if (rc != PLO_OK) return rc;
-    rc = plo_cse_cost_many_plan(pl, seeds, seed0, n, adds, muls, nullptr);
-    plo_cse_plan_destroy(pl);
-    return rc;
+    return with_plan(A, p, [&](plo_plan_t *pl) { return plo_cse_cost_many_plan(pl, seeds, seed0, n, adds, muls, nullptr); });
 }
 
 int plo_cse_search_plan(plo_plan_t *pl, uint64_t seed0, uint64_t nseeds, int cost_mode,
@@ -1040,9 +1089,8 @@ int plo_cse_search_plan(plo_plan_t *pl, uint64_t seed0, uint64_t nseeds, int cos
 {
     if (!pl || !out) return fail(PLO_E_ARG, "null argument");
     if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init not called");
-    plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
-    auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = require_device(NOINIT_CSE)) return rc;
+    CallScope call(st); st = call.st;
     out->adds = out->muls = 0xFFFFFFFFu; out->seed = ~0ull;
     uint64_t bkey = ~0ull, bseed = ~0ull;
     const bool big = pl->big;             // the 64-bit cost word of the HBM variant: 20-bit fields over 24-bit seed offsets; 16 over 32 otherwise
@@ -1061,37 +1109,32 @@ int plo_cse_search_plan(plo_plan_t *pl, uint64_t seed0, uint64_t nseeds, int cos
         out->adds = a; out->muls = mu; out->seed = bseed;
     }
     st->candidates = nseeds;
-    st->seconds = seconds_since(t0);
-    return PLO_OK;
+    return call.done(PLO_OK);
 }
 
 // -E: the schedule space of RecSub walked by index (PickState in plo_cse_wave.hip).  LDS-resident plans only.
 int plo_cse_enum_cost_many_plan(plo_plan_t *pl, uint64_t first, uint64_t n, uint32_t *adds, uint32_t *muls, uint64_t *prods, plo_stats_t *st)
 {
     if (!pl || !adds || !muls) return fail(PLO_E_ARG, "null argument");
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init not called");
+    if (const int rc = require_device(NOINIT_CSE)) return rc;
     if (pl->big) return fail(PLO_E_UNSUPPORTED, "schedule enumeration is for matrices of the LDS-resident kernel (the tree of anything larger cannot be walked)");
-    plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
-    auto t0 = std::chrono::steady_clock::now();
-    if (n == 0) return PLO_OK;
+    CallScope call(st); st = call.st;
+    if (n == 0) return PLO_OK;                                                   // (`seconds` stays 0)
     if (n > 0xFFFFFFFFull) return fail(PLO_E_ARG, "at most 2^32-1 schedules per call");
-    const int rc = cse_cost_many_run(n, nullptr, adds, muls, prods, st, [&](uint32_t *d_adds, uint32_t *d_muls, uint64_t *d_prods) {
+    return call.done(cse_cost_many_run(n, nullptr, adds, muls, prods, st, [&](uint32_t *d_adds, uint32_t *d_muls, uint64_t *d_prods) {
         plo::WaveJob J{}; J.seed0 = first; J.seeds = nullptr; J.ncand = n; J.adds = d_adds; J.muls = d_muls; J.best = nullptr; J.cost_mode = 0;
         J.enumerate = 1u; J.prods = (unsigned long long *)d_prods; J.prodmax = nullptr;
         return run_job(pl, J, st);
-    });
-    st->seconds = seconds_since(t0);
-    return rc;
+    }));
 }
 
 int plo_cse_enum_search_plan(plo_plan_t *pl, uint64_t first, uint64_t count, int cost_mode, plo_best_t *out, uint64_t *maxprod, plo_stats_t *st)
 {
     if (!pl || !out || !maxprod) return fail(PLO_E_ARG, "null argument");
     if (cost_mode != PLO_COST_SUM_THEN_ADD && cost_mode != PLO_COST_ADD_THEN_MUL && cost_mode != PLO_COST_RECSUB) return fail(PLO_E_ARG, "cost mode 0, 1 or 3");
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init not called");
+    if (const int rc = require_device(NOINIT_CSE)) return rc;
     if (pl->big) return fail(PLO_E_UNSUPPORTED, "schedule enumeration is for matrices of the LDS-resident kernel (the tree of anything larger cannot be walked)");
-    plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
-    auto t0 = std::chrono::steady_clock::now();
+    CallScope call(st); st = call.st;
     out->adds = out->muls = 0xFFFFFFFFu; out->seed = ~0ull; *maxprod = 0;
     DevBuf<unsigned long long> d_pm;
     HIPCHK(hipMalloc((void **)&d_pm.p, sizeof(unsigned long long)));
@@ -1108,19 +1151,12 @@ int plo_cse_enum_search_plan(plo_plan_t *pl, uint64_t first, uint64_t count, int
     if (count) { decode_key(bkey, cost_mode, 16u, &out->adds, &out->muls); out->seed = bidx; }
     *maxprod = pm;
     st->candidates = count;
-    st->seconds = seconds_since(t0);
-    return PLO_OK;
+    return call.done(PLO_OK);
 }
 
-int plo_cse_search(const plo_csr_t *A, uint32_t p, uint64_t seed0, uint64_t nseeds, int cost_mode,
-                   plo_best_t *out, plo_stats_t *stats)
+int plo_cse_search(const plo_csr_t *A, uint32_t p, uint64_t seed0, uint64_t nseeds, int cost_mode, plo_best_t *out, plo_stats_t *stats)
 {
-    plo_plan_t *pl = nullptr;
-    int rc = plo_cse_plan_create(A, p, &pl);
-    if (rc != PLO_OK) return rc;
-    rc = plo_cse_search_plan(pl, seed0, nseeds, cost_mode, out, stats);
-    plo_cse_plan_destroy(pl);
-    return rc;
+    return with_plan(A, p, [&](plo_plan_t *pl) { return plo_cse_search_plan(pl, seed0, nseeds, cost_mode, out, stats); });
 }
 
 } // extern "C" (the helpers below are C++)
@@ -1179,7 +1215,7 @@ CommSet *comm_for(const std::vector<int> &devs, std::string &why)
         for (int i = 0; i < n; ++i) { if (cs.dbuf[(size_t)i] || cs.strm[(size_t)i]) { (void)hipSetDevice(devs[(size_t)i]); if (cs.dbuf[(size_t)i]) (void)hipFree(cs.dbuf[(size_t)i]); if (cs.strm[(size_t)i]) (void)hipStreamDestroy(cs.strm[(size_t)i]); } if (cs.comms[(size_t)i]) R.CommDestroy(cs.comms[(size_t)i]); }
         return nullptr;
     }
-    cs.init_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    cs.init_seconds = seconds_since(t0);
     ++g_comm_inits;
     return &(cache[devs] = std::move(cs));
 }
@@ -1213,7 +1249,7 @@ bool rccl_min_pair(const std::vector<int> &devs, std::vector<std::array<unsigned
     for (int i = 0; i < n; ++i) hi0[(size_t)i] = w[(size_t)i][0];
     bool good = stage(0);
     if (good) { for (int i = 0; i < n; ++i) if (hi0[(size_t)i] != w[(size_t)i][0]) w[(size_t)i][1] = ~0ull; good = stage(1); }
-    seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    seconds = seconds_since(t0);
     return good;
 }
 
@@ -1316,7 +1352,7 @@ int sharded_search(uint64_t seed0, uint64_t nseeds, int ndev, const int *devices
     if (rc != PLO_OK) return rc;
     if (win < 0) return fail(PLO_E_INTERNAL, "no candidate reported");
     *best = bests[(size_t)win];
-    agg.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    agg.seconds = seconds_since(t0);
     if (stats) *stats = agg;
     return PLO_OK;
 }
@@ -1344,7 +1380,7 @@ int planless_search_multi(uint64_t seed0, uint64_t nseeds, int cost_mode, int nd
     if (rc != PLO_OK) return rc;
     out->adds = out->muls = 0xFFFFFFFFu; out->seed = ~0ull;
     if (win >= 0) *out = bests[(size_t)win];
-    agg.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    agg.seconds = seconds_since(t0);
     if (stats) *stats = agg;
     return PLO_OK;
 }
@@ -1391,15 +1427,14 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
 {
     if (!firsts || !seconds || npairs == 0 || per_pair == 0) return fail(PLO_E_ARG, "bad argument");
     if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init not called");
+    if (const int rc = require_device(NOINIT_CSE)) return rc;
     if (p < 3 || p >= 0x80000000u || !(p & 1u)) return fail(PLO_E_ARG, "modulus must be an odd prime below 2^31");
     for (uint32_t k = 0; k < npairs; ++k)
         for (const plo_csr_t *A : {&firsts[k], &seconds[k]})
             if (const char *bad = csr_defect(A, p)) return fail(PLO_E_ARG, "pair " + std::to_string(k) + ": " + bad);
     const uint64_t ncand = (uint64_t)npairs * per_pair;
     if (ncand > 0xFFFFFFFFull) return fail(PLO_E_ARG, "at most 2^32-1 candidates per call");
-    plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
+    CallScope call(st); st = call.st;
     if (best) { best->adds = best->muls = 0xFFFFFFFFu; best->seed = ~0ull; }
     std::atomic<bool> stuck{false};                  // some plan could not take twice the slots
     for (uint32_t cap_scale = 2; cap_scale <= 16; cap_scale *= 2) {
@@ -1441,7 +1476,7 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
         uint32_t lds = 0;
         const uint32_t W = pick_waves([&](uint32_t w) { return 64u + w * (2u * rsmax + region); }, false, g_lds_max, &lds);
         if (!W) return fail(PLO_E_CAPACITY, "chained candidate state does not fit LDS");
-        DevBuf<uint8_t> d_img; DevBuf<plo::WavePlan> d_plans; DevBuf<uint32_t> d_adds, d_muls, d_err; DevBuf<unsigned long long> d_best;
+        DevBuf<uint8_t> d_img; DevBuf<plo::WavePlan> d_plans;
         std::vector<uint8_t> blob(total + 64, 0);
         for (size_t k = 0; k < imgs.size(); ++k) std::memcpy(blob.data() + offs[k], imgs[k].data(), imgs[k].size());
         HIPCHK(hipMalloc((void **)&d_img.p, blob.size()));
@@ -1449,36 +1484,51 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
         for (size_t k = 0; k < plans.size(); ++k) plans[k].tmpl = (const uint64_t *)(d_img + offs[k]);
         HIPCHK(hipMalloc((void **)&d_plans.p, plans.size() * sizeof(plo::WavePlan)));
         HIPCHK(hipMemcpy(d_plans, plans.data(), plans.size() * sizeof(plo::WavePlan), hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc((void **)&d_err.p, 4)); HIPCHK(hipMemsetAsync(d_err, 0, 4, g_stream));
-        HIPCHK(hipMalloc((void **)&d_best.p, 8)); HIPCHK(hipMemsetAsync(d_best, 0xFF, 8, g_stream));
-        if (adds) HIPCHK(hipMalloc((void **)&d_adds.p, ncand * 4));
-        if (muls) HIPCHK(hipMalloc((void **)&d_muls.p, ncand * 4));
-        HIPCHK(hipFuncSetAttribute((const void *)plo::cse_chain_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int nb = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)plo::cse_chain_batch_kernel, (int)(W * 64), lds));
-        const uint64_t need = (ncand + W - 1) / W;
-        const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * std::max(nb, 1), need));
-        plo::WaveJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = ncand; J.adds = d_adds; J.muls = d_muls; J.best = best ? d_best.p : nullptr; J.cost_mode = (uint32_t)cost_mode; J.err = d_err;
-        const LaunchShape shape{grid, lds, W, 0};
-        const int trc = timed_launch(st, &shape, [&] { hipLaunchKernelGGL(plo::cse_chain_batch_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, (const plo::WavePlan *)d_plans, per_pair, region, rsmax, J); });
-        if (trc != PLO_OK) return trc;
-        st->candidates = ncand;
-        uint32_t err = 0; unsigned long long w = 0;
-        HIPCHK(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost));
-        if (err == plo::ERR_TABLE) continue;                                        // a pair table filled up: all plans again with twice the slots
-        if (err) return device_error((int)err);
-        if (adds) HIPCHK(hipMemcpy(adds, d_adds, ncand * 4, hipMemcpyDeviceToHost));
-        if (muls) HIPCHK(hipMemcpy(muls, d_muls, ncand * 4, hipMemcpyDeviceToHost));
-        if (best) {
-            HIPCHK(hipMemcpy(&w, d_best, 8, hipMemcpyDeviceToHost));
-            decode_key(w >> 32, cost_mode, 16u, &best->adds, &best->muls);          // (a sum-only key: the sum in .adds)
-            best->seed = seed0 + (w & 0xFFFFFFFFull);
-        }
-        st->seconds = seconds_since(t0);
-        return PLO_OK;
+        bool again = false;
+        const int rc = one_shot_search((const void *)plo::cse_chain_batch_kernel, W, lds, seed0, ncand, cost_mode, adds, muls, best, st, &again, [&](uint64_t grid, const plo::WaveJob &J) {
+            hipLaunchKernelGGL(plo::cse_chain_batch_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, (const plo::WavePlan *)d_plans, per_pair, region, rsmax, J);
+        });
+        if (rc != PLO_OK) return rc;
+        if (again) continue;                                                         // a pair table filled up: all plans again with twice the slots
+        return call.done(PLO_OK);
     }
     if (stuck) return fail(PLO_E_CAPACITY, "pair table full, and twice the slots do not fit the LDS-resident wave kernel");
     return device_error(plo::ERR_TABLE);
+}
+
+int plo_cse_chain_cost_many(plo_chain_t *ch, const uint64_t *seeds, uint64_t seed0, uint64_t n,
+                            uint32_t *adds, uint32_t *muls, plo_stats_t *st)
+{
+    if (!ch || !adds || !muls) return fail(PLO_E_ARG, "null argument");
+    CallScope call(st); st = call.st;                    // (as it was: no check for the device -- a chain exists only with one -- and `seconds` stays 0)
+    if (n == 0) return PLO_OK;
+    return cse_cost_many_run(n, seeds, adds, muls, nullptr, st, [&](uint32_t *d_adds, uint32_t *d_muls, uint64_t *d_seeds) {
+        plo::WaveJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.adds = d_adds; J.muls = d_muls; J.best = nullptr; J.cost_mode = 0;
+        return run_chain(ch, J, st);
+    });
+}
+
+int plo_cse_chain_search(plo_chain_t *ch, uint64_t seed0, uint64_t nseeds, int cost_mode, plo_best_t *out, plo_stats_t *st)
+{
+    if (!ch || !out) return fail(PLO_E_ARG, "null argument");
+    if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
+    CallScope call(st); st = call.st;                    // (as it was: no check for the device, and `seconds` stays 0)
+    out->adds = out->muls = 0xFFFFFFFFu; out->seed = ~0ull;
+    uint64_t bkey = ~0ull, bseed = ~0ull;
+    unsigned long long *d_best = ch->st[0]->d_best;
+    int rc = chunked_min(d_best, seed0, nseeds, 0xFFFFFFFFull, 32, &bkey, &bseed, [&](uint64_t s0, uint64_t cnt) {
+        plo::WaveJob J{}; J.seed0 = s0; J.ncand = cnt; J.best = d_best; J.cost_mode = (uint32_t)cost_mode;
+        return run_chain(ch, J, st);
+    });
+    if (rc != PLO_OK) return rc;
+    if (nseeds) {
+        uint32_t a = 0, mu = 0; plo_stats_t s2{};                            // the winner's costs from the device, whatever the key holds
+        rc = plo_cse_chain_cost_many(ch, &bseed, 0, 1, &a, &mu, &s2);
+        if (rc != PLO_OK) return rc;
+        out->adds = a; out->muls = mu; out->seed = bseed;
+    }
+    st->candidates = nseeds;
+    return PLO_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1517,6 +1567,74 @@ int layout_plan(plo::WavePlan &P, uint32_t m, uint32_t n, uint32_t nnz, uint32_t
     layout_wave_image(P);
     return PLO_OK;
 }
+// The PLO_KMETHOD_* knobs (tests and A/B runs).  depc_scratch, hard_bounds and debug are flags: set is on, whatever they hold.
+struct KmKnobs {
+    std::optional<long> depc_scratch = env_knob("PLO_KMETHOD_DEPC_SCRATCH"), hard_bounds = env_knob("PLO_KMETHOD_HARD_BOUNDS"), debug = env_knob("PLO_KM_DEBUG"),
+                        ent_margin = env_knob("PLO_KMETHOD_ENT_MARGIN"), pairs_div = env_knob("PLO_KMETHOD_PAIRS_DIV"), ent_div = env_knob("PLO_KMETHOD_ENT_DIV");
+};
+
+// The scratch of a wave (the small arrays of the decomposition; the combinations too with the A/B knob PLO_KMETHOD_DEPC_SCRATCH, the round-3 placement) and V (m x (n+1)) and
+// C (m x (rank+1)) of the elimination behind M's template.  Returns where V and C end.
+uint32_t kmethod_scratch_layout(plo::KPlan &K, uint32_t depc_bytes, bool depc_inside) {
+    uint32_t off = 0;
+    if (!depc_inside) { K.off_depc = (int32_t)off; off += depc_bytes; }
+    K.off_vrow = off;  off += 64u * 4u;
+    K.off_ord = off;   off += 128u * 2u;
+    K.off_piv = off;   off += 128u * 2u;
+    K.off_basis = off; off += 64u * 2u;
+    K.off_deps = off;  off += 64u * 2u;
+    K.off_rsd = off;   off += 66u * 2u;
+    K.scratch_bytes = round_up(off, 16);
+    K.off_vc = round_up(K.PM.tmpl_bytes, 16);
+    return K.off_vc + K.m * (K.n + 1u + K.rank + 1u) * 4u;
+}
+
+// The sizing launch: Dep's pair count and entries, maxima over a sample of the decompositions
+int kmethod_sample(plo::KPlan &K, uint64_t seed0, uint64_t nrestarts, uint32_t vc_end, uint32_t depc_bytes, bool depc_inside, plo_stats_t *st, uint32_t *pairs_max, uint32_t *ent_max) {
+    K.region = round_up(std::max(K.PM.region_bytes, vc_end), 16);
+    if (depc_inside) { const uint32_t at = K.region; K.region = at + depc_bytes; K.off_depc = -(int32_t)depc_bytes; }
+    uint32_t lds = 0;
+    const uint32_t W = pick_waves([&](uint32_t w) { return K.PM.rs_bytes + w * (K.region + K.scratch_bytes); }, false, g_lds_max, &lds);
+    if (!W) return fail(PLO_E_CAPACITY, "kernel-method state does not fit LDS");
+    DevBuf<uint32_t> d_sz, d_err;
+    HIPCHK(hipMalloc((void **)&d_err.p, 4)); HIPCHK(hipMemsetAsync(d_err, 0, 4, g_stream));
+    HIPCHK(hipMalloc((void **)&d_sz.p, 16)); HIPCHK(hipMemsetAsync(d_sz, 0, 16, g_stream));
+    HIPCHK(hipFuncSetAttribute((const void *)plo::kmethod_size_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    plo::WaveJob J{}; J.seed0 = seed0; J.ncand = std::min<uint64_t>(nrestarts, 4096); J.err = d_err;
+    const uint64_t grid = grid_for(J.ncand, W, (uint64_t)g_cus * 2u);
+    const int trc = timed_launch(st, nullptr, [&] { hipLaunchKernelGGL(plo::kmethod_size_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, d_sz.p); });
+    if (trc != PLO_OK) return trc;
+    uint32_t sz[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(sz, d_sz, 16, hipMemcpyDeviceToHost));
+    if (sz[2]) return device_error(plo::ERR_KDEC);
+    *pairs_max = sz[0]; *ent_max = sz[1];
+    return PLO_OK;
+}
+
+// Layout of Dep's image and of a wave's region for the search launch.  Rows <= m - rank and entries per row <= rank are hard bounds; the number of entries and the pair count come
+// from the sample of the sizing launch (+60 %; measured on 4x4x4_49_156_L: +25 % and +40 % are exceeded by a few of 10^6 restarts and the whole launch is repeated, +60 % and +80 %
+// never in 3 x 10^6: the rows of a restart are packed, a restart with more entries is reported -- ERR_TABLE -- and the launch repeated with the hard bound rows x rank, as for a
+// full table).  Round 2 sized the arrays for rows x rank: 17.3 KB per wave on 4x4x4_49_156_L, 7 waves per CU.
+int kmethod_dep_layout(plo::KPlan &K, const KmKnobs &knobs, uint32_t cap_scale, uint32_t pairs_max, uint32_t ent_max, uint32_t vc_end, uint32_t depc_bytes, bool depc_inside) {
+    const uint32_t R = K.rank, hard = K.ndeps * R;
+    uint32_t capD = 64;
+    while (capD < (cap_scale * pairs_max * 3u) / 4u + 16u) capD <<= 1;
+    uint32_t entD = (cap_scale == 1 && !knobs.hard_bounds) ? std::min<uint32_t>(hard, ent_max + (uint32_t)((uint64_t)ent_max * (knobs.ent_margin ? (uint32_t)*knobs.ent_margin : 60u) / 100u) + 16u) : hard;
+    if (knobs.ent_div && cap_scale == 1) entD = std::max<uint32_t>(R, entD / (uint32_t)std::max(1l, *knobs.ent_div));   // test knob: undersized entry arrays, exercises the repeat-with-hard-bounds path
+    const int rc = layout_plan(K.PD, K.ndeps, K.m, entD, K.PM.p, R, entD, capD);
+    if (rc != PLO_OK) return rc;
+    K.rsD = nullptr;                                                          // Dep's row starts are computed per restart on the device
+    K.region = round_up(std::max(std::max(K.PM.region_bytes, K.PD.region_bytes), vc_end), 16);
+    if (depc_inside) {
+        // the combinations live from the end of the decomposition to the end of Dep's image build: behind Free's region (Optimizer on Free
+        // runs meanwhile) and behind the elimination arrays (they are copied out of C), over Dep's tie list / multiplier list (idle until
+        // Dep's Optimizer call)
+        const uint32_t at = round_up(std::max(std::max(K.PM.region_bytes, vc_end), K.PD.off_ties), 16);
+        K.region = std::max(K.region, at + depc_bytes);
+        K.off_depc = (int32_t)at - (int32_t)K.region;
+    }
+    return PLO_OK;
+}
 } // namespace
 
 int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t nrestarts, uint32_t per_block, int cost_mode,
@@ -1524,25 +1642,27 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
 {
     if (!M || nrestarts == 0 || per_block == 0) return fail(PLO_E_ARG, "bad argument");
     if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init not called");
+    if (const int rc = require_device(NOINIT_CSE)) return rc;
     if (p < 3 || p >= 0x80000000u || !(p & 1u)) return fail(PLO_E_ARG, "modulus must be an odd prime below 2^31");
     if (const char *bad = csr_defect(M, p)) return fail(PLO_E_ARG, bad);
     if (M->m == 0 || M->m > 128 || M->n == 0 || M->n > 64) return fail(PLO_E_UNSUPPORTED, "device decomposition needs at most 128 rows and 64 columns");
     if (nrestarts > 0xFFFFFFFFull) return fail(PLO_E_ARG, "at most 2^32-1 restarts per call");
-    plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
+    CallScope call(st); st = call.st;
     if (best) { best->adds = best->muls = 0xFFFFFFFFu; best->seed = ~0ull; }
     const uint32_t m = M->m, n = M->n, R = rank_mod_p(M, p), ndeps = m - R;
     if (ndeps == 0) return fail(PLO_E_UNSUPPORTED, "zero dimensional kernel");
     if (ndeps > 64) return fail(PLO_E_UNSUPPORTED, "more than 64 dependent rows: Dep's ProgramGen keeps one row per lane");
     if (R == 0) return fail(PLO_E_UNSUPPORTED, "zero matrix");
 
+    const KmKnobs knobs;
+    const uint32_t depc_bytes = round_up(ndeps * R * 4u, 16);
+    const bool depc_inside = !knobs.depc_scratch;
     uint32_t pairs_max = 0, ent_max = 0;
     // Dep's table starts at 0.75 x the sampled PAIR count (an upper bound of its distinct triples, usually far above it): a
     // smaller image means more resident waves; a full table is reported by the device and the launch repeated with twice the slots
     for (uint32_t cap_scale = 1; cap_scale <= 32; cap_scale *= 2) {
         plo::KPlan K{};
-        DevBuf<uint8_t> d_img; DevBuf<uint32_t> d_adds, d_muls, d_info, d_err, d_sz; DevBuf<unsigned long long> d_best;      // of this attempt
+        DevBuf<uint8_t> d_img; DevBuf<uint32_t> d_info;      // of this attempt
         // plan and image of M (the layout of Free)
         plo_plan tmp; tmp.cap_scale = std::max(2u, cap_scale);
         set_matrix(&tmp, M, p);
@@ -1551,85 +1671,28 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
         if (rc != PLO_OK) return rc;
         K.PM = tmp.P; K.m = m; K.n = n; K.rank = R; K.ndeps = ndeps; K.per_block = per_block;
         K.mers = 0; for (uint32_t kk = 2; kk < 31; ++kk) if (p == (1u << kk) - 1u) K.mers = kk;
-        uint32_t off = 0;
-        const uint32_t depc_bytes = round_up(ndeps * R * 4u, 16);
-        const bool depc_inside = !getenv("PLO_KMETHOD_DEPC_SCRATCH");             // (A/B knob: the round-3 placement in the scratch)
-        if (!depc_inside) { K.off_depc = (int32_t)off; off += depc_bytes; }
-        K.off_vrow = off;  off += 64u * 4u;
-        K.off_ord = off;   off += 128u * 2u;
-        K.off_piv = off;   off += 128u * 2u;
-        K.off_basis = off; off += 64u * 2u;
-        K.off_deps = off;  off += 64u * 2u;
-        K.off_rsd = off;   off += 66u * 2u;
-        K.scratch_bytes = round_up(off, 16);
-        K.off_vc = round_up(K.PM.tmpl_bytes, 16);                                 // V (m x (n+1)) and C (m x (rank+1)) of the elimination, behind M's template
-        const uint32_t vc_end = K.off_vc + m * (n + 1u + R + 1u) * 4u;
+        const uint32_t vc_end = kmethod_scratch_layout(K, depc_bytes, depc_inside);
         HIPCHK(hipMalloc((void **)&d_img.p, img.size() + 64)); HIPCHK(hipMemcpy(d_img, img.data(), img.size(), hipMemcpyHostToDevice));
         K.PM.tmpl = (const uint64_t *)d_img.p;
-        HIPCHK(hipMalloc((void **)&d_err.p, 4)); HIPCHK(hipMemsetAsync(d_err, 0, 4, g_stream));
         if (cap_scale == 1) {
-            // sizing launch: Dep's pair count over a sample of the decompositions
-            K.region = round_up(std::max(K.PM.region_bytes, vc_end), 16);
-            if (depc_inside) { const uint32_t at = round_up(std::max(K.PM.region_bytes, vc_end), 16); K.region = at + depc_bytes; K.off_depc = -(int32_t)depc_bytes; }
-            uint32_t lds = 0;
-            const uint32_t W = pick_waves([&](uint32_t w) { return K.PM.rs_bytes + w * (K.region + K.scratch_bytes); }, false, g_lds_max, &lds);
-            if (!W) return fail(PLO_E_CAPACITY, "kernel-method state does not fit LDS");
-            HIPCHK(hipMalloc((void **)&d_sz.p, 16)); HIPCHK(hipMemsetAsync(d_sz, 0, 16, g_stream));
-            HIPCHK(hipFuncSetAttribute((const void *)plo::kmethod_size_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            plo::WaveJob J{}; J.seed0 = seed0; J.ncand = std::min<uint64_t>(nrestarts, 4096); J.err = d_err;
-            const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * 2u, (J.ncand + W - 1) / W));
-            const int trc = timed_launch(st, nullptr, [&] { hipLaunchKernelGGL(plo::kmethod_size_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, d_sz.p); });
-            if (trc != PLO_OK) return trc;
-            uint32_t sz[4] = {0, 0, 0, 0};
-            HIPCHK(hipMemcpy(sz, d_sz, 16, hipMemcpyDeviceToHost));
-            if (sz[2]) return device_error(plo::ERR_KDEC);
-            pairs_max = sz[0]; ent_max = sz[1];
-            if (const char *e = getenv("PLO_KMETHOD_PAIRS_DIV")) pairs_max /= (uint32_t)std::max(1l, strtol(e, nullptr, 10));   // test knob: undersized first table, exercises the repeat-with-more-slots path
+            if ((rc = kmethod_sample(K, seed0, nrestarts, vc_end, depc_bytes, depc_inside, st, &pairs_max, &ent_max)) != PLO_OK) return rc;
+            if (knobs.pairs_div) pairs_max /= (uint32_t)std::max(1l, *knobs.pairs_div);   // test knob: undersized first table, exercises the repeat-with-more-slots path
         }
-        // layout of Dep's image: rows <= m - rank, entries per row <= rank (hard bounds); the number of entries and the pair count from the
-        // sample of the sizing launch (+60 %; measured on 4x4x4_49_156_L: +25 % and +40 % are exceeded by a few of 10^6 restarts and the whole launch is repeated, +60 % and +80 % never in 3 x 10^6: the rows of a restart are packed, a restart with more entries is reported -- ERR_TABLE -- and
-        // the launch repeated with the hard bound rows x rank, as for a full table).  Round 2 sized the arrays for rows x rank: 17.3 KB per
-        // wave on 4x4x4_49_156_L, 7 waves per CU.
-        uint32_t capD = 64;
-        while (capD < (cap_scale * pairs_max * 3u) / 4u + 16u) capD <<= 1;
-        uint32_t entD = (cap_scale == 1 && !getenv("PLO_KMETHOD_HARD_BOUNDS")) ? std::min<uint32_t>(ndeps * R, ent_max + (uint32_t)((uint64_t)ent_max * (getenv("PLO_KMETHOD_ENT_MARGIN") ? (uint32_t)atoi(getenv("PLO_KMETHOD_ENT_MARGIN")) : 60u) / 100u) + 16u) : ndeps * R;
-        if (const char *e = getenv("PLO_KMETHOD_ENT_DIV")) { if (cap_scale == 1) entD = std::max<uint32_t>(R, entD / (uint32_t)std::max(1l, strtol(e, nullptr, 10))); }   // test knob: undersized entry arrays, exercises the repeat-with-hard-bounds path
-        rc = layout_plan(K.PD, ndeps, m, entD, p, R, entD, capD);
-        if (rc != PLO_OK) return rc;
-        K.rsD = nullptr;                                                          // Dep's row starts are computed per restart on the device
-        K.region = round_up(std::max(std::max(K.PM.region_bytes, K.PD.region_bytes), vc_end), 16);
-        if (depc_inside) {
-            // the combinations live from the end of the decomposition to the end of Dep's image build: behind Free's region (Optimizer on Free
-            // runs meanwhile) and behind the elimination arrays (they are copied out of C), over Dep's tie list / multiplier list (idle until
-            // Dep's Optimizer call)
-            const uint32_t at = round_up(std::max(std::max(K.PM.region_bytes, vc_end), K.PD.off_ties), 16);
-            K.region = std::max(K.region, at + depc_bytes);
-            K.off_depc = (int32_t)at - (int32_t)K.region;
-        }
+        if ((rc = kmethod_dep_layout(K, knobs, cap_scale, pairs_max, ent_max, vc_end, depc_bytes, depc_inside)) != PLO_OK) return rc;
         uint32_t lds = 0, bestw = 0;
         const uint32_t W = pick_waves([&](uint32_t w) { return K.PM.rs_bytes + K.PD.rs_bytes + w * (K.region + K.scratch_bytes); }, true, g_lds_max, &lds, &bestw);
         if (!W) return fail(PLO_E_CAPACITY, "kernel-method state does not fit LDS");
-        if (getenv("PLO_KM_DEBUG")) fprintf(stderr, "# kernel method layout: region of M %u B (table %u slots), of Dep %u B (table %u slots, sampled pairs %u, entries %u of at most %u), elimination arrays end at %u B, scratch %u B; %u waves per workgroup, %u B of LDS, %u waves per CU\n",
-                                            K.PM.region_bytes, K.PM.cap, K.PD.region_bytes, K.PD.cap, pairs_max, K.PD.nnz, ndeps * R, vc_end, K.scratch_bytes, W, lds, bestw);
-        HIPCHK(hipMalloc((void **)&d_best.p, 8)); HIPCHK(hipMemsetAsync(d_best, 0xFF, 8, g_stream));
-        if (adds) HIPCHK(hipMalloc((void **)&d_adds.p, nrestarts * 4));
-        if (muls) HIPCHK(hipMalloc((void **)&d_muls.p, nrestarts * 4));
+        if (knobs.debug) fprintf(stderr, "# kernel method layout: region of M %u B (table %u slots), of Dep %u B (table %u slots, sampled pairs %u, entries %u of at most %u), elimination arrays end at %u B, scratch %u B; %u waves per workgroup, %u B of LDS, %u waves per CU\n",
+                                 K.PM.region_bytes, K.PM.cap, K.PD.region_bytes, K.PD.cap, pairs_max, K.PD.nnz, ndeps * R, vc_end, K.scratch_bytes, W, lds, bestw);
         if (info) HIPCHK(hipMalloc((void **)&d_info.p, nrestarts * 12));
-        const void *fn = K.PM.unit ? (const void *)plo::kmethod_kernel<true> : (const void *)plo::kmethod_kernel<false>;
-        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int nb = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)(W * 64), lds));
-        const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * std::max(nb, 1), (nrestarts + W - 1) / W));
-        plo::WaveJob J{}; J.seed0 = seed0; J.ncand = nrestarts; J.adds = d_adds; J.muls = d_muls; J.best = best ? d_best.p : nullptr; J.cost_mode = (uint32_t)cost_mode; J.err = d_err;
-        plo::KInfo I{d_info.p};
-        const LaunchShape shape{grid, lds, W, 0};
-        const int trc = timed_launch(st, &shape, [&] {
+        const plo::KInfo I{d_info.p};
+        bool again = false;
+        rc = one_shot_search(K.PM.unit ? (const void *)plo::kmethod_kernel<true> : (const void *)plo::kmethod_kernel<false>, W, lds, seed0, nrestarts, cost_mode, adds, muls, best, st, &again,
+                             [&](uint64_t grid, const plo::WaveJob &J) {
             if (K.PM.unit) hipLaunchKernelGGL(plo::kmethod_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I);
             else hipLaunchKernelGGL(plo::kmethod_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I);
         });
-        if (trc != PLO_OK) return trc;
-        uint32_t err = 0; HIPCHK(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost));
-        st->candidates = nrestarts;
+        if (rc != PLO_OK) return rc;
 #ifdef PLO_KM_PROFILE
         if (getenv("PLO_KM_STATS")) {
             unsigned long long g[8] = {0};
@@ -1638,64 +1701,14 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
                         g[5], (double)g[0] / g[5], (double)g[1] / g[5], (double)g[2] / g[5], (double)g[3] / g[5], (double)g[4] / g[5], (double)g[6] / g[5], (double)g[7] / g[5]);
         }
 #endif
-        if (err == plo::ERR_TABLE) continue;                                     // a pair table filled up: again with twice the slots
-        if (err) return device_error((int)err);
-        if (adds) HIPCHK(hipMemcpy(adds, d_adds, nrestarts * 4, hipMemcpyDeviceToHost));
-        if (muls) HIPCHK(hipMemcpy(muls, d_muls, nrestarts * 4, hipMemcpyDeviceToHost));
+        if (again) continue;                                                     // a pair table filled up: again with twice the slots
         if (info) HIPCHK(hipMemcpy(info, d_info, nrestarts * 12, hipMemcpyDeviceToHost));
-        if (best) {
-            unsigned long long w = 0;
-            HIPCHK(hipMemcpy(&w, d_best, 8, hipMemcpyDeviceToHost));
-            decode_key(w >> 32, cost_mode, 16u, &best->adds, &best->muls);          // (a sum-only key: the sum in .adds, as plo_cse_chain_batch)
-            best->seed = seed0 + (w & 0xFFFFFFFFull);
-        }
-        st->seconds = seconds_since(t0);
-        return PLO_OK;
+        return call.done(PLO_OK);
     }
     return device_error(plo::ERR_TABLE);
 }
 
-int plo_cse_chain_cost_many(plo_chain_t *ch, const uint64_t *seeds, uint64_t seed0, uint64_t n,
-                            uint32_t *adds, uint32_t *muls, plo_stats_t *st)
-{
-    if (!ch || !adds || !muls) return fail(PLO_E_ARG, "null argument");
-    plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
-    if (n == 0) return PLO_OK;
-    return cse_cost_many_run(n, seeds, adds, muls, nullptr, st, [&](uint32_t *d_adds, uint32_t *d_muls, uint64_t *d_seeds) {
-        plo::WaveJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.adds = d_adds; J.muls = d_muls; J.best = nullptr; J.cost_mode = 0;
-        return run_chain(ch, J, st);
-    });
-}
-
-int plo_cse_chain_search(plo_chain_t *ch, uint64_t seed0, uint64_t nseeds, int cost_mode, plo_best_t *out, plo_stats_t *st)
-{
-    if (!ch || !out) return fail(PLO_E_ARG, "null argument");
-    if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
-    plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
-    out->adds = out->muls = 0xFFFFFFFFu; out->seed = ~0ull;
-    uint64_t bkey = ~0ull, bseed = ~0ull;
-    unsigned long long *d_best = ch->st[0]->d_best;
-    int rc = chunked_min(d_best, seed0, nseeds, 0xFFFFFFFFull, 32, &bkey, &bseed, [&](uint64_t s0, uint64_t cnt) {
-        plo::WaveJob J{}; J.seed0 = s0; J.ncand = cnt; J.best = d_best; J.cost_mode = (uint32_t)cost_mode;
-        return run_chain(ch, J, st);
-    });
-    if (rc != PLO_OK) return rc;
-    if (nseeds) {
-        uint32_t a = 0, mu = 0; plo_stats_t s2{};                            // the winner's costs from the device, whatever the key holds
-        rc = plo_cse_chain_cost_many(ch, &bseed, 0, 1, &a, &mu, &s2);
-        if (rc != PLO_OK) return rc;
-        out->adds = a; out->muls = mu; out->seed = bseed;
-    }
-    st->candidates = nseeds;
-    return PLO_OK;
-}
-
-int plo_cob_search(uint32_t n, uint32_t m, const uint32_t *TM, const uint32_t *Cand, uint32_t row, uint32_t offsetblock,
-                   const uint32_t *coeffs, uint32_t ncoeffs, uint32_t p, int32_t w0, int32_t w1,
-                   plo_cob_best_t *out, plo_stats_t *st)
-{
-    return plo_cob_search_range(n, m, TM, Cand, row, offsetblock, coeffs, ncoeffs, p, w0, w1, 0, (uint64_t)ncoeffs * ncoeffs * ncoeffs, out, st);
-}
+} // extern "C"
 
 namespace {
 // Host side of one enumeration: the right nullspace of the rows already chosen restricted to the block, the block of TM, the
@@ -1750,7 +1763,37 @@ void cob_decode(unsigned long long w, unsigned long long init, uint32_t n, int32
     if (out->found) { const uint32_t sc = (uint32_t)(w >> 32) - 1u; out->zeros_v = (int32_t)(sc / (n + 1)); out->zeros_w = (int32_t)(sc % (n + 1)); out->index = (uint32_t)~(uint32_t)w; }
     else { out->zeros_v = w0; out->zeros_w = w1; out->index = 0; }
 }
+
+// The context's scratch buffer grown to `words` words (with 1024 to spare) and its event pair created: both are kept between calls
+int cob_scratch(size_t words) {
+    DevCtx &cx = cur_ctx();
+    if (cx.cob_words < words) {
+        if (cx.cob_buf) (void)hipFree(cx.cob_buf);
+        cx.cob_buf = nullptr; cx.cob_words = 0;
+        HIPCHK(hipMalloc((void **)&cx.cob_buf, (words + 1024) * 4)); cx.cob_words = words + 1024;
+    }
+    if (!cx.cob_e0) { HIPCHK(hipEventCreate(&cx.cob_e0)); HIPCHK(hipEventCreate(&cx.cob_e1)); }
+    return PLO_OK;
+}
+// `up` into that buffer, then the one launch of an enumeration between the context's events: the statistics of the call but its candidates, algo_bytes and seconds
+template <class Launch> int cob_launch(const std::vector<uint32_t> &up, uint64_t grid, size_t lds, plo_stats_t *st, Launch launch) {
+    DevCtx &cx = cur_ctx();
+    HIPCHK(hipMemcpyAsync(cx.cob_buf, up.data(), up.size() * 4, hipMemcpyHostToDevice, g_stream));
+    float ms = 0;
+    if (const int rc = timed_between(cx.cob_e0, cx.cob_e1, &ms, launch)) return rc;
+    st->kernel_ms = ms; st->launches = 1; st->grid = (uint32_t)grid; st->lds_bytes = (uint32_t)lds; st->waves_per_wg = 4;
+    return PLO_OK;
+}
 } // namespace
+
+extern "C" {
+
+int plo_cob_search(uint32_t n, uint32_t m, const uint32_t *TM, const uint32_t *Cand, uint32_t row, uint32_t offsetblock,
+                   const uint32_t *coeffs, uint32_t ncoeffs, uint32_t p, int32_t w0, int32_t w1,
+                   plo_cob_best_t *out, plo_stats_t *st)
+{
+    return plo_cob_search_range(n, m, TM, Cand, row, offsetblock, coeffs, ncoeffs, p, w0, w1, 0, (uint64_t)ncoeffs * ncoeffs * ncoeffs, out, st);
+}
 
 // Up to PLO_COB_BATCH enumerations of the same shape (n, m, row, block) in ONE launch: one upload, one kernel (blockIdx.y = the
 // enumeration), one download.  bin/sparsifier over the rationals enumerates modulo two primes: one launch instead of two.
@@ -1758,9 +1801,8 @@ int plo_cob_search_batch(uint32_t nprob, uint32_t n, uint32_t m, uint32_t row, u
 {
     if (!prob || !out || nprob == 0 || nprob > PLO_COB_BATCH) return fail(PLO_E_ARG, "1 to 4 enumerations per launch");
     for (uint32_t k = 0; k < nprob; ++k) { const int rc = cob_check(n, m, prob[k].TM, prob[k].Cand, row, offsetblock, prob[k].coeffs, prob[k].ncoeffs, prob[k].p); if (rc != PLO_OK) return rc; }
-    if (g_device < 0) { int rc = plo_init(0); if (rc != PLO_OK) return rc; }
-    plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
-    auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = require_device(NOINIT_DEVICE0)) return rc;
+    CallScope call(st); st = call.st;
     CobPrep R[PLO_COB_BATCH]; uint32_t live[PLO_COB_BATCH], nlive = 0;
     for (uint32_t k = 0; k < nprob; ++k) {
         cob_prepare(n, m, prob[k].TM, prob[k].Cand, row, offsetblock, prob[k].p, prob[k].w0, prob[k].w1, R[k]);
@@ -1769,7 +1811,7 @@ int plo_cob_search_batch(uint32_t nprob, uint32_t n, uint32_t m, uint32_t row, u
         if (R[k].dependent) { out[k].found = 0; out[k].zeros_v = prob[k].w0; out[k].zeros_w = prob[k].w1; out[k].index = 0; }
         else live[nlive++] = k;
     }
-    if (nlive == 0) { st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); return PLO_OK; }
+    if (nlive == 0) return call.done(PLO_OK);
     // one device buffer kept by the context, one upload: [best words (2 each) | per enumeration: TM block | nullspace block | coefficients]
     DevCtx &cx = cur_ctx();
     size_t off[PLO_COB_BATCH][3], words = 2 * (size_t)nlive; bool tab = !getenv("PLO_COB_GENERIC"); size_t lds = 0;
@@ -1783,12 +1825,7 @@ int plo_cob_search_batch(uint32_t nprob, uint32_t n, uint32_t m, uint32_t row, u
     }
     for (uint32_t q = 0; q < nlive; ++q) { const uint32_t k = live[q], C = prob[k].ncoeffs; lds = std::max<size_t>(lds, tab ? (size_t)(4ull * C * ((size_t)B.ms[q] + B.qs[q]) * 4) : (4 * (size_t)m + 4 * (size_t)R[k].qn + C) * 4); }
     if (lds > g_lds_max) return fail(PLO_E_CAPACITY, "block of TM does not fit LDS");
-    if (cx.cob_words < words) {
-        if (cx.cob_buf) (void)hipFree(cx.cob_buf);
-        cx.cob_buf = nullptr; cx.cob_words = 0;
-        HIPCHK(hipMalloc((void **)&cx.cob_buf, (words + 1024) * 4)); cx.cob_words = words + 1024;
-    }
-    if (!cx.cob_e0) { HIPCHK(hipEventCreate(&cx.cob_e0)); HIPCHK(hipEventCreate(&cx.cob_e1)); }
+    if (const int rc = cob_scratch(words)) return rc;
     std::vector<uint32_t> up(words);
     for (uint32_t q = 0; q < nlive; ++q) {
         const uint32_t k = live[q], C = prob[k].ncoeffs, p = prob[k].p;
@@ -1800,21 +1837,14 @@ int plo_cob_search_batch(uint32_t nprob, uint32_t n, uint32_t m, uint32_t row, u
     }
     for (uint32_t q = nlive; q < PLO_COB_BATCH; ++q) B.J[q] = B.J[0];      // (never launched: blockIdx.y < nlive)
     B.tab = tab ? 1u : 0u;
-    HIPCHK(hipMemcpyAsync(cx.cob_buf, up.data(), words * 4, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipFuncSetAttribute((const void *)plo::cob_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const uint64_t grid = tab ? std::max<uint64_t>(1, std::min<uint64_t>((maxgroups + 3) / 4, (uint64_t)g_cus * 2)) : std::max<uint64_t>(1, std::min<uint64_t>((maxtotal + 255) / 256, (uint64_t)g_cus * 8));
-    HIPCHK(hipEventRecord(cx.cob_e0, g_stream));
-    hipLaunchKernelGGL(plo::cob_batch_kernel, dim3((uint32_t)grid, nlive), dim3(256), lds, g_stream, B);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(cx.cob_e1, g_stream)); HIPCHK(hipEventSynchronize(cx.cob_e1));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, cx.cob_e0, cx.cob_e1));
+    if (const int rc = cob_launch(up, grid, lds, st, [&] { hipLaunchKernelGGL(plo::cob_batch_kernel, dim3((uint32_t)grid, nlive), dim3(256), lds, g_stream, B); })) return rc;
     unsigned long long w[PLO_COB_BATCH] = {0, 0, 0, 0};
     HIPCHK(hipMemcpy(w, cx.cob_buf, 8 * (size_t)nlive, hipMemcpyDeviceToHost));
     for (uint32_t q = 0; q < nlive; ++q) { const uint32_t k = live[q]; cob_decode(w[q], R[k].init, n, prob[k].w0, prob[k].w1, &out[k]); }
-    st->kernel_ms = ms; st->launches = 1; st->grid = (uint32_t)grid; st->lds_bytes = (uint32_t)lds; st->waves_per_wg = 4;
     st->algo_bytes = (16ull * m + 8) * nlive;
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return PLO_OK;
+    return call.done(PLO_OK);
 }
 
 int plo_cob_search_range(uint32_t n, uint32_t m, const uint32_t *TM, const uint32_t *Cand, uint32_t row, uint32_t offsetblock,
@@ -1824,14 +1854,13 @@ int plo_cob_search_range(uint32_t n, uint32_t m, const uint32_t *TM, const uint3
     if (!out) return fail(PLO_E_ARG, "null argument");
     { const int rc = cob_check(n, m, TM, Cand, row, offsetblock, coeffs, ncoeffs, p); if (rc != PLO_OK) return rc; }
     if (first_group > (uint64_t)ncoeffs * ncoeffs * ncoeffs || ngroups > (uint64_t)ncoeffs * ncoeffs * ncoeffs - first_group) return fail(PLO_E_ARG, "group range outside the (i,j,k) prefixes");
-    if (g_device < 0) { int rc = plo_init(0); if (rc != PLO_OK) return rc; }
-    plo_stats_t local{}; if (!st) st = &local; else *st = plo_stats_t{};
-    auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = require_device(NOINIT_DEVICE0)) return rc;
+    CallScope call(st); st = call.st;
     CobPrep R; cob_prepare(n, m, TM, Cand, row, offsetblock, p, w0, w1, R);
     if (R.dependent) {      // chosen rows are dependent: rank(Cand with row := w) can never exceed `row` (:174)
         out->found = 0; out->zeros_v = w0; out->zeros_w = w1; out->index = 0;
         st->candidates = ngroups * ncoeffs;
-        return PLO_OK;
+        return PLO_OK;                                       // (`seconds` stays 0 here, unlike the batch entry)
     }
     const uint32_t qn = R.qn, fb = R.fb; const std::vector<uint32_t> &nb = R.nb, &tmb = R.tmb; const unsigned long long init = R.init;
     const uint64_t first = first_group * ncoeffs, total = (first_group + ngroups) * ncoeffs;      // flattened (i,j,k,l) range of this call
@@ -1840,15 +1869,9 @@ int plo_cob_search_range(uint32_t n, uint32_t m, const uint32_t *TM, const uint3
     // one device buffer kept by the context, one upload: [best word (2) | TM block | nullspace block | coefficients]
     DevCtx &cx = cur_ctx();
     const size_t o_tm = 2, o_nb = o_tm + tmb.size(), o_cf = o_nb + nb.size(), words = o_cf + ncoeffs;
-    if (cx.cob_words < words) {
-        if (cx.cob_buf) (void)hipFree(cx.cob_buf);
-        cx.cob_buf = nullptr; cx.cob_words = 0;
-        HIPCHK(hipMalloc((void **)&cx.cob_buf, (words + 1024) * 4)); cx.cob_words = words + 1024;
-    }
-    if (!cx.cob_e0) { HIPCHK(hipEventCreate(&cx.cob_e0)); HIPCHK(hipEventCreate(&cx.cob_e1)); }
+    if (const int rc = cob_scratch(words)) return rc;
     std::vector<uint32_t> up(words);
     memcpy(up.data(), &init, 8); memcpy(up.data() + o_tm, tmb.data(), tmb.size() * 4); memcpy(up.data() + o_nb, nb.data(), nb.size() * 4); memcpy(up.data() + o_cf, coeffs, (size_t)ncoeffs * 4);
-    HIPCHK(hipMemcpyAsync(cx.cob_buf, up.data(), words * 4, hipMemcpyHostToDevice, g_stream));
     uint32_t *d_tm = cx.cob_buf + o_tm, *d_nb = cx.cob_buf + o_nb, *d_cf = cx.cob_buf + o_cf; unsigned long long *d_best = (unsigned long long *)cx.cob_buf;
     plo::CobJob J{}; J.n = n; J.m = m; J.qn = qn; J.fb = fb; J.C = ncoeffs; J.p = p; J.mu = (~0ull) / p; J.first = first; J.total = total;
     J.tm = d_tm; J.nb = d_nb; J.coeffs = d_cf; J.best = d_best;
@@ -1856,29 +1879,18 @@ int plo_cob_search_range(uint32_t n, uint32_t m, const uint32_t *TM, const uint3
     const uint32_t mstride = m | 1u, qstride = std::max<uint32_t>(qn, 1u) | 1u;
     const size_t lds_tab = 4ull * ncoeffs * ((size_t)mstride + qstride) * 4;
     const bool use_tab = lds_tab <= 72u * 1024u && !getenv("PLO_COB_GENERIC");
-    hipEvent_t e0 = cx.cob_e0, e1 = cx.cob_e1;
-    uint64_t grid;
-    if (use_tab) {
-        HIPCHK(hipFuncSetAttribute((const void *)plo::cob_tab_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tab));
-        grid = std::max<uint64_t>(1, std::min<uint64_t>((ngroups + 3) / 4, (uint64_t)g_cus * 2));
-        HIPCHK(hipEventRecord(e0, g_stream));
-        hipLaunchKernelGGL(plo::cob_tab_kernel, dim3((uint32_t)grid), dim3(256), lds_tab, g_stream, J, mstride, qstride);
-    } else {
-        HIPCHK(hipFuncSetAttribute((const void *)plo::cob_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        grid = std::max<uint64_t>(1, std::min<uint64_t>((total - first + 255) / 256, (uint64_t)g_cus * 8));
-        HIPCHK(hipEventRecord(e0, g_stream));
-        hipLaunchKernelGGL(plo::cob_kernel, dim3((uint32_t)grid), dim3(256), lds, g_stream, J);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, g_stream)); HIPCHK(hipEventSynchronize(e1));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    HIPCHK(hipFuncSetAttribute(use_tab ? (const void *)plo::cob_tab_kernel : (const void *)plo::cob_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(use_tab ? lds_tab : lds)));
+    const uint64_t grid = use_tab ? std::max<uint64_t>(1, std::min<uint64_t>((ngroups + 3) / 4, (uint64_t)g_cus * 2)) : std::max<uint64_t>(1, std::min<uint64_t>((total - first + 255) / 256, (uint64_t)g_cus * 8));
+    if (const int rc = cob_launch(up, grid, use_tab ? lds_tab : lds, st, [&] {
+            if (use_tab) hipLaunchKernelGGL(plo::cob_tab_kernel, dim3((uint32_t)grid), dim3(256), lds_tab, g_stream, J, mstride, qstride);
+            else hipLaunchKernelGGL(plo::cob_kernel, dim3((uint32_t)grid), dim3(256), lds, g_stream, J);
+        })) return rc;
     unsigned long long w = 0;
     HIPCHK(hipMemcpy(&w, d_best, 8, hipMemcpyDeviceToHost));
     cob_decode(w, init, n, w0, w1, out);
-    st->kernel_ms = ms; st->launches = 1; st->candidates = total - first; st->grid = (uint32_t)grid; st->lds_bytes = (uint32_t)(use_tab ? lds_tab : lds); st->waves_per_wg = 4;
+    st->candidates = total - first;
     st->algo_bytes = 16ull * m + 8;                       // the 4 x m block of TM, once, plus the result word
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return PLO_OK;
+    return call.done(PLO_OK);
 }
 
 } // extern "C"
@@ -1897,14 +1909,12 @@ struct plo_lin_plan : AtomsPlan { plo::LinPlan P{}; };
 namespace {
 // Launch of a trilplacer or inplacer job (one wavefront per candidate, plo::TrilJob): `kernel` is the plan's instantiation, `tool` names it in the error text
 template <class Plan, class Kernel> int atoms_launch(Plan *pl, Kernel kernel, const char *tool, plo::TrilJob J, plo_stats_t *st) {
-    HIPCHK(hipMemsetAsync(pl->d_err, 0, sizeof(uint32_t), g_stream));
     J.err = pl->d_err;
-    const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
-    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * pl->blocks_per_cu, need));
-    const int rc = timed_launch(pl, grid, J.ncand, st, [&] { hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J); });
-    if (rc != PLO_OK) return rc;
-    uint32_t err = 0;
-    HIPCHK(hipMemcpy(&err, pl->d_err, sizeof err, hipMemcpyDeviceToHost));
+    const uint64_t grid = grid_for(J.ncand, pl->waves_per_wg, (uint64_t)g_cus * pl->blocks_per_cu);
+    const int err = checked_launch(pl->d_err, st, LaunchShape{grid, pl->lds_bytes, pl->waves_per_wg, pl->algo_bytes},
+                                   [&] { hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J); });
+    if (err < 0) return err;
+    st->candidates += J.ncand;
     if (err) return fail(err == plo::TERR_CAP ? PLO_E_INTERNAL : PLO_E_UNSUPPORTED, std::string("device (") + tool + "): error " + std::to_string(err));
     return PLO_OK;
 }
@@ -1912,19 +1922,17 @@ template <class Plan, class Kernel> int atoms_launch(Plan *pl, Kernel kernel, co
 // Body of a plo_*_cost_many entry of these searches: `width` words per candidate come back in `out`; launch(d_out, d_seeds, st) fills in
 // the job and launches it
 template <class Launch> int cost_many_run(const void *pl, const uint64_t *seeds, uint64_t n, uint32_t width, uint32_t *out, plo_stats_t *stats, Launch launch) {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;      // (the device before the arguments, here and in atoms_search)
     if (!pl || !out) return fail(PLO_E_ARG, "null argument");
     if (n >= (1ull << 31)) return fail(PLO_E_ARG, "at most 2^31-1 candidates per call");
-    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
-    if (n == 0) return PLO_OK;
+    CallScope call(stats); plo_stats_t *st = call.st;
+    if (n == 0) return PLO_OK;                                       // (`seconds` stays 0)
     DevBuf<uint32_t> d_out; DevBuf<uint64_t> d_seeds;
     HIPCHK(hipMalloc((void **)&d_out.p, n * width * sizeof(uint32_t)));
     if (seeds && (hipMalloc((void **)&d_seeds.p, n * 8) != hipSuccess || hipMemcpy(d_seeds, seeds, n * 8, hipMemcpyHostToDevice) != hipSuccess)) return fail(PLO_E_HIP, "seed upload");
     int rc = launch(d_out.p, d_seeds.p, st);
     if (rc == PLO_OK && hipMemcpy(out, d_out, n * width * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back");
-    st->seconds = seconds_since(t0);
-    return rc;
+    return call.done(rc);
 }
 
 int tril_launch(plo_tril_plan *pl, plo::TrilJob J, plo_stats_t *st) {
@@ -1939,11 +1947,7 @@ int lin_launch(plo_lin_plan *pl, plo::TrilJob J, plo_stats_t *st) {
 }
 
 template <class Plan> void atoms_destroy(Plan *pl) {
-    if (!pl) return;
-    if (pl->d_img) (void)hipFree(pl->d_img);
-    if (pl->d_err) (void)hipFree(pl->d_err);
-    if (pl->d_best) (void)hipFree(pl->d_best);
-    delete pl;
+    if (pl) { dev_free(pl->d_img, pl->d_err, pl->d_best); delete pl; }
 }
 
 // ---- the plo::TrilMat image of a rational CSR matrix.  Entries num/den: all +-1 gives the unit kernel (small signed values);
@@ -2015,13 +2019,20 @@ template <class Plan> int atoms_finish(Plan *pl, uint32_t lds_per_wave, const st
     return PLO_OK;
 }
 
+// Body of plo_tril_cost_many and plo_lin_cost_many: the six counts of every candidate
+template <class Plan> int atoms_cost_many(Plan *pl, int (*launch)(Plan *, plo::TrilJob, plo_stats_t *), const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats) {
+    return cost_many_run(pl, seeds, n, 6, ops6, stats, [&](uint32_t *d_ops, const uint64_t *d_seeds, plo_stats_t *st) {
+        plo::TrilJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.ops = d_ops; J.best = nullptr;
+        return launch(pl, J, st);
+    });
+}
+
 // Body of plo_tril_search and plo_lin_search: *w gets the packed word of the best candidate, (ADD << 48 | SCA << 32 | (seed - seed0) << 1 | variant)
 template <class Plan> int atoms_search(Plan *pl, const void *best, int (*launch)(Plan *, plo::TrilJob, plo_stats_t *), uint64_t seed0, uint64_t nseeds, unsigned long long *w, plo_stats_t *stats) {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
     if (!pl || !best) return fail(PLO_E_ARG, "null argument");
     if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
-    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
+    CallScope call(stats); plo_stats_t *st = call.st;
     const unsigned long long init = ~0ull;
     HIPCHK(hipMemcpy(pl->d_best, &init, 8, hipMemcpyHostToDevice));
     plo::TrilJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.ops = nullptr; J.best = pl->d_best;
@@ -2029,8 +2040,7 @@ template <class Plan> int atoms_search(Plan *pl, const void *best, int (*launch)
     if (rc != PLO_OK) return rc;
     HIPCHK(hipMemcpy(w, pl->d_best, 8, hipMemcpyDeviceToHost));
     if (*w == init) return fail(PLO_E_INTERNAL, "no candidate reported");
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return PLO_OK;
+    return call.done(PLO_OK);
 }
 } // namespace
 
@@ -2040,7 +2050,7 @@ int plo_tril_plan_create(const plo_icsr_t *A, const plo_icsr_t *B, const plo_ics
 
 int plo_tril_plan_create_q(const plo_qcsr_t *A, const plo_qcsr_t *B, const plo_qcsr_t *T, int expanded, plo_tril_plan_t **plan)
 {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
     if (!A || !B || !T || !plan) return fail(PLO_E_ARG, "null argument");
     const plo_qcsr_t *Ms[3] = {A, B, T};
     if (A->m == 0 || A->m != B->m || A->m != T->m) return fail(PLO_E_ARG, "A, B and T (transposed product matrix) need the same number of rows");
@@ -2086,13 +2096,7 @@ int plo_tril_plan_create_x(const plo_icsr_t *A, const plo_icsr_t *B, const plo_i
 
 void plo_tril_plan_destroy(plo_tril_plan_t *pl) { atoms_destroy(pl); }
 
-int plo_tril_cost_many(plo_tril_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats)
-{
-    return cost_many_run(pl, seeds, n, 6, ops6, stats, [&](uint32_t *d_ops, const uint64_t *d_seeds, plo_stats_t *st) {
-        plo::TrilJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.ops = d_ops; J.best = nullptr;
-        return tril_launch(pl, J, st);
-    });
-}
+int plo_tril_cost_many(plo_tril_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats) { return atoms_cost_many(pl, tril_launch, seeds, seed0, n, ops6, stats); }
 
 int plo_tril_search(plo_tril_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_tril_best_t *best, plo_stats_t *stats)
 {
@@ -2130,7 +2134,7 @@ extern "C" {
 
 int plo_lin_plan_create_q(const plo_qcsr_t *A, plo_lin_plan_t **plan)
 {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
     if (!A || !plan) return fail(PLO_E_ARG, "null argument");
     if (!A->rowptr || !A->col || !A->num || A->m == 0 || A->n == 0) return fail(PLO_E_ARG, "bad matrix");
     if (A->m > 16382u || A->n > 16382u) return fail(PLO_E_CAPACITY, "more than 16382 rows or columns (an atom holds 14-bit variables)");
@@ -2156,13 +2160,7 @@ int plo_lin_plan_create_q(const plo_qcsr_t *A, plo_lin_plan_t **plan)
 
 void plo_lin_plan_destroy(plo_lin_plan_t *pl) { atoms_destroy(pl); }
 
-int plo_lin_cost_many(plo_lin_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats)
-{
-    return cost_many_run(pl, seeds, n, 6, ops6, stats, [&](uint32_t *d_ops, const uint64_t *d_seeds, plo_stats_t *st) {
-        plo::TrilJob J{}; J.seed0 = seed0; J.seeds = d_seeds; J.ncand = n; J.ops = d_ops; J.best = nullptr;
-        return lin_launch(pl, J, st);
-    });
-}
+int plo_lin_cost_many(plo_lin_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats) { return atoms_cost_many(pl, lin_launch, seeds, seed0, n, ops6, stats); }
 
 int plo_lin_search(plo_lin_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_lin_best_t *best, plo_stats_t *stats)
 {
@@ -2215,6 +2213,7 @@ bool orbit_shape(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, 
     n = (uint32_t)s; m = P->m / n; k = R->n / n;
     return (uint64_t)m * k == L->n && (uint64_t)k * n == R->n && (uint64_t)m * n == P->m;
 }
+
 const char *qcsr_defect(const plo_qcsr_t *A) {
     if (!A->rowptr || (A->rowptr[A->m] && (!A->col || !A->num))) return "null arrays";
     for (uint32_t i = 0; i < A->m; ++i) {
@@ -2227,6 +2226,15 @@ const char *qcsr_defect(const plo_qcsr_t *A) {
     return nullptr;
 }
 int64_t gcd64(int64_t a, int64_t b) { if (a < 0) a = -a; if (b < 0) b = -b; while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
+// the residue of num/den modulo p, false when den is no unit
+bool residue_of(int64_t num, int64_t den, uint32_t p, uint32_t &out) {
+    int64_t d = den % (int64_t)p, a = num % (int64_t)p;
+    if (d < 0) d += p;
+    if (a < 0) a += p;
+    if (gcd64(d, p) != 1) return false;
+    out = (uint32_t)((uint64_t)a * inv_mod((uint32_t)d, p) % p);
+    return true;
+}
 
 using orbit_fn_t = void (*)(plo::OrbitPlan, plo::OrbitJob);
 orbit_fn_t orbit_fn(bool mod, int action) {
@@ -2326,7 +2334,7 @@ int orbit_cse_size(plo_orbit_plan *pl)
     const orbit_cse_fn_t fn = orbit_cse_fn(pl->action, true);
     HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     plo::OrbitJob J{}; J.seeds = d_seeds; J.ncand = 256;
-    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g_cus * 2u, (J.ncand + W - 1) / W));
+    const uint64_t grid = grid_for(J.ncand, W, (uint64_t)g_cus * 2u);
     const int rc = timed_launch((plo_stats_t *)nullptr, nullptr, [&] { hipLaunchKernelGGL(fn, dim3((uint32_t)grid), dim3(64 * W), lds, g_stream, pl->P, J, C, d_sz.p); });
     if (rc != PLO_OK) return rc;
     uint32_t sz[9] = {0};
@@ -2336,25 +2344,21 @@ int orbit_cse_size(plo_orbit_plan *pl)
 }
 
 int orbit_launch(plo_orbit_plan *pl, plo::OrbitJob J, plo_stats_t *st) {
-    const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
-    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(pl->grid_max, need));
+    const uint64_t grid = grid_for(J.ncand, pl->waves_per_wg, pl->grid_max);
     if (!pl->cse)
         return timed_launch(pl, grid, J.ncand, st, [&] {
             hipLaunchKernelGGL(orbit_fn(pl->P.p != 0, pl->action), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
         });
-    HIPCHK(hipMemsetAsync(pl->d_err, 0, 4, g_stream));
-    int rc = timed_launch(pl, grid, J.ncand, st, [&] {
+    const int err = checked_launch(pl->d_err, st, LaunchShape{grid, pl->lds_bytes, pl->waves_per_wg, pl->algo_bytes}, [&] {
         hipLaunchKernelGGL(orbit_cse_fn(pl->action, false), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J, pl->C, (uint32_t *)nullptr);
     });
-    if (rc != PLO_OK) return rc;
-    uint32_t err = 0;
-    HIPCHK(hipMemcpy(&err, pl->d_err, 4, hipMemcpyDeviceToHost));
-    if (err == plo::ERR_TABLE) {                          // a table or the entry arrays were outgrown: again with twice the slots and the hard entry bound
-        if (st) st->candidates -= J.ncand;
+    if (err < 0) return err;
+    if (err == plo::ERR_TABLE) {                          // a table or the entry arrays were outgrown: again with twice the slots and the hard entry bound (its candidates are not counted)
         ++pl->cse_relaunches; pl->cse_scale *= 2;
-        rc = orbit_cse_layout(pl);
+        const int rc = orbit_cse_layout(pl);
         return rc != PLO_OK ? rc : (int)ORBIT_AGAIN;
     }
+    if (st) st->candidates += J.ncand;
     if (err) return fail(PLO_E_INTERNAL, "device: error word " + std::to_string(err) + " in the CSE measure of the orbit search");
 #ifdef PLO_ORBIT_CSE_PROFILE
     if (getenv("PLO_ORBIT_CSE_STATS")) {
@@ -2368,8 +2372,7 @@ int orbit_launch(plo_orbit_plan *pl, plo::OrbitJob J, plo_stats_t *st) {
 }
 
 int orbit_growth_launch(plo_orbit_plan *pl, plo::OrbitGrowthJob J, plo_stats_t *st) {
-    const uint64_t need = (J.ncand + pl->waves_per_wg - 1) / pl->waves_per_wg;
-    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(pl->grid_max, need));
+    const uint64_t grid = grid_for(J.ncand, pl->waves_per_wg, pl->grid_max);
     J.off_sum = pl->g_off_sum; J.wave_bytes = pl->g_wave_bytes;
     return timed_launch(pl, grid, J.ncand, st, [&] {
         hipLaunchKernelGGL(orbit_growth_fn(pl->action), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
@@ -2383,62 +2386,15 @@ __int128 orbit_factor_bound(int action, uint32_t sd, uint32_t si) {
     if (action == PLO_ORBIT_ACT_HOUSEHOLDER) return (__int128)sd * si;
     return (__int128)1 << (si >= 2 ? si - 2 : 0);
 }
-} // namespace
 
-static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan);
-
-extern "C" {
-
-int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, plo_orbit_plan_t **plan)
-{
-    return plo_orbit_plan_create_act(L, R, P, modulus, measure, PLO_ORBIT_ACT_TRIANGULAR, plan);
-}
-
-int plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, plo_orbit_plan_t **plan)
-{
-    if (measure == PLO_ORBIT_CSE) return fail(PLO_E_ARG, "PLO_ORBIT_CSE needs sub and cse_seed0: plo_orbit_plan_create_cse");
-    // (the growth factor has its own create function; here the measure is refused with the words every unknown measure gets)
-    if (measure == PLO_ORBIT_GROWTH) return fail(PLO_E_ARG, !L || !R || !P || !plan ? "null argument" : "measure must be PLO_ORBIT_DENSITY or PLO_ORBIT_CANONICAL");
-    return orbit_plan_build(L, R, P, modulus, measure, action, 0, 0, plan);
-}
-
-int plo_orbit_plan_create_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int action, uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan)
-{
-    if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
-    if (modulus == 0 || !(modulus & 1) || modulus >= (1ull << 31) || !is_prime32(modulus)) return fail(PLO_E_ARG, "the CSE measure needs an odd prime modulus below 2^31");
-    if (sub == 0 || sub > 65536u) return fail(PLO_E_ARG, "sub outside [1, 65536]");
-    return orbit_plan_build(L, R, P, modulus, PLO_ORBIT_CSE, action, sub, cse_seed0, plan);
-}
-
-int plo_orbit_plan_create_growth(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, int action, plo_orbit_plan_t **plan)
-{
-    if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
-    if (action == PLO_ORBIT_ACT_HOUSEHOLDER) return fail(PLO_E_ARG, "the Householder action is orthogonal and preserves the 2-norm growth factor: there is nothing to search");
-    return orbit_plan_build(L, R, P, 0, PLO_ORBIT_GROWTH, action, 0, 0, plan);
-}
-
-int plo_orbit_plan_info(plo_orbit_plan_t *pl, uint32_t out[8])
-{
-    if (!pl || !out) return fail(PLO_E_ARG, "null argument");
-    out[0] = pl->waves_per_wg; out[1] = pl->lds_bytes;
-    for (int i = 0; i < 3; ++i) out[2 + i] = pl->cse ? pl->C.W[i].cap : 0u;
-    out[5] = pl->cse ? std::max(pl->C.W[0].nnz, std::max(pl->C.W[1].nnz, pl->C.W[2].nnz)) : 0u;
-    out[6] = pl->cse_relaunches; out[7] = pl->cse ? pl->C.keep_full : 0u;
-    return PLO_OK;
-}
-
-} // extern "C"
-
-// the body of the create functions; sub > 0: a PLO_ORBIT_CSE plan
-static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan)
-{
+// A plan is built in three steps (orbit_plan_build below).  1: admission.  The order of the checks decides which refusal an input with two defects gets; m, k, n come back.
+int orbit_admit(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, const void *plan, uint32_t &m, uint32_t &k, uint32_t &n) {
     const bool cse = measure == PLO_ORBIT_CSE, growth = measure == PLO_ORBIT_GROWTH;
     if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
     if (!cse && !growth && measure != PLO_ORBIT_DENSITY && measure != PLO_ORBIT_CANONICAL) return fail(PLO_E_ARG, "measure must be PLO_ORBIT_DENSITY or PLO_ORBIT_CANONICAL");
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
     if (action != PLO_ORBIT_ACT_TRIANGULAR && action != PLO_ORBIT_ACT_PLUQ && action != PLO_ORBIT_ACT_HOUSEHOLDER) return fail(PLO_E_ARG, "action must be one of PLO_ORBIT_ACT_*");
     if (modulus == 1) return fail(PLO_E_ARG, "modulus 1");
-    uint32_t m = 0, k = 0, n = 0;
     if (!orbit_shape(L, R, P, m, k, n)) return fail(PLO_E_ARG, "shapes are not r x mk, r x kn, mn x r");
     for (const plo_qcsr_t *A : {L, R, P}) if (const char *d = qcsr_defect(A)) return fail(PLO_E_ARG, d);
     if (modulus >= (1ull << 31)) return fail(PLO_E_UNSUPPORTED, "modulus of 2^31 or more: host path only");
@@ -2450,7 +2406,15 @@ static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
         if (r > 64 || m * n > 64) return fail(PLO_E_CAPACITY, "CSE measure: r or mn above 64 (ProgramGen of the wave kernel keeps one row per lane)");
         if (m * k > 64 || k * n > 64) return fail(PLO_E_CAPACITY, "CSE measure: mk or kn above 64 (a transformed row of more than 64 entries)");
     }
-    // the rows of L, of R and of P^T, each as (position, value) lists
+    return PLO_OK;
+}
+
+// 2: the 3r rows of L, of R and of P^T as the kernels take them: residues modulo the modulus, or over Q integers after a scale per
+// row, with the proofs that every sum the kernels form stays below 2^62 (and below 2^53 for the growth measure's doubles)
+struct OrbitRows { std::vector<int64_t> val, scale; std::vector<uint16_t> pos; std::vector<uint32_t> rp{0}; };
+int orbit_rows_image(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint32_t m, uint32_t k, uint32_t n, uint64_t modulus, int action, bool growth, OrbitRows &I) {
+    const uint32_t r = L->m;
+    // the rows, each as (position, value) lists
     std::vector<std::vector<std::pair<uint16_t, std::pair<int64_t, int64_t>>>> rows(3u * r);
     for (uint32_t i = 0; i < r; ++i) {
         for (uint32_t e = L->rowptr[i]; e < L->rowptr[i + 1]; ++e) rows[i].push_back({(uint16_t)((L->col[e] / k) << 8 | (L->col[e] % k)), {L->num[e], L->den ? L->den[e] : 1}});
@@ -2458,18 +2422,17 @@ static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
     }
     for (uint32_t i = 0; i < P->m; ++i)
         for (uint32_t e = P->rowptr[i]; e < P->rowptr[i + 1]; ++e) rows[2u * r + P->col[e]].push_back({(uint16_t)((i / n) << 8 | (i % n)), {P->num[e], P->den ? P->den[e] : 1}});
-    std::vector<int64_t> val, scale(3u * r, 1);
-    std::vector<uint16_t> pos;
-    std::vector<uint32_t> rp{0};
+    std::vector<int64_t> &val = I.val, &scale = I.scale;
+    std::vector<uint16_t> &pos = I.pos;
+    std::vector<uint32_t> &rp = I.rp;
+    scale.assign(3u * r, 1);
     const uint32_t inv_size[3] = {m, k, n};            // the factor of each part with an inverse: U^-1, V^-1, W^-T
     const uint32_t dir_size[3] = {k, n, m};            // and the direct one: V, W, U
     for (uint32_t g = 0; g < 3u * r; ++g) {
         if (modulus) {
             for (auto &e : rows[g]) {
-                const int64_t mo = (int64_t)modulus;
-                int64_t a = e.second.first % mo, d = e.second.second % mo; if (a < 0) a += mo;
-                if (gcd64(d, mo) != 1) return fail(PLO_E_UNSUPPORTED, "a denominator is not invertible modulo the modulus");
-                const uint64_t v = (uint64_t)a * inv_mod((uint32_t)d, (uint32_t)modulus) % modulus;
+                uint32_t v = 0;
+                if (!residue_of(e.second.first, e.second.second, (uint32_t)modulus, v)) return fail(PLO_E_UNSUPPORTED, "a denominator is not invertible modulo the modulus");
                 if (v) { pos.push_back(e.first); val.push_back((int64_t)v); }
             }
         } else {
@@ -2504,6 +2467,13 @@ static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
         }
         rp.push_back((uint32_t)val.size());
     }
+    return PLO_OK;
+}
+
+// 3: the LDS layout of the shared image and of a wave, the waves per workgroup, and the device side of the plan
+int orbit_plan_setup(const OrbitRows &I, uint32_t m, uint32_t k, uint32_t n, uint32_t r, uint64_t modulus, int measure, int action, uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan) {
+    const bool cse = measure == PLO_ORBIT_CSE, growth = measure == PLO_ORBIT_GROWTH;
+    const std::vector<int64_t> &val = I.val, &scale = I.scale; const std::vector<uint16_t> &pos = I.pos; const std::vector<uint32_t> &rp = I.rp;
     const uint32_t nnz = (uint32_t)val.size(), nrows = 3u * r, smax = std::max(m, std::max(k, n));
     plo_orbit_plan *pl = new plo_orbit_plan();
     plo::OrbitPlan &Q = pl->P;
@@ -2570,16 +2540,91 @@ static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_
     *plan = pl;
     return PLO_OK;
 }
+// the total order of the orbit search as a (hi, lo) word pair for sharded_search: (cost, nnz, nno), then the seed
+std::pair<unsigned long long, unsigned long long> orbit_key(const plo_orbit_best_t &pb, uint64_t seed0) { return {((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, pb.seed - seed0}; }
+
+// Body of plo_orbit_search and plo_orbit_growth_search.  launch(st) starts the search with pl->d_best as the job's best words and leaves N words per wave slot there, compared
+// in order, the last one the candidate (all ones in a slot that saw none); b gets the minimum.  The slots are cleared and launch() called again while it answers ORBIT_AGAIN
+// (a CSE plan that outgrew a table has other slots afterwards).
+template <size_t N, class Launch> int orbit_search_run(plo_orbit_plan *pl, const void *best, bool growth, uint64_t nseeds, plo_stats_t *stats, std::array<uint64_t, N> &b, Launch launch) {
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
+    if (!pl || !best) return fail(PLO_E_ARG, "null argument");
+    if (pl->growth != growth) return fail(PLO_E_ARG, growth ? "not a plan of plo_orbit_plan_create_growth" : "a growth plan: its cost is a double, plo_orbit_growth_search returns it");
+    if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
+    CallScope call(stats);
+    uint64_t slots;
+    int rc;
+    do {
+        slots = (uint64_t)pl->grid_max * pl->waves_per_wg;
+        HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, 8 * N * slots, g_stream));
+        rc = launch(call.st);
+    } while (rc == ORBIT_AGAIN);
+    if (rc != PLO_OK) return rc;
+    std::vector<uint64_t> w(N * slots);
+    HIPCHK(hipMemcpy(w.data(), pl->d_best, 8 * N * slots, hipMemcpyDeviceToHost));
+    b.fill(~0ull);
+    for (uint64_t s = 0; s < slots; ++s) {
+        std::array<uint64_t, N> c;
+        std::copy_n(w.begin() + N * s, N, c.begin());
+        if (c[N - 1] != ~0ull && c < b) b = c;
+    }
+    if (b[N - 1] == ~0ull) return fail(PLO_E_INTERNAL, "no candidate reported");
+    return call.done(PLO_OK);
+}
+} // namespace
+
+// the body of the create functions; sub > 0: a PLO_ORBIT_CSE plan
+static int orbit_plan_build(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan) {
+    uint32_t m = 0, k = 0, n = 0;
+    if (const int rc = orbit_admit(L, R, P, modulus, measure, action, plan, m, k, n)) return rc;
+    OrbitRows I;
+    if (const int rc = orbit_rows_image(L, R, P, m, k, n, modulus, action, measure == PLO_ORBIT_GROWTH, I)) return rc;
+    return orbit_plan_setup(I, m, k, n, L->m, modulus, measure, action, sub, cse_seed0, plan);
+}
 
 extern "C" {
 
+int plo_orbit_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, plo_orbit_plan_t **plan)
+{
+    return plo_orbit_plan_create_act(L, R, P, modulus, measure, PLO_ORBIT_ACT_TRIANGULAR, plan);
+}
+
+int plo_orbit_plan_create_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int measure, int action, plo_orbit_plan_t **plan)
+{
+    if (measure == PLO_ORBIT_CSE) return fail(PLO_E_ARG, "PLO_ORBIT_CSE needs sub and cse_seed0: plo_orbit_plan_create_cse");
+    // (the growth factor has its own create function; here the measure is refused with the words every unknown measure gets)
+    if (measure == PLO_ORBIT_GROWTH) return fail(PLO_E_ARG, !L || !R || !P || !plan ? "null argument" : "measure must be PLO_ORBIT_DENSITY or PLO_ORBIT_CANONICAL");
+    return orbit_plan_build(L, R, P, modulus, measure, action, 0, 0, plan);
+}
+
+int plo_orbit_plan_create_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int action, uint32_t sub, uint64_t cse_seed0, plo_orbit_plan_t **plan)
+{
+    if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
+    if (modulus == 0 || !(modulus & 1) || modulus >= (1ull << 31) || !is_prime32(modulus)) return fail(PLO_E_ARG, "the CSE measure needs an odd prime modulus below 2^31");
+    if (sub == 0 || sub > 65536u) return fail(PLO_E_ARG, "sub outside [1, 65536]");
+    return orbit_plan_build(L, R, P, modulus, PLO_ORBIT_CSE, action, sub, cse_seed0, plan);
+}
+
+int plo_orbit_plan_create_growth(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, int action, plo_orbit_plan_t **plan)
+{
+    if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
+    if (action == PLO_ORBIT_ACT_HOUSEHOLDER) return fail(PLO_E_ARG, "the Householder action is orthogonal and preserves the 2-norm growth factor: there is nothing to search");
+    return orbit_plan_build(L, R, P, 0, PLO_ORBIT_GROWTH, action, 0, 0, plan);
+}
+
+int plo_orbit_plan_info(plo_orbit_plan_t *pl, uint32_t out[8])
+{
+    if (!pl || !out) return fail(PLO_E_ARG, "null argument");
+    out[0] = pl->waves_per_wg; out[1] = pl->lds_bytes;
+    for (int i = 0; i < 3; ++i) out[2 + i] = pl->cse ? pl->C.W[i].cap : 0u;
+    out[5] = pl->cse ? std::max(pl->C.W[0].nnz, std::max(pl->C.W[1].nnz, pl->C.W[2].nnz)) : 0u;
+    out[6] = pl->cse_relaunches; out[7] = pl->cse ? pl->C.keep_full : 0u;
+    return PLO_OK;
+}
+
 void plo_orbit_plan_destroy(plo_orbit_plan_t *pl)
 {
-    if (!pl) return;
-    if (pl->d_img) (void)hipFree(pl->d_img);
-    if (pl->d_best) (void)hipFree(pl->d_best);
-    if (pl->d_err) (void)hipFree(pl->d_err);
-    delete pl;
+    if (pl) { dev_free(pl->d_img, pl->d_best, pl->d_err); delete pl; }
 }
 
 int plo_orbit_cost_many(plo_orbit_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *out3, plo_stats_t *stats)
@@ -2595,29 +2640,14 @@ int plo_orbit_cost_many(plo_orbit_plan_t *pl, const uint64_t *seeds, uint64_t se
 
 int plo_orbit_search(plo_orbit_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_orbit_best_t *best, plo_stats_t *stats)
 {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
-    if (!pl || !best) return fail(PLO_E_ARG, "null argument");
-    if (pl->growth) return fail(PLO_E_ARG, "a growth plan: its cost is a double, plo_orbit_growth_search returns it");
-    if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
-    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
-    uint64_t slots;
-    int rc;
-    do {                                                  // (a CSE plan that outgrew a table has other per-wave words afterwards)
-        slots = (uint64_t)pl->grid_max * pl->waves_per_wg;
-        HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, 16 * slots, g_stream));
+    std::array<uint64_t, 2> b;                            // ((cost, nnz, nno) key, candidate)
+    const int rc = orbit_search_run(pl, best, false, nseeds, stats, b, [&](plo_stats_t *st) {
         plo::OrbitJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.out3 = nullptr; J.best = pl->d_best;
-        rc = orbit_launch(pl, J, st);
-    } while (rc == ORBIT_AGAIN);
+        return orbit_launch(pl, J, st);
+    });
     if (rc != PLO_OK) return rc;
-    std::vector<uint64_t> w(2 * slots);
-    HIPCHK(hipMemcpy(w.data(), pl->d_best, 16 * slots, hipMemcpyDeviceToHost));
-    uint64_t bk = ~0ull, bi = ~0ull;
-    for (uint64_t s = 0; s < slots; ++s) if (w[2 * s + 1] != ~0ull && (w[2 * s] < bk || (w[2 * s] == bk && w[2 * s + 1] < bi))) { bk = w[2 * s]; bi = w[2 * s + 1]; }
-    if (bi == ~0ull) return fail(PLO_E_INTERNAL, "no candidate reported");
-    best->cost = (uint32_t)(bk >> 42); best->nnz = (uint32_t)(bk >> 21) & 0x1FFFFFu; best->nno = (uint32_t)bk & 0x1FFFFFu; best->reserved = 0;
-    best->seed = seed0 + bi;
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    best->cost = (uint32_t)(b[0] >> 42); best->nnz = (uint32_t)(b[0] >> 21) & 0x1FFFFFu; best->nno = (uint32_t)b[0] & 0x1FFFFFu; best->reserved = 0;
+    best->seed = seed0 + b[1];
     return PLO_OK;
 }
 
@@ -2633,7 +2663,7 @@ int plo_orbit_search_multi_act(const plo_qcsr_t *L, const plo_qcsr_t *R, const p
     if (!L || !R || !P || !best) return fail(PLO_E_ARG, "null argument");
     return sharded_search(seed0, nseeds, ndev, devices, best, stats,
         [&](plo_orbit_plan_t **plan) { return plo_orbit_plan_create_act(L, R, P, modulus, measure, action, plan); }, plo_orbit_search, plo_orbit_plan_destroy,
-        [&](const plo_orbit_best_t &pb) { return std::make_pair(((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, pb.seed - seed0); });   // (cost, nnz, nno), then seed
+        [&](const plo_orbit_best_t &pb) { return orbit_key(pb, seed0); });
 }
 
 int plo_orbit_search_multi_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint64_t modulus, int action, uint32_t sub, uint64_t cse_seed0,
@@ -2642,7 +2672,7 @@ int plo_orbit_search_multi_cse(const plo_qcsr_t *L, const plo_qcsr_t *R, const p
     if (!L || !R || !P || !best) return fail(PLO_E_ARG, "null argument");
     return sharded_search(seed0, nseeds, ndev, devices, best, stats,
         [&](plo_orbit_plan_t **plan) { return plo_orbit_plan_create_cse(L, R, P, modulus, action, sub, cse_seed0, plan); }, plo_orbit_search, plo_orbit_plan_destroy,
-        [&](const plo_orbit_best_t &pb) { return std::make_pair(((unsigned long long)pb.cost << 42) | ((unsigned long long)pb.nnz << 21) | pb.nno, pb.seed - seed0); });
+        [&](const plo_orbit_best_t &pb) { return orbit_key(pb, seed0); });
 }
 
 int plo_orbit_growth_many(plo_orbit_plan_t *pl, const uint64_t *seeds, uint64_t seed0, uint64_t n, double *cost, uint32_t *nnz_nno, plo_stats_t *stats)
@@ -2661,28 +2691,14 @@ int plo_orbit_growth_many(plo_orbit_plan_t *pl, const uint64_t *seeds, uint64_t 
 
 int plo_orbit_growth_search(plo_orbit_plan_t *pl, uint64_t seed0, uint64_t nseeds, plo_orbit_gbest_t *best, plo_stats_t *stats)
 {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
-    if (!pl || !best) return fail(PLO_E_ARG, "null argument");
-    if (!pl->growth) return fail(PLO_E_ARG, "not a plan of plo_orbit_plan_create_growth");
-    if (nseeds == 0 || nseeds >= (1ull << 31)) return fail(PLO_E_ARG, "1 .. 2^31-1 candidates per call");
-    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t slots = (uint64_t)pl->grid_max * pl->waves_per_wg;
-    HIPCHK(hipMemsetAsync(pl->d_best, 0xFF, 24 * slots, g_stream));
-    plo::OrbitGrowthJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.cost = nullptr; J.cnt2 = nullptr; J.best = pl->d_best;
-    const int rc = orbit_growth_launch(pl, J, st);
+    std::array<uint64_t, 3> b;                            // (bits of the cost, nnz << 21 | nno, candidate): the lexicographic minimum
+    const int rc = orbit_search_run(pl, best, true, nseeds, stats, b, [&](plo_stats_t *st) {
+        plo::OrbitGrowthJob J{}; J.seed0 = seed0; J.seeds = nullptr; J.ncand = nseeds; J.cost = nullptr; J.cnt2 = nullptr; J.best = pl->d_best;
+        return orbit_growth_launch(pl, J, st);
+    });
     if (rc != PLO_OK) return rc;
-    std::vector<uint64_t> w(3 * slots);
-    HIPCHK(hipMemcpy(w.data(), pl->d_best, 24 * slots, hipMemcpyDeviceToHost));
-    std::array<uint64_t, 3> b{~0ull, ~0ull, ~0ull};       // (bits of the cost, nnz << 21 | nno, candidate): the lexicographic minimum
-    for (uint64_t s = 0; s < slots; ++s) {
-        const std::array<uint64_t, 3> c{w[3 * s], w[3 * s + 1], w[3 * s + 2]};
-        if (c[2] != ~0ull && c < b) b = c;
-    }
-    if (b[2] == ~0ull) return fail(PLO_E_INTERNAL, "no candidate reported");
     memcpy(&best->cost, &b[0], 8); best->nnz = (uint32_t)(b[1] >> 21) & 0x1FFFFFu; best->nno = (uint32_t)b[1] & 0x1FFFFFu;
     best->seed = seed0 + b[2];
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return PLO_OK;
 }
 
@@ -2708,15 +2724,6 @@ struct plo_dep_plan {
 
 namespace {
 #define PLO_DEP_MAX_HITS (1ull << 24)
-// the residue of num/den modulo p, false when den is no unit
-bool dep_residue(int64_t num, int64_t den, uint32_t p, uint32_t &out) {
-    int64_t d = den % (int64_t)p, a = num % (int64_t)p;
-    if (d < 0) d += p;
-    if (a < 0) a += p;
-    if (gcd64(d, p) != 1) return false;
-    out = (uint32_t)((uint64_t)a * inv_mod((uint32_t)d, p) % p);
-    return true;
-}
 // the reference's order: by top row, then (q1, v1), (q2, v2), ..., a prefix before its extensions
 bool dep_before(const plo_dep_hit_t &a, const plo_dep_hit_t &b) {
     if (a.rows[0] != b.rows[0]) return a.rows[0] < b.rows[0];
@@ -2729,10 +2736,9 @@ bool dep_before(const plo_dep_hit_t &a, const plo_dep_hit_t &b) {
 } // namespace
 
 extern "C" {
-
 int plo_dep_plan_create_q(const plo_qcsr_t *M, const int64_t *cnum, const int64_t *cden, uint32_t ncoef, uint64_t modulus, uint32_t level, plo_dep_plan_t **plan)
 {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
     if (!M || !plan || (ncoef && (!cnum || !cden))) return fail(PLO_E_ARG, "null argument");
     if (modulus == 1) return fail(PLO_E_ARG, "modulus 1");
     if (level == 0 || ncoef == 0) return fail(PLO_E_ARG, "level and the number of coefficients must be positive");
@@ -2747,9 +2753,9 @@ int plo_dep_plan_create_q(const plo_qcsr_t *M, const int64_t *cnum, const int64_
     std::vector<uint32_t> dense((size_t)m * ld, 0u), coef(ncoef);
     for (uint32_t i = 0; i < m; ++i)
         for (uint32_t e = M->rowptr[i]; e < M->rowptr[i + 1]; ++e)
-            if (!dep_residue(M->num[e], M->den ? M->den[e] : 1, p, dense[(size_t)i * ld + M->col[e]])) return fail(PLO_E_UNSUPPORTED, "a denominator of the matrix is no unit modulo " + std::to_string(p));
+            if (!residue_of(M->num[e], M->den ? M->den[e] : 1, p, dense[(size_t)i * ld + M->col[e]])) return fail(PLO_E_UNSUPPORTED, "a denominator of the matrix is no unit modulo " + std::to_string(p));
     for (uint32_t v = 0; v < ncoef; ++v)
-        if (!dep_residue(cnum[v], cden[v], p, coef[v])) return fail(PLO_E_UNSUPPORTED, "a denominator of a coefficient is no unit modulo " + std::to_string(p));
+        if (!residue_of(cnum[v], cden[v], p, coef[v])) return fail(PLO_E_UNSUPPORTED, "a denominator of a coefficient is no unit modulo " + std::to_string(p));
     plo_dep_plan *pl = new plo_dep_plan();
     plo::DepPlan &Q = pl->P;
     pl->level = level;
@@ -2784,33 +2790,28 @@ int plo_dep_plan_create_q(const plo_qcsr_t *M, const int64_t *cnum, const int64_
 
 void plo_dep_plan_destroy(plo_dep_plan_t *pl)
 {
-    if (!pl) return;
-    if (pl->d_img) (void)hipFree(pl->d_img);
-    if (pl->d_ctr) (void)hipFree(pl->d_ctr);
-    delete pl;
+    if (pl) { dev_free(pl->d_img, pl->d_ctr); delete pl; }
 }
 
 int plo_dep_search(plo_dep_plan_t *pl, uint32_t row0, uint32_t row1, plo_dep_hit_t *hits, uint64_t cap, uint64_t *nhits, plo_stats_t *stats)
 {
-    if (g_device < 0) return fail(PLO_E_HIP, "plo_init was not called (or found no HIP device)");
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
     if (!pl || !nhits || (cap && !hits)) return fail(PLO_E_ARG, "null argument");
     if (row0 > row1 || row1 > pl->P.m) return fail(PLO_E_ARG, "top rows out of range");
-    plo_stats_t local{}; plo_stats_t *st = stats ? stats : &local; *st = plo_stats_t{};
-    const auto t0 = std::chrono::steady_clock::now();
+    CallScope call(stats); plo_stats_t *st = call.st;
     *nhits = 0;
     const uint32_t m = pl->P.m, C = pl->P.C, nrows = row1 - row0;
     std::vector<uint64_t> toff(nrows + 1u, 0);
     for (uint32_t r = 0; r < nrows; ++r) toff[r + 1u] = toff[r] + (uint64_t)(m - 1u - (row0 + r)) * C;
     const uint64_t ntasks = toff[nrows];
-    if (pl->level < 2u || ntasks == 0) return PLO_OK;
+    if (pl->level < 2u || ntasks == 0) return PLO_OK;           // (`seconds` stays 0)
     const uint64_t dcap = std::min<uint64_t>(cap, PLO_DEP_MAX_HITS);
     DevBuf<uint64_t> d_toff; DevBuf<plo_dep_hit_t> d_hits;
     if (hipMalloc((void **)&d_toff.p, 8ull * (nrows + 1u)) != hipSuccess || hipMemcpy(d_toff, toff.data(), 8ull * (nrows + 1u), hipMemcpyHostToDevice) != hipSuccess ||
         hipMalloc((void **)&d_hits.p, std::max<uint64_t>(1, dcap) * sizeof(plo_dep_hit_t)) != hipSuccess ||
         hipMemsetAsync(pl->d_ctr, 0, 16, g_stream) != hipSuccess) return fail(PLO_E_HIP, "device buffers of the dependency search");
     plo::DepJob J{}; J.row0 = row0; J.nrows = nrows; J.toff = d_toff; J.ntasks = ntasks; J.next = pl->d_ctr; J.count = pl->d_ctr + 1; J.hits = d_hits; J.cap = dcap;
-    const uint64_t need = (ntasks + pl->waves_per_wg - 1) / pl->waves_per_wg;
-    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(pl->grid_max, need));
+    const uint64_t grid = grid_for(ntasks, pl->waves_per_wg, pl->grid_max);
     int rc = timed_launch(pl, grid, ntasks, st, [&] {
         if (pl->m_in_lds) hipLaunchKernelGGL((plo::dep_kernel<true>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
         else hipLaunchKernelGGL((plo::dep_kernel<false>), dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
@@ -2825,8 +2826,6 @@ int plo_dep_search(plo_dep_plan_t *pl, uint32_t row0, uint32_t row1, plo_dep_hit
         else if (found > cap) rc = fail(PLO_E_CAPACITY, std::to_string(found) + " hits for a buffer of " + std::to_string(cap));
         else std::sort(hits, hits + found, dep_before);
     }
-    st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    return call.done(rc);
 }
-
 } // extern "C"
