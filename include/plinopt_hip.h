@@ -182,6 +182,21 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
  * plo_cse_chain_batch. */
 int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t nrestarts, uint32_t per_block, int cost_mode,
                       uint32_t *adds, uint32_t *muls, uint32_t *info, plo_best_t *best, plo_stats_t *stats);
+/* The kernel method over PRESCRIBED row orders (bin/optimizer -N; replaces the loop body of AllKernelOpt, include/plinopt_optimize.inl:
+ * 1357-1418, which decomposes M once for every order of its rows).  Order index pi (first <= pi < first + count) is the pi-th
+ * permutation of 0..m-1 in lexicographic order: that of std::next_permutation from the identity, and of the reference's factoradic
+ * kthpermutation (include/plinopt_library.inl:289-304).  Candidate c (0 <= c < count*sub) is restart j = c % sub of order
+ * pi = first + c / sub: the decomposition in that order with NotIndep the FIRST draw of the stream of seed0 + pi (no shuffle; restated
+ * in oracle/plo_oracle.c plo_oracle_kernel_order), then Optimizer() on Free and on Dep from the stream of seed0 + pi*sub + j.  Both seeds
+ * depend on pi only, not on first: the results of ranges compose, and a walk of all m! orders may be split into calls, processes or
+ * machines at will.  adds/muls (count*sub entries), info (3 per candidate: rank, NotIndep, dependent rows computed through Dep) and best
+ * may each be NULL.  best is the minimum under (cost key of cost_mode, candidate index), the smaller index winning ties; best->seed holds
+ * the winner's seed0 + pi*sub + j, so pi = (best->seed - seed0) / sub and j = (best->seed - seed0) % sub.  With PLO_COST_SUM best->adds
+ * holds the sum and best->muls 0.  The call runs in launches of at most 2^25 candidates; stats->candidates, kernel_ms and launches are
+ * sums over them.  PLO_E_ARG: fewer than 2 or more than 12 rows, count == 0, sub == 0, first + count > m!.  Otherwise the limits and
+ * codes of plo_kernel_search (PLO_E_UNSUPPORTED: a kernel of dimension zero, a zero matrix, more than 64 columns). */
+int plo_kernel_search_orders(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t first, uint64_t count, uint32_t sub, int cost_mode,
+                             uint32_t *adds, uint32_t *muls, uint32_t *info, plo_best_t *best, plo_stats_t *stats);
 /* The restart loop of KernelOptimiser (include/plinopt_optimize.inl:1299-1340) over `ndev` devices from one process: contiguous
  * shards of the restart range, one host thread and one device each, minimum under (cmpOpCount key, seed) by the RCCL MIN
  * all-reduces of plo_cse_search_multi (same conventions for devices, stats->reduce and PLO_MULTI_REDUCE).  per_block must be 1

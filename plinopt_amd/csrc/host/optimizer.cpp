@@ -2,7 +2,7 @@
 // bin/optimizer -- front-end keeping the reference CLI contract of
 // src/optimizer.cpp:150-228: flags -D -K -G -A -F -E -N -P -M -q # -v # -O #,
 // SLP on stdout only (:87), `#`-prefixed statistics on stderr (:89-98).
-// New flags (the reference has none): --gpu N (0 = host only), --seed S.
+// New flags (the reference has none): --gpu N (0 = host only), --seed S, --orders first:count (a range of -N's row orders).
 //
 // With -q p the restart loop of CSEOptimiser (include/plinopt_optimize.inl:
 // 1204-1238) runs on the GPU through the C-ABI of libplinopt_hip.so
@@ -36,6 +36,7 @@ struct HipLib {
     PLO_SYM(chain_batch, plo_cse_chain_batch);
     PLO_SYM_OPT(kernel_search, plo_kernel_search);   // optional: -K with the decompositions on the device
     PLO_SYM_OPT(kernel_search_multi, plo_kernel_search_multi);   // optional: the same over N devices from this process
+    PLO_SYM_OPT(kernel_search_orders, plo_kernel_search_orders);   // optional: -N over 10 to 12 rows, or over a range of orders
     explicit HipLib(void *lib = nullptr) : h(lib), ok(lib != nullptr) {}   // empty until load(): the methods load it only when they use the GPU
     bool load() { *this = HipLib(open_hip_lib()); if (!h) ++g_failures; return ok; }
 };
@@ -359,13 +360,95 @@ template <class F> bool kernel_method(const F &f, const SparseMat<typename F::El
     return true;
 }
 
-// AllKernelOpt (-N, :1357-1418): every order of the rows (m <= 9 here: m! eliminations on the host; the reference allows 12).
-// Orders that give the same decomposition (same computed rows, same combinations) are searched once; the restarts are
-// shared out between the distinct decompositions.
+// --orders first:count: -N over that range of order indices only (a walk of 12! split over processes and machines; a bounded run)
+struct { bool set = false; uint64_t first = 0, count = 0; } g_orders;
+inline uint64_t factorial(size_t m) { uint64_t r = 1; for (size_t k = 2; k <= m; ++k) r *= k; return r; }
+// the pi-th permutation of 0..m-1 in lexicographic order: the order std::next_permutation reaches after pi steps from the
+// identity, by the digits of pi in the factorial base (kthpermutation, include/plinopt_library.inl:289-304)
+inline std::vector<size_t> kth_order(size_t m, uint64_t pi) {
+    std::vector<size_t> left(m), ord;
+    for (size_t i = 0; i < m; ++i) left[i] = i;
+    for (size_t i = 0; i < m; ++i) {
+        const uint64_t fc = factorial(m - 1 - i); const size_t d = (size_t)(pi / fc); pi %= fc;
+        ord.push_back(left[d]); left.erase(left.begin() + (long)d);
+    }
+    return ord;
+}
+
+// AllKernelOpt (-N, :1357-1418) by order INDEX, for 10 to 12 rows (up to 12! = 479,001,600 orders, as the reference allows) and
+// for a range of orders (--orders): candidate c = (pi - first) * sub + j is restart j of order pi, the pi-th permutation of the
+// rows; its decomposition draws NotIndep from the stream of seed0 + pi, its two Optimizer calls run from seed0 + pi * sub + j.
+// No order is searched twice as below, but none is left out either: 12! signatures do not fit a map.  The minimum is under
+// (cmpOpCount, candidate index).  On the device the whole walk is plo_kernel_search_orders; on the host (--gpu 0, the
+// rationals, a modulus above 2^31, a refusal of the device) the same definition over the threads.
+template <class F> bool allorders_method(const F &f, const SparseMat<typename F::Elt> &lM, uint64_t seed0, size_t loops, int gpu, uint32_t q,
+                                         int verbose, Ops &gops, std::string &gtext) {
+    const size_t m = lM.rowdim();
+    const uint64_t mfact = factorial(m), first = g_orders.set ? g_orders.first : 0, count = g_orders.set ? g_orders.count : mfact;
+    const uint64_t sub = std::min<uint64_t>(std::max<uint64_t>(1, loops / mfact), 0xFFFFFFFFull);
+    Ops best; uint64_t seed = 0; bool have = false, on_gpu = false; double kms = 0;
+    if constexpr (std::is_same<F, ZpField>::value) if (q != 0 && gpu > 0) {
+        HipLib L;
+        if (!L.load() || L.init(0) != PLO_OK) { ++g_failures, std::cerr << "# \033[1;31mERROR: -N: cannot use the GPU: " << (L.last_error ? L.last_error() : "library missing") << "\033[0m" << std::endl; return false; }
+        if (!L.kernel_search_orders) { ++g_failures, std::cerr << "# \033[1;31mERROR: -N: libplinopt_hip.so lacks plo_kernel_search_orders\033[0m" << std::endl; return false; }
+        std::vector<uint32_t> rp, cc, vv; to_csr(lM, rp, cc, vv);
+        plo_csr_t A{(uint32_t)m, (uint32_t)lM.coldim(), rp.data(), cc.data(), vv.data()};
+        plo_best_t b{}; plo_stats_t st{};
+        const int rc = L.kernel_search_orders(&A, q, seed0, first, count, (uint32_t)sub, PLO_COST_SUM_THEN_ADD, nullptr, nullptr, nullptr, &b, &st);
+        if (rc == PLO_OK) { best = {b.adds, b.muls}; seed = b.seed; have = true; on_gpu = true; kms = st.kernel_ms; }
+        else if (rc == PLO_E_UNSUPPORTED || rc == PLO_E_CAPACITY) std::clog << "# -N on the GPU refused (" << L.last_error() << "): host walk" << std::endl;
+        else { ++g_failures; std::cerr << "# \033[1;31mERROR: -N on the GPU: " << L.last_error() << "\033[0m" << std::endl; return false; }
+    }
+    if (!have) {
+        bool zero = false; uint64_t bcand = 0;
+#pragma omp parallel
+        {
+            Ops tb; uint64_t tc = 0; bool th = false;                   // of this thread
+#pragma omp for schedule(dynamic, 16) nowait
+            for (long long k = 0; k < (long long)count; ++k) {
+                const uint64_t pi = first + (uint64_t)k;
+                KernelDecomp<F> kd; CandRng rng(seed0 + pi);
+                if (!kernel_decomp_order(f, lM, kth_order(m, pi), rng, kd)) {
+#pragma omp atomic write
+                    zero = true;
+                    continue;
+                }
+                for (uint64_t j = 0; j < sub; ++j) {
+                    Ops ops; (void)kernel_text(f, kd, seed0 + pi * sub + j, ops);
+                    const uint64_t c = (uint64_t)k * sub + j;
+                    if (!th || cmp_op_count(ops, tb) || (!cmp_op_count(tb, ops) && c < tc)) { tb = ops; tc = c; th = true; }
+                }
+            }
+#pragma omp critical
+            if (th && (!have || cmp_op_count(tb, best) || (!cmp_op_count(best, tb) && tc < bcand))) { best = tb; bcand = tc; have = true; }
+        }
+        if (zero) { std::clog << "# \033[1;36mZero dimensional kernel.\033[0m" << std::endl; return false; }
+        seed = seed0 + first * sub + bcand;
+    }
+    if (!have) return false;
+    const uint64_t bpi = (seed - seed0) / sub;
+    KernelDecomp<F> kd; CandRng rng(seed0 + bpi);
+    if (!kernel_decomp_order(f, lM, kth_order(m, bpi), rng, kd)) return false;
+    Ops rops; std::string t = kernel_text(f, kd, seed, rops);
+    if (rops != best) { ++g_failures, std::cerr << "# \033[1;31mERROR: -N replay gives " << rops.first << '|' << rops.second << ", search said " << best.first << '|' << best.second << "\033[0m" << std::endl; return false; }
+    if (verbose > 0) {
+        std::clog << "# Found N: " << best.first << '|' << best.second << " instead of " << gops.first << '|' << gops.second << "\t[order " << bpi << ", seed " << seed << "] ("
+                  << count << " of " << mfact << " row orders from " << first << ", " << sub << " restarts each, ";
+        if (on_gpu) std::clog << "GPU kernel " << kms << " ms)" << std::endl; else std::clog << "host)" << std::endl;
+    }
+    if (cmp_op_count(best, gops)) { gops = best; gtext = t; }
+    else std::clog << "# \033[1;36mNo kernel permutation has less additions.\033[0m" << std::endl;        // :1409-1413
+    return true;
+}
+
+// AllKernelOpt (-N, :1357-1418): every order of the rows.  Up to 9 rows: m! eliminations on the host; orders that give the same
+// decomposition (same computed rows, same combinations) are searched once; the restarts are shared out between the distinct
+// decompositions.  10 to 12 rows, and --orders: allorders_method above.  13 rows and more: nothing, as in the reference (:1463).
 template <class F> bool allkernels_method(const F &f, const SparseMat<typename F::Elt> &lM, uint64_t seed0, size_t loops, int gpu, uint32_t q,
                                           int verbose, Ops &gops, std::string &gtext) {
     const size_t m = lM.rowdim();
-    if (m > 9) { std::clog << "# -N skipped: " << m << "! row orders (this build walks up to 9!)" << std::endl; return false; }
+    if (m > 12) { std::clog << "# -N skipped: " << m << " rows (the row orders are walked up to 12!, as in the reference)" << std::endl; return false; }
+    if (m > 9 || g_orders.set) return allorders_method(f, lM, seed0, loops, gpu, q, verbose, gops, gtext);
     std::vector<size_t> ord(m);
     for (size_t i = 0; i < m; ++i) ord[i] = i;
     std::map<std::vector<size_t>, std::pair<std::vector<size_t>, uint64_t>> distinct;     // signature -> (order, permutation index)
@@ -778,7 +861,7 @@ int main(int argc, char **argv)
     for (int i = 1; i < argc; ++i) {
         std::string a(argv[i]);
         if (a == "-h") {
-            std::clog << "Usage: " << argv[0] << " [-h|-M|-P|-K|-D|-G|-E|-N|-A|-q #|-O #|--gpu #|--seed #] [stdin|matrixfile.sms]\n"
+            std::clog << "Usage: " << argv[0] << " [-h|-M|-P|-K|-D|-G|-E|-N|-A|-q #|-O #|--gpu #|--seed #|--orders #:#] [stdin|matrixfile.sms]\n"
                       << "  -D/-K/-G: direct/kernel/LU methods (default is all)\n"
                       << "  -F: kernel method with the identity added to its goals (inputs may join the row basis)\n"
                       << "  -q #: search modulo (default is Rationals, on the host)\n"
@@ -789,6 +872,10 @@ int main(int argc, char **argv)
                       << "  -E: also walk the exhaustive tree of greedy CSE schedules (bounded by max(-O, 2^22) schedules; every DISTINCT triple of\n"
                       << "      frequency > 1 is a child, once -- the reference tries it once per row holding it); best by additions then multiplications\n"
                       << "      of the printed program, or with --recsub by RecSub's own counts (multiplications before ProgramGen)\n"
+                      << "  -N: also walk the kernel method over EVERY order of the rows, up to 12 rows (12! orders).  Up to 9 rows equal decompositions are searched once and share\n"
+                      << "      the -O restarts; 10 to 12 rows walk all m! orders by index with max(1, -O / m!) restarts each, on the GPU with -q below 2^31 and --gpu >= 1\n"
+                      << "  --orders first:count: with -N, only the row orders of index first .. first+count-1 (lexicographic order of the permutations): splits a\n"
+                      << "      walk over processes and machines; results of ranges compose (seeds depend on the order index only)\n"
                       << "  --only D|K|G|A|E|N: run exactly that method\n"
                       << "  --host-decomp: -K makes the nullspace decompositions on the host (default: on the device when the matrix has at most 64 rows and columns)\n"
                       << "  --kernel-block #: restarts per nullspace decomposition of -K (default 1: one decomposition per restart, as the reference)\n"
@@ -814,6 +901,13 @@ int main(int argc, char **argv)
         else if (a == "--fork-shards") g_fork_shards = true;
         else if (a == "--kernel-block" && i + 1 < argc) g_kernel_block = std::max<uint64_t>(1, strtoull(argv[++i], nullptr, 10));
         else if (a == "--recsub") g_recsub_order = true;
+        else if (a == "--orders" && i + 1 < argc) {
+            const std::string v(argv[++i]); const size_t colon = v.find(':');
+            const bool ok = colon != std::string::npos && colon > 0 && colon + 1 < v.size() && v.find_first_not_of("0123456789:") == std::string::npos && v.find(':', colon + 1) == std::string::npos
+                            && colon <= 18 && v.size() - colon - 1 <= 18;
+            if (!ok) { std::cerr << "# ERROR: --orders takes first:count, two natural numbers" << std::endl; return -1; }
+            g_orders.set = true; g_orders.first = strtoull(v.c_str(), nullptr, 10); g_orders.count = strtoull(v.c_str() + colon + 1, nullptr, 10);
+        }
         else if (a == "--only" && i + 1 < argc) { only = argv[++i]; }   // run exactly one method (D, G or A): for tests and timing
         else filename = a;
     }
@@ -824,6 +918,14 @@ int main(int argc, char **argv)
         QMat MQ;
         if (filename.empty()) MQ = read_sms(std::cin);
         else { std::ifstream in(filename); if (!in) return -1; MQ = read_sms(in); }
+        if (g_orders.set) {
+            const size_t m = MQ.rowdim();
+            if (!allkernels) { std::cerr << "# ERROR: --orders is a range of the row orders of -N (--only N)" << std::endl; return -1; }
+            if (m < 2 || m > 12) { std::cerr << "# ERROR: --orders: the row orders are walked for 2 to 12 rows, the matrix has " << m << std::endl; return -1; }
+            if (g_orders.count == 0 || g_orders.first >= factorial(m) || g_orders.count > factorial(m) - g_orders.first) {
+                std::cerr << "# ERROR: --orders " << g_orders.first << ':' << g_orders.count << " is no range of the " << factorial(m) << " orders of " << m << " rows" << std::endl; return -1;
+            }
+        }
         if (printPretty || printMaple) {                                             // src/optimizer.cpp:65-73 (LinBox's writers are not in the tree: plain dense forms)
             auto dense = [&](const char *open, const char *rowopen, const char *sep, const char *rowclose, const char *rowsep, const char *close) {
                 std::clog << open;

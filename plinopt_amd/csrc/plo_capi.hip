@@ -1590,7 +1590,9 @@ uint32_t kmethod_scratch_layout(plo::KPlan &K, uint32_t depc_bytes, bool depc_in
 }
 
 // The sizing launch: Dep's pair count and entries, maxima over a sample of the decompositions
-int kmethod_sample(plo::KPlan &K, uint64_t seed0, uint64_t nrestarts, uint32_t vc_end, uint32_t depc_bytes, bool depc_inside, plo_stats_t *st, uint32_t *pairs_max, uint32_t *ent_max) {
+// (ord: the walk over prescribed row orders -- the sample is `norders` orders at equal distances over the whole range of the call)
+int kmethod_sample(plo::KPlan &K, uint64_t seed0, uint64_t nrestarts, uint32_t vc_end, uint32_t depc_bytes, bool depc_inside, plo_stats_t *st, uint32_t *pairs_max, uint32_t *ent_max,
+                   const plo::KOrd *ord = nullptr, uint64_t norders = 0) {
     K.region = round_up(std::max(K.PM.region_bytes, vc_end), 16);
     if (depc_inside) { const uint32_t at = K.region; K.region = at + depc_bytes; K.off_depc = -(int32_t)depc_bytes; }
     uint32_t lds = 0;
@@ -1599,10 +1601,14 @@ int kmethod_sample(plo::KPlan &K, uint64_t seed0, uint64_t nrestarts, uint32_t v
     DevBuf<uint32_t> d_sz, d_err;
     HIPCHK(hipMalloc((void **)&d_err.p, 4)); HIPCHK(hipMemsetAsync(d_err, 0, 4, g_stream));
     HIPCHK(hipMalloc((void **)&d_sz.p, 16)); HIPCHK(hipMemsetAsync(d_sz, 0, 16, g_stream));
-    HIPCHK(hipFuncSetAttribute((const void *)plo::kmethod_size_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    plo::WaveJob J{}; J.seed0 = seed0; J.ncand = std::min<uint64_t>(nrestarts, 4096); J.err = d_err;
+    HIPCHK(hipFuncSetAttribute(ord ? (const void *)plo::kmethod_size_orders_kernel : (const void *)plo::kmethod_size_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    plo::WaveJob J{}; J.seed0 = seed0; J.ncand = std::min<uint64_t>(ord ? norders : nrestarts, 4096); J.err = d_err;
     const uint64_t grid = grid_for(J.ncand, W, (uint64_t)g_cus * 2u);
-    const int trc = timed_launch(st, nullptr, [&] { hipLaunchKernelGGL(plo::kmethod_size_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, d_sz.p); });
+    plo::KOrd O{}; if (ord) { O = *ord; O.step_num = norders; O.step_den = J.ncand; }
+    const int trc = timed_launch(st, nullptr, [&] {
+        if (ord) hipLaunchKernelGGL(plo::kmethod_size_orders_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, O, d_sz.p);
+        else hipLaunchKernelGGL(plo::kmethod_size_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, d_sz.p);
+    });
     if (trc != PLO_OK) return trc;
     uint32_t sz[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpy(sz, d_sz, 16, hipMemcpyDeviceToHost));
@@ -1635,18 +1641,17 @@ int kmethod_dep_layout(plo::KPlan &K, const KmKnobs &knobs, uint32_t cap_scale, 
     }
     return PLO_OK;
 }
-} // namespace
 
-int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t nrestarts, uint32_t per_block, int cost_mode,
-                      uint32_t *adds, uint32_t *muls, uint32_t *info, plo_best_t *best, plo_stats_t *st)
+// The walk over prescribed row orders (plo_kernel_search_orders): orders first .. first + count - 1, `sub` restarts each
+struct KOrdReq { uint64_t first, count; uint32_t sub; };
+
+// Body of plo_kernel_search (ord == nullptr: `total` restarts of random orders) and of plo_kernel_search_orders (total = count * sub
+// candidates), arguments checked.  The candidates go to the device in launches of at most `chunk`; the minimum is carried over the
+// launches on the host, the earlier launch winning ties; a launch that reports a full table is repeated with twice the slots, and
+// the launches after it keep the larger tables.
+int kernel_search_run(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t total, uint64_t chunk, uint32_t per_block, int cost_mode,
+                      uint32_t *adds, uint32_t *muls, uint32_t *info, plo_best_t *best, plo_stats_t *st, const KOrdReq *ord)
 {
-    if (!M || nrestarts == 0 || per_block == 0) return fail(PLO_E_ARG, "bad argument");
-    if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
-    if (const int rc = require_device(NOINIT_CSE)) return rc;
-    if (p < 3 || p >= 0x80000000u || !(p & 1u)) return fail(PLO_E_ARG, "modulus must be an odd prime below 2^31");
-    if (const char *bad = csr_defect(M, p)) return fail(PLO_E_ARG, bad);
-    if (M->m == 0 || M->m > 128 || M->n == 0 || M->n > 64) return fail(PLO_E_UNSUPPORTED, "device decomposition needs at most 128 rows and 64 columns");
-    if (nrestarts > 0xFFFFFFFFull) return fail(PLO_E_ARG, "at most 2^32-1 restarts per call");
     CallScope call(st); st = call.st;
     if (best) { best->adds = best->muls = 0xFFFFFFFFu; best->seed = ~0ull; }
     const uint32_t m = M->m, n = M->n, R = rank_mod_p(M, p), ndeps = m - R;
@@ -1658,11 +1663,15 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
     const uint32_t depc_bytes = round_up(ndeps * R * 4u, 16);
     const bool depc_inside = !knobs.depc_scratch;
     uint32_t pairs_max = 0, ent_max = 0;
+    plo::KOrd O{};
+    if (ord) { O.seed0 = seed0; O.first = ord->first; O.sub = ord->sub; O.fact[0] = 1u; for (uint32_t k = 1; k < 12u; ++k) O.fact[k] = O.fact[k - 1u] * k; }
+    const uint64_t cseed0 = ord ? seed0 + ord->first * ord->sub : seed0;      // seed of candidate 0 of the call
+    uint64_t done = 0;
     // Dep's table starts at 0.75 x the sampled PAIR count (an upper bound of its distinct triples, usually far above it): a
     // smaller image means more resident waves; a full table is reported by the device and the launch repeated with twice the slots
     for (uint32_t cap_scale = 1; cap_scale <= 32; cap_scale *= 2) {
         plo::KPlan K{};
-        DevBuf<uint8_t> d_img; DevBuf<uint32_t> d_info;      // of this attempt
+        DevBuf<uint8_t> d_img;      // of this attempt
         // plan and image of M (the layout of Free)
         plo_plan tmp; tmp.cap_scale = std::max(2u, cap_scale);
         set_matrix(&tmp, M, p);
@@ -1675,7 +1684,7 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
         HIPCHK(hipMalloc((void **)&d_img.p, img.size() + 64)); HIPCHK(hipMemcpy(d_img, img.data(), img.size(), hipMemcpyHostToDevice));
         K.PM.tmpl = (const uint64_t *)d_img.p;
         if (cap_scale == 1) {
-            if ((rc = kmethod_sample(K, seed0, nrestarts, vc_end, depc_bytes, depc_inside, st, &pairs_max, &ent_max)) != PLO_OK) return rc;
+            if ((rc = kmethod_sample(K, seed0, total, vc_end, depc_bytes, depc_inside, st, &pairs_max, &ent_max, ord ? &O : nullptr, ord ? ord->count : 0)) != PLO_OK) return rc;
             if (knobs.pairs_div) pairs_max /= (uint32_t)std::max(1l, *knobs.pairs_div);   // test knob: undersized first table, exercises the repeat-with-more-slots path
         }
         if ((rc = kmethod_dep_layout(K, knobs, cap_scale, pairs_max, ent_max, vc_end, depc_bytes, depc_inside)) != PLO_OK) return rc;
@@ -1684,15 +1693,31 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
         if (!W) return fail(PLO_E_CAPACITY, "kernel-method state does not fit LDS");
         if (knobs.debug) fprintf(stderr, "# kernel method layout: region of M %u B (table %u slots), of Dep %u B (table %u slots, sampled pairs %u, entries %u of at most %u), elimination arrays end at %u B, scratch %u B; %u waves per workgroup, %u B of LDS, %u waves per CU\n",
                                  K.PM.region_bytes, K.PM.cap, K.PD.region_bytes, K.PD.cap, pairs_max, K.PD.nnz, ndeps * R, vc_end, K.scratch_bytes, W, lds, bestw);
-        if (info) HIPCHK(hipMalloc((void **)&d_info.p, nrestarts * 12));
-        const plo::KInfo I{d_info.p};
+        const void *fn = ord ? (K.PM.unit ? (const void *)plo::kmethod_orders_kernel<true> : (const void *)plo::kmethod_orders_kernel<false>)
+                             : (K.PM.unit ? (const void *)plo::kmethod_kernel<true> : (const void *)plo::kmethod_kernel<false>);
         bool again = false;
-        rc = one_shot_search(K.PM.unit ? (const void *)plo::kmethod_kernel<true> : (const void *)plo::kmethod_kernel<false>, W, lds, seed0, nrestarts, cost_mode, adds, muls, best, st, &again,
-                             [&](uint64_t grid, const plo::WaveJob &J) {
-            if (K.PM.unit) hipLaunchKernelGGL(plo::kmethod_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I);
-            else hipLaunchKernelGGL(plo::kmethod_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I);
-        });
-        if (rc != PLO_OK) return rc;
+        while (done < total && !again) {                                         // the launches at this table size
+            const uint64_t cnt = std::min<uint64_t>(chunk, total - done);
+            DevBuf<uint32_t> d_info;
+            if (info) HIPCHK(hipMalloc((void **)&d_info.p, cnt * 12));
+            const plo::KInfo I{d_info.p};
+            O.cand0 = done;
+            plo_best_t cb{0xFFFFFFFFu, 0xFFFFFFFFu, ~0ull};
+            rc = one_shot_search(fn, W, lds, cseed0 + done, cnt, cost_mode, adds ? adds + done : nullptr, muls ? muls + done : nullptr, best ? &cb : nullptr, st, &again,
+                                 [&](uint64_t grid, const plo::WaveJob &J) {
+                if (ord) {
+                    if (K.PM.unit) hipLaunchKernelGGL(plo::kmethod_orders_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I, O);
+                    else hipLaunchKernelGGL(plo::kmethod_orders_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I, O);
+                }
+                else if (K.PM.unit) hipLaunchKernelGGL(plo::kmethod_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I);
+                else hipLaunchKernelGGL(plo::kmethod_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, K, J, I);
+            });
+            if (rc != PLO_OK) return rc;
+            if (again) break;
+            if (info) HIPCHK(hipMemcpy(info + 3u * done, d_info, cnt * 12, hipMemcpyDeviceToHost));
+            if (best && (best->seed == ~0ull || plo_pack_cost(cb.adds, cb.muls, cost_mode, 0) < plo_pack_cost(best->adds, best->muls, cost_mode, 0))) *best = cb;
+            done += cnt;
+        }
 #ifdef PLO_KM_PROFILE
         if (getenv("PLO_KM_STATS")) {
             unsigned long long g[8] = {0};
@@ -1702,10 +1727,42 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
         }
 #endif
         if (again) continue;                                                     // a pair table filled up: again with twice the slots
-        if (info) HIPCHK(hipMemcpy(info, d_info, nrestarts * 12, hipMemcpyDeviceToHost));
+        st->candidates = total;
         return call.done(PLO_OK);
     }
     return device_error(plo::ERR_TABLE);
+}
+} // namespace
+
+int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t nrestarts, uint32_t per_block, int cost_mode,
+                      uint32_t *adds, uint32_t *muls, uint32_t *info, plo_best_t *best, plo_stats_t *st)
+{
+    if (!M || nrestarts == 0 || per_block == 0) return fail(PLO_E_ARG, "bad argument");
+    if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
+    if (const int rc = require_device(NOINIT_CSE)) return rc;
+    if (p < 3 || p >= 0x80000000u || !(p & 1u)) return fail(PLO_E_ARG, "modulus must be an odd prime below 2^31");
+    if (const char *bad = csr_defect(M, p)) return fail(PLO_E_ARG, bad);
+    if (M->m == 0 || M->m > 128 || M->n == 0 || M->n > 64) return fail(PLO_E_UNSUPPORTED, "device decomposition needs at most 128 rows and 64 columns");
+    if (nrestarts > 0xFFFFFFFFull) return fail(PLO_E_ARG, "at most 2^32-1 restarts per call");
+    return kernel_search_run(M, p, seed0, nrestarts, nrestarts, per_block, cost_mode, adds, muls, info, best, st, nullptr);
+}
+
+int plo_kernel_search_orders(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t first, uint64_t count, uint32_t sub, int cost_mode,
+                             uint32_t *adds, uint32_t *muls, uint32_t *info, plo_best_t *best, plo_stats_t *st)
+{
+    if (!M || count == 0 || sub == 0) return fail(PLO_E_ARG, "bad argument");
+    if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
+    if (M->m < 2 || M->m > 12) return fail(PLO_E_ARG, "the row orders are walked for 2 to 12 rows");
+    uint64_t mfact = 1; for (uint32_t k = 2; k <= M->m; ++k) mfact *= k;
+    if (first >= mfact || count > mfact - first) return fail(PLO_E_ARG, "order range beyond m!");
+    if (const int rc = require_device(NOINIT_CSE)) return rc;
+    if (p < 3 || p >= 0x80000000u || !(p & 1u)) return fail(PLO_E_ARG, "modulus must be an odd prime below 2^31");
+    if (const char *bad = csr_defect(M, p)) return fail(PLO_E_ARG, bad);
+    if (M->n == 0 || M->n > 64) return fail(PLO_E_UNSUPPORTED, "device decomposition needs at most 128 rows and 64 columns");
+    // launches of at most 2^25 candidates (the device packs key << 32 | candidate, and no launch should hold a shared device for long); PLO_KORD_CHUNK: test knob, fewer
+    const uint64_t chunk = (uint64_t)std::min<long>(std::max<long>(env_knob("PLO_KORD_CHUNK").value_or(1l << 25), 1l), 1l << 25);
+    const KOrdReq ord{first, count, sub};
+    return kernel_search_run(M, p, seed0, count * sub, chunk, 1u, cost_mode, adds, muls, info, best, st, &ord);
 }
 
 } // extern "C"

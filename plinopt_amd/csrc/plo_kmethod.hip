@@ -26,6 +26,11 @@
 // sizes of Dep's image are bounded from rank(M) by the host, its pair table by a
 // sizing launch (kmethod_size_kernel); a full table is reported (ERR_TABLE) and
 // the launch repeated with a larger one, as for the other wave-kernel plans.
+//
+// Order enumeration (`bin/optimizer -N`, plo_kernel_search_orders): kmethod_orders_kernel is the same wave with step 2's
+// shuffle replaced by the pi-th permutation of the rows in lexicographic order (KOrd, kmethod_kth_order), m <= 12.  It shares
+// kmethod_decompose<ORD> and kmethod_candidate<UNITM, ORD> but is a kernel of its own: the random-order kernels compile to the
+// instructions they had, and a KPlan needs no more LDS.
 // ===========================================================================
 #pragma once
 #include <hip/hip_runtime.h>
@@ -53,6 +58,32 @@ __device__ unsigned long long g_kprof[8];   // lane 0 of every wave: cycles in i
 #endif
 struct KInfo { uint32_t *info; };  // optional, 3 words per candidate: rank, NotIndep, dependent rows
 enum { ERR_KDEC = 5 };             // device error word: decomposition inconsistent (rank, table of M)
+// Order enumeration (`bin/optimizer -N`, AllKernelOpt, reference include/plinopt_optimize.inl:1357-1418): the row order of a
+// decomposition is not drawn but PRESCRIBED -- the pi-th permutation of 0..m-1 in lexicographic order (std::next_permutation
+// from the identity; the reference's factoradic kthpermutation, include/plinopt_library.inl:289-304), m <= 12.  Candidate c of
+// a launch is global candidate g = cand0 + c of the call: order pi = first + g / sub, restart g % sub.  The decomposition's
+// stream is that of seed0 + pi (no shuffle: its first draw is NotIndep), the two Optimizer calls run from the job's seed0 + c.
+struct KOrd {
+    uint64_t seed0;                // of the call: the decomposition of order pi draws from seed0 + pi
+    uint64_t first, cand0;         // first order of the call; global index of the launch's candidate 0 (counted from first * sub)
+    uint64_t step_num, step_den;   // sizing launch only: sample s stands for order first + s * step_num / step_den (spread over the range)
+    uint32_t sub;                  // restarts per order
+    uint32_t fact[12];             // k! for k < m
+};
+// S.ord := the pi-th permutation of 0..m-1 (pi < m! <= 12! < 2^32).  Lane i takes digit i of pi in the factorial base, two divisions
+// each; the digits are then resolved against the set of rows not yet placed, one v_readlane and one bit search per position.
+__device__ __forceinline__ void kmethod_kth_order(const KOrd &O, uint32_t m, uint32_t pi, uint16_t *ord, uint32_t lane) {
+    uint32_t f = 1u;
+#pragma unroll
+    for (uint32_t k = 0; k < 12u; ++k) if (k + 1u + lane == m) f = O.fact[k];          // (m-1-lane)!
+    const uint32_t dig = lane < m ? (pi / f) % (m - lane) : 0u;
+    uint32_t left = (1u << m) - 1u;
+    for (uint32_t i = 0; i < m; ++i) {
+        const uint32_t pos = nth_set_bit((uint64_t)left, (uint32_t)__builtin_amdgcn_readlane((int)dig, (int)i));
+        left &= ~(1u << pos);
+        if (lane == 0) ord[i] = (uint16_t)pos;
+    }
+}
 
 // product mod p for the elimination: shift-and-add when p is a Mersenne prime (131071 = 2^17 - 1, the tools' usual modulus), Barrett otherwise
 __device__ __forceinline__ uint32_t kmul(uint32_t a, uint32_t b, uint32_t p, uint64_t mu, uint32_t mers) {
@@ -75,7 +106,8 @@ __device__ __forceinline__ KScratch kscratch(const KPlan &K, uint8_t *scr) {
 
 // Steps 1-2 and the draw of NotIndep.  M's image must be in `reg`.  Returns the number of dependent rows KEPT in Dep
 // (0: zero dimensional kernel); S.deps / S.depc hold the dependent rows in elimination order and their combinations
-// (indexed by basis position), S.basis the basis rows.
+// (indexed by basis position), S.basis the basis rows.  ORD: no shuffle -- the caller has put the order into S.ord (kmethod_kth_order).
+template <bool ORD>
 __device__ uint32_t kmethod_decompose(const KPlan &K, uint8_t *reg, const KScratch &S, const uint16_t *rsM, uint64_t dseed, uint32_t lane,
                                       uint32_t &notindep_out)
 {
@@ -91,10 +123,12 @@ __device__ uint32_t kmethod_decompose(const KPlan &K, uint8_t *reg, const KScrat
     const uint32_t sv = n + 1u, sc = R + 1u;
     uint32_t *V = (uint32_t *)(reg + K.off_vc), *C = V + m * sv;
     uint32_t rng = 1u + (uint32_t)(splitmix64(dseed) % 2147483646ull);
-    for (uint32_t row = lane; row < m; row += 64u) S.ord[row] = (uint16_t)row;
-    PLO_WAVE_SYNC();
-    if (lane == 0) for (uint32_t i = m; i > 1u; --i) { const uint32_t j = rng_next(rng) % i; const uint16_t t = S.ord[i - 1u]; S.ord[i - 1u] = S.ord[j]; S.ord[j] = t; }
-    rng = uni32(rng);
+    if (!ORD) {
+        for (uint32_t row = lane; row < m; row += 64u) S.ord[row] = (uint16_t)row;
+        PLO_WAVE_SYNC();
+        if (lane == 0) for (uint32_t i = m; i > 1u; --i) { const uint32_t j = rng_next(rng) % i; const uint16_t t = S.ord[i - 1u]; S.ord[i - 1u] = S.ord[j]; S.ord[j] = t; }
+        rng = uni32(rng);
+    }
     PLO_WAVE_SYNC();
     uint32_t mypos[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};                          // place of this lane's rows (lane, lane + 64) in the order
     for (uint32_t q = lane; q < m; q += 64u) S.piv[S.ord[q]] = (uint16_t)q;  // (piv doubles as the inverse permutation)
@@ -167,7 +201,7 @@ __device__ __forceinline__ uint32_t kmethod_dep_row(const KPlan &K, const KScrat
 }
 
 // One restart.  Returns adds<<32 | muls of the two programs together.
-template <bool UNITM>
+template <bool UNITM, bool ORD = false>
 __device__ uint64_t kmethod_candidate(const KPlan &K, uint8_t *reg, uint8_t *scr, const uint16_t *rsM, const uint16_t *rsD, uint64_t dseed, uint64_t seed,
                                       uint32_t lane, uint32_t *errw, uint32_t *info3)
 {
@@ -180,7 +214,7 @@ __device__ uint64_t kmethod_candidate(const KPlan &K, uint8_t *reg, uint8_t *scr
     for (uint32_t i = lane; i < (PM.tmpl_bytes >> 3); i += 64u) ((uint64_t *)reg)[i] = PM.tmpl[i];
     PLO_WAVE_SYNC();
     uint32_t notindep = 0;
-    const uint32_t kept = kmethod_decompose(K, reg, S, rsM, dseed, lane, notindep);
+    const uint32_t kept = kmethod_decompose<ORD>(K, reg, S, rsM, dseed, lane, notindep);
     if (info3 && lane == 0) { info3[0] = R; info3[1] = notindep; info3[2] = kept; }
     if (kept == 0u) { if (lane == 0) atomicMax(errw, (uint32_t)ERR_KDEC); return 0; }
     KP_T(0);
@@ -361,7 +395,76 @@ __global__ __launch_bounds__(256) void kmethod_size_kernel(KPlan K, WaveJob J, u
         for (uint32_t i = lane; i < twM; i += 64u) ((uint64_t *)reg)[i] = K.PM.tmpl[i];
         PLO_WAVE_SYNC();
         uint32_t ni = 0;
-        const uint32_t kept = kmethod_decompose(K, reg, S, rsM, dseed, lane, ni);
+        const uint32_t kept = kmethod_decompose<false>(K, reg, S, rsM, dseed, lane, ni);
+        if (kept == 0u) { if (lane == 0) atomicMax(&sz[2], 1u); continue; }
+        uint32_t pairs = 0, ent = 0;
+        for (uint32_t j = 0; j < kept; ++j) {
+            const uint32_t ln = kmethod_dep_row(K, S, j, lane);
+            pairs += ln * (ln - (ln ? 1u : 0u)) / 2u; ent += ln;
+        }
+        if (lane == 0) { atomicMax(&sz[0], pairs); atomicMax(&sz[1], ent); }
+        PLO_WAVE_SYNC();
+    }
+}
+
+// ---- the same two kernels over PRESCRIBED row orders (KOrd).  Kernels of their own, not a run-time branch of the two above: the
+// random-order kernels keep the code and the registers they had.
+template <bool UNITM>
+__global__ __launch_bounds__(256) void kmethod_orders_kernel(KPlan K, WaveJob J, KInfo I, KOrd O)
+{
+    extern __shared__ uint64_t lds64[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    kmethod_stage_rs(K, lds64);
+    const uint16_t *rsM = (const uint16_t *)lds64, *rsD = (const uint16_t *)(lds64 + (K.PM.rs_bytes >> 3));
+    uint8_t *reg = (uint8_t *)lds64 + K.PM.rs_bytes + K.PD.rs_bytes + (size_t)wave * (K.region + K.scratch_bytes);
+    uint8_t *scr = reg + K.region;
+    uint16_t *ord = kscratch(K, scr).ord;
+    uint64_t best = ~0ull;
+    const uint64_t stride = (uint64_t)gridDim.x * nwaves;
+    for (uint64_t c = (uint64_t)blockIdx.x * nwaves + wave; c < J.ncand; c += stride) {
+        const uint64_t pi = O.first + (O.cand0 + c) / O.sub;                     // 64-bit: count * sub does not fit 32
+        kmethod_kth_order(O, K.m, (uint32_t)pi, ord, lane);                     // (the scratch is not touched by the image copy that opens the candidate)
+        const uint64_t res = kmethod_candidate<UNITM, true>(K, reg, scr, rsM, rsD, O.seed0 + pi, J.seed0 + c, lane, J.err, I.info ? I.info + 3ull * c : nullptr);
+        const uint32_t a = (uint32_t)(res >> 32), mu_ = (uint32_t)res;
+        if (lane == 0) { if (J.adds) J.adds[c] = a; if (J.muls) J.muls[c] = mu_; }
+        const uint64_t packed = ((uint64_t)cost_key32(a, mu_, J.cost_mode) << 32) | (uint32_t)c;
+        best = packed < best ? packed : best;
+        PLO_WAVE_SYNC();
+    }
+    if (J.best) {
+        __syncthreads();
+        if (lane == 0) lds64[wave] = best;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint64_t b = lds64[0];
+            for (uint32_t w = 1; w < nwaves; ++w) b = lds64[w] < b ? lds64[w] : b;
+            if (b != ~0ull) atomicMin(J.best, (unsigned long long)b);
+        }
+    }
+}
+template __global__ void kmethod_orders_kernel<true>(KPlan, WaveJob, KInfo, KOrd);
+template __global__ void kmethod_orders_kernel<false>(KPlan, WaveJob, KInfo, KOrd);
+
+// Sizing launch of the order walk: sample c is an order of the WHOLE range (first + c * step_num / step_den), not one of its first
+// few -- neighbouring indices share a long prefix and hence a basis.  sz as above.
+__global__ __launch_bounds__(256) void kmethod_size_orders_kernel(KPlan K, WaveJob J, KOrd O, uint32_t *sz)
+{
+    extern __shared__ uint64_t lds64[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const uint32_t rwM = K.PM.rs_bytes >> 3, twM = K.PM.tmpl_bytes >> 3;
+    for (uint32_t i = threadIdx.x; i < rwM; i += blockDim.x) lds64[i] = K.PM.tmpl[twM + i];
+    __syncthreads();
+    const uint16_t *rsM = (const uint16_t *)lds64;
+    uint8_t *reg = (uint8_t *)lds64 + K.PM.rs_bytes + (size_t)wave * (K.region + K.scratch_bytes);
+    const KScratch S = kscratch(K, reg + K.region);
+    const uint64_t stride = (uint64_t)gridDim.x * nwaves;
+    for (uint64_t c = (uint64_t)blockIdx.x * nwaves + wave; c < J.ncand; c += stride) {
+        const uint64_t pi = O.first + c * O.step_num / O.step_den;
+        for (uint32_t i = lane; i < twM; i += 64u) ((uint64_t *)reg)[i] = K.PM.tmpl[i];
+        kmethod_kth_order(O, K.m, (uint32_t)pi, S.ord, lane);
+        PLO_WAVE_SYNC();
+        uint32_t ni = 0;
+        const uint32_t kept = kmethod_decompose<true>(K, reg, S, rsM, O.seed0 + pi, lane, ni);
         if (kept == 0u) { if (lane == 0) atomicMax(&sz[2], 1u); continue; }
         uint32_t pairs = 0, ent = 0;
         for (uint32_t j = 0; j < kept; ++j) {

@@ -192,6 +192,24 @@ def kernel_search(M, p, seed0, nrestarts, per_block=1, cost_mode=capi.COST_SUM_T
     return (list(adds) if want_costs else None), (list(muls) if want_costs else None), inf, (b.adds, b.muls, b.seed), st.as_dict()
 
 
+def kernel_search_orders(M, p, seed0, first, count, sub=1, cost_mode=capi.COST_SUM_THEN_ADD, want_costs=True):
+    """The kernel method over prescribed row orders (`plo_kernel_search_orders`, `bin/optimizer -N`): candidate c is restart
+    c % sub of the (first + c // sub)-th permutation of the rows in lexicographic order.  M = (m, n, rowptr, col, val).  Returns
+    (adds, muls, info, (best adds, best muls, best seed), stats); the winner's order index is (best seed - seed0) // sub."""
+    L = capi.lib()
+    m, n, rp, col, val = M
+    A, keep = capi.make_csr(m, n, rp, col, val)
+    nc = count * sub
+    adds = (ctypes.c_uint32 * max(nc, 1))() if want_costs else None
+    muls = (ctypes.c_uint32 * max(nc, 1))() if want_costs else None
+    info = (ctypes.c_uint32 * max(3 * nc, 1))() if want_costs else None
+    b, st = capi.Best(), capi.Stats()
+    capi.check(L.plo_kernel_search_orders(ctypes.byref(A), p, seed0, first, count, sub, cost_mode, adds, muls, info, ctypes.byref(b), ctypes.byref(st)))
+    del keep
+    inf = [tuple(info[3 * k:3 * k + 3]) for k in range(nc)] if want_costs else None
+    return (list(adds[:nc]) if want_costs else None), (list(muls[:nc]) if want_costs else None), inf, (b.adds, b.muls, b.seed), st.as_dict()
+
+
 def kernel_search_multi(M, p, seed0, nrestarts, devices, cost_mode=capi.COST_SUM_THEN_ADD):
     """`plo_kernel_search_multi`: the restart loop of the kernel method over the listed devices from this process (one host thread
     and one device per contiguous shard, minimum by the RCCL MIN all-reduces).  Returns ((adds, muls, seed), stats)."""
