@@ -1,8 +1,8 @@
 // ==========================================================================
 // plo_dl.hpp -- what the host tools that drive the device share (bin/optimizer, bin/sparsifier, bin/trilplacer, bin/inplacer,
 // bin/orbiter): where they look for libplinopt_hip.so (PLO_HIP_LIB / PLINOPT_HIP_LIB, then plinopt_amd/ beside the tool's bin/
-// directory and the tool's own directory, then the loader's search path), how they name its symbols, and the rational CSR
-// that the plo_*_plan_create_q entries take.
+// directory and the tool's own directory, then the loader's search path), how they name its symbols, and the CSRs of its
+// entries: over Z_p, and the rational one that the plo_*_plan_create_q entries take.
 // ==========================================================================
 #pragma once
 #include "plo_host.hpp"
@@ -32,6 +32,20 @@ inline void *open_hip_lib() {
 template <class Fn> Fn hip_sym(void *h, const char *name, bool *ok) { Fn f = h ? (Fn)dlsym(h, name) : nullptr; if (!f && ok) *ok = false; return f; }
 #define PLO_SYM(field, fn) decltype(&fn) field = plo::hip_sym<decltype(&fn)>(h, #fn, &ok)
 #define PLO_SYM_OPT(field, fn) decltype(&fn) field = plo::hip_sym<decltype(&fn)>(h, #fn, nullptr)
+
+// A matrix over Z_p (residues below 2^31) as the CSR of the C-ABI
+struct Csr {
+    uint32_t m = 0, n = 0; std::vector<uint32_t> rp{0}, col, val;
+    plo_csr_t view() const { return plo_csr_t{m, n, rp.data(), col.data(), val.data()}; }
+};
+template <class E> Csr csr(const SparseMat<E> &M) {
+    Csr c; c.m = (uint32_t)M.rowdim(); c.n = (uint32_t)M.coldim();
+    for (const auto &row : M.rows) {
+        for (const auto &e : row) { c.col.push_back((uint32_t)e.first); c.val.push_back((uint32_t)e.second); }
+        c.rp.push_back((uint32_t)c.col.size());
+    }
+    return c;
+}
 
 // A matrix over Q as the rational CSR of the C-ABI; wide: a coefficient that does not fit its 64-bit numerators and denominators
 // (Rat is 128 bits wide, its denominator positive), which keeps the matrix on the host
