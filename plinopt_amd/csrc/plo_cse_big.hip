@@ -656,10 +656,18 @@ template <class LOG> __device__ __forceinline__ void dlog_append3(LOG dlog, uint
     if (h2) dlog[base + n1 + (uint32_t)__builtin_popcountll(m2 & below)] = e2;
     if (h3) dlog[base + n1 + n2 + (uint32_t)__builtin_popcountll(m3 & below)] = e3;
 }
+// Inclusive prefix sum over the 64 lanes of a wave, in registers: six v_add_u32_dpp and no LDS instruction (a loop of __shfl_up is
+// six ds_bpermute, each a dependent LDS round trip).  Within a row of 16 lanes by row_shr:1/2/4/8 (a lane near the row's start adds
+// the old value, 0); then lane 15 of rows 0 and 2 goes to rows 1 and 3 (row_bcast:15, rows 0xA), then lane 31 to rows 2 and 3
+// (row_bcast:31, rows 0xC).
+// EVERY LANE OF THE WAVE MUST BE ACTIVE: DPP reads nothing from a lane that is switched off.  The callers are all on wave-uniform
+// paths: the tie pick (inside `wave == 0`), the head of a batch of the flat sweep (the batch loop runs to nrw, a function of the wave),
+// the partition pass and bounds() of the merge (the round and group loops run on workgroup-uniform counts) and ProgramGen's compaction.
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)v, o); if ((int)lane >= o) v += t; }
+#define PLO_DPP_ADD(ctrl_, rows_) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl_, rows_, 0xF, false)
+    PLO_DPP_ADD(0x111, 0xF); PLO_DPP_ADD(0x112, 0xF); PLO_DPP_ADD(0x114, 0xF); PLO_DPP_ADD(0x118, 0xF);     // row_shr:1, 2, 4, 8
+    PLO_DPP_ADD(0x142, 0xA); PLO_DPP_ADD(0x143, 0xC);                                                       // row_bcast:15, row_bcast:31
+#undef PLO_DPP_ADD
     return v;
 }
 // add `delta` to the biased count of `key` in the LDS summing table (find or claim)
@@ -1105,9 +1113,7 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                     uint32_t q8[8], mine = 0;
 #pragma unroll
                     for (int u = 0; u < 8; ++u) { q8[u] = sh.cblk[lane * 8u + (uint32_t)u]; mine += q8[u]; }
-                    uint32_t inc = mine;
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)inc, o); if ((int)lane >= o) inc += t; }
+                    const uint32_t inc = wave_incl_scan(mine);
                     const uint64_t hm0 = __ballot(k32 < inc);
                     if (!hm0) { if (lane == 0) wg_max(&sh.errflag, (uint32_t)BERR_SEL); }
                     const uint32_t L0 = hm0 ? (uint32_t)__builtin_ctzll(hm0) : 0u;
@@ -1120,9 +1126,7 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                     k = (uint64_t)k32;
                 }
                 const uint32_t c = blk * 64u + lane;
-                uint32_t q = c < ncols ? gload32(&cntM[c]) : 0u, incl = q;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) { uint32_t t = (uint32_t)__shfl_up((int)incl, o); if ((int)lane >= o) incl += t; }
+                const uint32_t q = c < ncols ? gload32(&cntM[c]) : 0u, incl = wave_incl_scan(q);
                 const uint64_t kk = k - run;                                           // (both wave-uniform)
                 const uint64_t hm = __ballot(kk < (uint64_t)incl);
                 if (!hm) { if (lane == 0) wg_max(&sh.errflag, (uint32_t)BERR_SEL); }
@@ -1392,7 +1396,7 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                 const uint32_t qq = have ? wave + (k0 + lane) * nwaves : wave;
                 const uint4 R0 = *(const uint4 *)(aff + 4u * qq);
                 const uint32_t Lr = have ? (R0.z & PLO_RW_LEN) : 0u;
-                const uint32_t RZ = R0.z - 1u;                          // the record word with the row's LAST POSITION in the length field (L >= 2: no borrow), once per row instead of an add per entry
+                const uint32_t RZ = R0.z;                               // the record word: the trips take via and vib from it
                 const uint32_t E = wave_incl_scan(Lr), S = E - Lr, T = RL(E, 63);
                 const uint32_t safe = RL(R0.y, 0);
                 uint32_t qlo = 0;
@@ -1433,9 +1437,8 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                     auto body3 = [&](uint32_t t, uint32_t adc, uint32_t zc, uint32_t ppc, uint32_t rzc, uint32_t ec) {
                         const uint32_t pa = ppc & 0xFFFFu, pb = ppc >> 16;
                         const bool in = w0 + (t << 6) + lane < T, act = in && zc != pa && zc != pb;
-                        // (the two UNCONDITIONAL stores: see the one-ahead loop below)
+                        // (the UNCONDITIONAL store: see the one-ahead loop below)
                         ent[act && zc > pa ? adc - 1u - (zc > pb ? 1u : 0u) : dump] = ec;
-                        ent[in && zc == (rzc & PLO_RW_LEN) ? adc - 1u : dump] = (rzc & PLO_RW_NEW) | lm;
                         if (act) retire_entry(ec, rzc, zc > pa, make_uint2(0, 0), make_uint2(0, 0));
                     };
                     uint32_t a0_, z0_, p0_, r0_, e0_, a1_, z1_, p1_, r1_, e1_, a2_, z2_, p2_, r2_, e2_;
@@ -1458,12 +1461,11 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
 #endif
                         const uint32_t pa = ppc & 0xFFFFu, pb = ppc >> 16;
                         const bool in = w0 + (t << 6) + lane < T, act = in && zc != pa && zc != pb;
-                        // the row is rewritten in the same pass (:96-110): entries right of the first removed position shift left;
-                        // the new column's entry goes last (len and the +-1 counters were updated by the search).  Both stores are
-                        // UNCONDITIONAL (idle lanes write to a dump word behind the entries): behind a branch the compiler cannot
-                        // count them and waits for every store of the trip (vmcnt(0)) before it uses the entry requested a trip ahead.
+                        // the row is rewritten in the same pass (:96-110): entries right of the first removed position shift left
+                        // (the new column's entry goes last, at the end of the batch: below).  The store is UNCONDITIONAL (idle
+                        // lanes write to a dump word behind the entries): behind a branch the compiler cannot count it and waits
+                        // for every store of the trip (vmcnt(0)) before it uses the entry requested a trip ahead.
                         ent[act && zc > pa ? adc - 1u - (zc > pb ? 1u : 0u) : dump] = ec;
-                        ent[in && zc == (rzc & PLO_RW_LEN) ? adc - 1u : dump] = (rzc & PLO_RW_NEW) | lm;
 #ifdef PLO_BIG_PROFILE
                         __builtin_amdgcn_wave_barrier(); const unsigned long long t1_ = clock64(); probe_iters = 0;
 #endif
@@ -1477,6 +1479,11 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                     }
 #endif
                 }
+                // The new column's entry goes last (len and the +-1 counters were updated by the search): ONE store per row, by the
+                // lane that holds the row's record, not a test and a store in every trip (one lane in a hundred had anything to
+                // store there).  This wave issued every load of the row before it (the in-order property of the in-place rewrite),
+                // and a trip's store reaches position L - 3 at most: L - 2 is written here alone.
+                if (have) ent[R0.y + Lr - 2u] = (R0.z & PLO_RW_NEW) | lm;
             }
             } else
             for (uint32_t k0 = 0; k0 < nrw; k0 += 64u) {
