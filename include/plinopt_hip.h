@@ -167,6 +167,21 @@ int plo_cse_chain_cost_many(plo_chain_t *chain, const uint64_t *seeds, uint64_t 
 int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_t *seconds, uint32_t p, uint64_t seed0, uint32_t per_pair,
                         int cost_mode, uint32_t *adds, uint32_t *muls, plo_best_t *best, plo_stats_t *stats);
 
+/* nprob independent restart searches in one call.  Problem q is the loop of CSEOptimiser on firsts[q] (seconds == NULL),
+ * or the chained loop of LUOptimiser on (firsts[q], seconds[q]) with one random stream, as plo_cse_chain_*.
+ * Candidate j of problem q (0 <= j < per_problem) has seed seed0 + q*per_problem + j.
+ * bests[q] = its minimum under (cost key of cost_mode, seed), with the winner's split under every cost mode; status[q] = PLO_OK,
+ * or the code with which the LDS-resident wave kernel refuses that problem (PLO_E_CAPACITY / PLO_E_UNSUPPORTED; bests[q] is then
+ * +infinity and the other problems are not affected).  One workgroup per problem (plo::cse_batch_kernel), one launch per bucket
+ * of LDS footprints; a problem whose pair table fills up is built again with twice the slots and launched again alone (scale 2,
+ * 4, 8, 16, then PLO_E_CAPACITY for that problem).  stats->launches counts the launches, stats->candidates the candidates
+ * evaluated, those of repeated problems again; the shape fields are the last launch's.  Environment: PLO_BATCH_GRID caps the
+ * workgroups of a launch (tests), PLO_BATCH_STATS prints one '#' line per launch on stderr.
+ * PLO_E_ARG: a null array (seconds may be), nprob == 0, per_problem == 0, an even modulus or one of 2^31 and more, cost_mode outside
+ * 0..2, more than 2^32-1 candidates, a defective matrix. */
+int plo_cse_batch_search(uint32_t nprob, const plo_csr_t *firsts, const plo_csr_t *seconds, uint32_t p, uint64_t seed0,
+                         uint32_t per_problem, int cost_mode, plo_best_t *bests, int32_t *status, plo_stats_t *stats);
+
 
 /* The kernel method of bin/optimizer -K with EVERYTHING on the device (plo::kmethod_kernel): restart c (seed seed0 + c) is one
  * pass of the loop of KernelOptimiser, include/plinopt_optimize.inl:1299-1340 -- a nullspace decomposition of M

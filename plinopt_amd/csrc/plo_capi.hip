@@ -7,6 +7,7 @@
 // entry point fails with PLO_E_HIP.
 // ===========================================================================
 #include "plo_cse_wave.hip"
+#include "plo_cse_batch.hip"
 #include "plo_kmethod.hip"
 #include "plo_cse_big.hip"
 #include "plo_cob.hip"
@@ -1494,6 +1495,175 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
     }
     if (stuck) return fail(PLO_E_CAPACITY, "pair table full, and twice the slots do not fit the LDS-resident wave kernel");
     return device_error(plo::ERR_TABLE);
+}
+
+} // extern "C"
+namespace {
+// Host side of one problem of plo_cse_batch_search: its one or two plans and images at the table scale they were last built with
+struct BatchSlot {
+    uint32_t scale = 2;                  // cap_scale asked for (2, 4, 8, 16: the growth rule of plo_cse_chain_batch, per problem)
+    uint32_t got[2] = {0, 0};            // the scale each plan took (one that no longer fits twice the slots keeps the largest table that does)
+    plo::WavePlan P[2]{};
+    std::vector<uint8_t> img[2];
+    int rc = PLO_OK; std::string why;
+    uint32_t foot = 0;                   // LDS bytes of the problem beside the reduction scratch, with one wave: row starts + one region
+};
+// Buckets of plo_cse_batch_search by that footprint: up to 4, 8, 16, 32, 64 KiB and the rest of the LDS
+constexpr uint32_t BATCH_BUCKETS = 6;
+uint32_t batch_bucket(uint32_t foot) { uint32_t b = 0; while (b + 1 < BATCH_BUCKETS && foot > (4096u << b)) ++b; return b; }
+
+// fn(k) for 0 <= k < n on host threads (no OpenMP runtime in this library: the callers bring their own)
+template <class Fn> void on_host_threads(size_t n, Fn fn) {
+    std::atomic<size_t> next{0};
+    auto work = [&]() { for (;;) { const size_t k = next.fetch_add(1); if (k >= n) break; fn(k); } };
+    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)64, n}));
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work);
+    work();
+    for (auto &th : pool) th.join();
+}
+
+// the plans of one problem at S.scale; S.rc / S.why: the refusal of the wave kernel, if any
+void batch_build(BatchSlot &S, const plo_csr_t *first, const plo_csr_t *second, uint32_t p, size_t lds_max)
+{
+    const uint32_t prev[2] = {S.got[0], S.got[1]};
+    const int nmat = second ? 2 : 1;
+    S.rc = PLO_OK; S.why.clear();
+    for (int k = 0; k < nmat; ++k) {
+        plo_plan tmp;
+        set_matrix(&tmp, k ? second : first, p);
+        int rc = PLO_E_CAPACITY;
+        for (uint32_t s = S.scale; s >= 2u; s /= 2u) {
+            tmp.cap_scale = s;
+            rc = build_plan(&tmp, &S.img[k]);
+            if (rc != PLO_E_CAPACITY) { S.got[k] = s; break; }
+            if (s == S.scale) S.why = g_err;
+        }
+        if (rc != PLO_OK) { S.rc = rc; if (rc != PLO_E_CAPACITY) S.why = g_err; return; }
+        S.P[k] = tmp.P;
+    }
+    if (prev[0] && S.got[0] == prev[0] && S.got[1] == prev[1]) { S.rc = PLO_E_CAPACITY; S.why = "pair table full, and with twice the slots: " + S.why; return; }
+    const uint32_t region = nmat == 2 ? std::max(S.P[0].region_bytes, S.P[1].region_bytes) : S.P[0].region_bytes;
+    S.foot = S.P[0].rs_bytes + (nmat == 2 ? S.P[1].rs_bytes : 0u) + region;
+    if (64ull + S.foot > lds_max) { S.rc = PLO_E_CAPACITY; S.why = "candidate state does not fit the 160 KiB LDS of one CU"; }
+}
+} // namespace
+extern "C" {
+
+// Many restart searches in one call, one minimum each (plo::cse_batch_kernel, one workgroup per problem).
+int plo_cse_batch_search(uint32_t nprob, const plo_csr_t *firsts, const plo_csr_t *seconds, uint32_t p, uint64_t seed0,
+                         uint32_t per_problem, int cost_mode, plo_best_t *bests, int32_t *status, plo_stats_t *st)
+{
+    if (!firsts || !bests || !status || nprob == 0 || per_problem == 0) return fail(PLO_E_ARG, "bad argument");
+    if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
+    if (p < 3 || p >= 0x80000000u || !(p & 1u)) return fail(PLO_E_ARG, "modulus must be an odd prime below 2^31");
+    if ((uint64_t)nprob * per_problem > 0xFFFFFFFFull) return fail(PLO_E_ARG, "at most 2^32-1 candidates per call");
+    if (const int rc = require_device(NOINIT_CSE)) return rc;
+    for (uint32_t q = 0; q < nprob; ++q) {
+        if (const char *bad = csr_defect(&firsts[q], p)) return fail(PLO_E_ARG, "problem " + std::to_string(q) + ": " + bad);
+        if (seconds) if (const char *bad = csr_defect(&seconds[q], p)) return fail(PLO_E_ARG, "problem " + std::to_string(q) + ", second matrix: " + bad);
+    }
+    CallScope call(st); st = call.st;
+    for (uint32_t q = 0; q < nprob; ++q) { bests[q].adds = bests[q].muls = 0xFFFFFFFFu; bests[q].seed = ~0ull; status[q] = PLO_OK; }
+    const std::optional<long> grid_cap = env_knob("PLO_BATCH_GRID");           // test knob: one workgroup can be made to take many problems in turn
+    const bool batch_stats = env_knob("PLO_BATCH_STATS").has_value();          // a '#' line per launch on stderr (the measurements of DESIGN.md 2.11)
+    const size_t lds_max = g_lds_max;
+    DevBuf<unsigned long long> d_keys; DevBuf<uint32_t> d_adds, d_muls, d_err;
+    HIPCHK(hipMalloc((void **)&d_keys.p, nprob * 8ull)); HIPCHK(hipMalloc((void **)&d_adds.p, nprob * 4ull));
+    HIPCHK(hipMalloc((void **)&d_muls.p, nprob * 4ull)); HIPCHK(hipMalloc((void **)&d_err.p, nprob * 4ull));
+    HIPCHK(hipMemsetAsync(d_keys, 0xFF, nprob * 8ull, g_stream));
+    std::vector<BatchSlot> S(nprob);
+    std::vector<uint32_t> todo(nprob), err(nprob);
+    for (uint32_t q = 0; q < nprob; ++q) todo[q] = q;
+    while (!todo.empty()) {
+        on_host_threads(todo.size(), [&](size_t k) { const uint32_t q = todo[k]; batch_build(S[q], &firsts[q], seconds ? &seconds[q] : nullptr, p, lds_max); });
+        std::vector<uint32_t> live[BATCH_BUCKETS];
+        size_t total = 0, nlive = 0;
+        for (const uint32_t q : todo) {
+            if (S[q].rc == PLO_E_CAPACITY || S[q].rc == PLO_E_UNSUPPORTED) { status[q] = S[q].rc; continue; }     // the wave kernel refuses this problem alone
+            if (S[q].rc != PLO_OK) return fail(S[q].rc, "problem " + std::to_string(q) + ": " + S[q].why);
+            live[batch_bucket(S[q].foot)].push_back(q); ++nlive;
+            for (int k = 0; k < (seconds ? 2 : 1); ++k) total += round_up((uint32_t)S[q].img[k].size(), 64);
+        }
+        if (!nlive) break;
+        // one device buffer for all images, one array of problems in bucket order
+        std::vector<uint8_t> blob(total + 64, 0);
+        std::vector<plo::BatchProb> probs; probs.reserve(nlive);
+        DevBuf<uint8_t> d_img; DevBuf<plo::BatchProb> d_probs;
+        HIPCHK(hipMalloc((void **)&d_img.p, blob.size()));
+        size_t off = 0;
+        for (const auto &bucket : live)
+            for (const uint32_t q : bucket) {
+                plo::BatchProb B{}; B.q = q; B.chained = seconds ? 1u : 0u;
+                for (int k = 0; k < (seconds ? 2 : 1); ++k) {
+                    std::memcpy(blob.data() + off, S[q].img[k].data(), S[q].img[k].size());
+                    (k ? B.P2 : B.P1) = S[q].P[k];
+                    (k ? B.P2 : B.P1).tmpl = (const uint64_t *)(d_img.p + off);
+                    off += round_up((uint32_t)S[q].img[k].size(), 64);
+                }
+                probs.push_back(B);
+            }
+        HIPCHK(hipMemcpy(d_img, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc((void **)&d_probs.p, probs.size() * sizeof(plo::BatchProb)));
+        HIPCHK(hipMemcpy(d_probs, probs.data(), probs.size() * sizeof(plo::BatchProb), hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(d_err, 0, nprob * 4ull, g_stream));
+        size_t first = 0;
+        for (const auto &bucket : live)
+            for (size_t b0 = 0, b1; b0 < bucket.size(); b0 = b1) {
+                // One launch takes the problems b0 .. b1-1 of the bucket: all of them, unless the largest row starts and the largest region -- of different
+                // problems -- no longer fit the LDS together (only possible for footprints near the LDS: each problem alone fits, batch_build)
+                plo::BatchJob J{}; J.probs = d_probs.p + first; J.per = per_problem; J.cost_mode = (uint32_t)cost_mode; J.seed0 = seed0;
+                J.keys = d_keys; J.adds = d_adds; J.muls = d_muls; J.err = d_err;
+                for (b1 = b0; b1 < bucket.size(); ++b1) {
+                    const BatchSlot &X = S[bucket[b1]];
+                    const uint32_t r1 = std::max(J.rs1max, X.P[0].rs_bytes), r2 = seconds ? std::max(J.rs2max, X.P[1].rs_bytes) : 0u;
+                    const uint32_t rg = std::max(J.region, X.foot - X.P[0].rs_bytes - (seconds ? X.P[1].rs_bytes : 0u));
+                    if (b1 > b0 && 64ull + r1 + r2 + rg > lds_max) break;
+                    J.rs1max = r1; J.rs2max = r2; J.region = rg;
+                }
+                const size_t count = b1 - b0;
+                J.nprob = (uint32_t)count;
+                // Waves per workgroup: 8, 4, 2 or 1, the most that fit the LDS -- the waves of a workgroup are all the parallelism one problem gets -- and
+                // no more than twice its candidates.  One workgroup per problem, handed out by the hardware as workgroups retire, so that cheap and dear
+                // problems balance themselves; the stride loop of the kernel only turns under the grid knob (and past 2^31 - 1 problems).
+                const auto need = [&](uint32_t w) { return 64u + J.rs1max + J.rs2max + w * J.region; };
+                uint32_t W = 8;
+                while (W > 1u && (need(W) > lds_max || W / 2u >= per_problem)) W /= 2u;
+                const uint32_t lds = need(W);
+                uint32_t per_cu = 1;
+                if (const int rc = occupancy_for((const void *)plo::cse_batch_kernel, W, lds, &per_cu)) return rc;
+                uint64_t grid = std::min<uint64_t>(count, 0x7FFFFFFFull);
+                if (grid_cap && *grid_cap > 0) grid = std::min<uint64_t>(grid, (uint64_t)*grid_cap);
+                const LaunchShape shape{grid, lds, W, 0};
+                const double ms0 = st->kernel_ms;
+                if (const int rc = timed_launch(st, &shape, [&] { hipLaunchKernelGGL(plo::cse_batch_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, J); })) return rc;
+                if (batch_stats) fprintf(stderr, "# batch: scale %u, bucket %u: %zu problems, %u waves per workgroup, %u LDS bytes, %u workgroups per CU, grid %llu, %.3f ms\n",
+                                         S[bucket[b0]].scale, batch_bucket(S[bucket[b0]].foot), count, W, lds, per_cu, (unsigned long long)grid, st->kernel_ms - ms0);
+                st->candidates += (uint64_t)count * per_problem;
+                first += count;
+            }
+        HIPCHK(hipMemcpy(err.data(), d_err, nprob * 4ull, hipMemcpyDeviceToHost));
+        // a full pair table is that problem's alone: only those are built again with twice the slots and launched again
+        std::vector<uint32_t> next;
+        for (const auto &bucket : live)
+            for (const uint32_t q : bucket) {
+                if (!err[q]) continue;
+                if (err[q] != plo::ERR_TABLE) { const int rc = device_error((int)err[q]); return fail(rc, "problem " + std::to_string(q) + ": " + g_err); }
+                if (S[q].scale >= 16u) { status[q] = PLO_E_CAPACITY; continue; }
+                S[q].scale *= 2u; next.push_back(q);
+            }
+        todo = std::move(next);
+    }
+    std::vector<unsigned long long> keys(nprob); std::vector<uint32_t> adds(nprob), muls(nprob);
+    HIPCHK(hipMemcpy(keys.data(), d_keys, nprob * 8ull, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(adds.data(), d_adds, nprob * 4ull, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(muls.data(), d_muls, nprob * 4ull, hipMemcpyDeviceToHost));
+    for (uint32_t q = 0; q < nprob; ++q) {
+        if (status[q] != PLO_OK) continue;
+        if (keys[q] == ~0ull) return fail(PLO_E_INTERNAL, "problem " + std::to_string(q) + ": no result");
+        bests[q].adds = adds[q]; bests[q].muls = muls[q]; bests[q].seed = seed0 + (uint64_t)q * per_problem + (keys[q] & 0xFFFFFFFFull);
+    }
+    return call.done(PLO_OK);
 }
 
 int plo_cse_chain_cost_many(plo_chain_t *ch, const uint64_t *seeds, uint64_t seed0, uint64_t n,

@@ -175,6 +175,31 @@ def chain_batch(pairs, p, seed0, per_pair, cost_mode=capi.COST_SUM_THEN_ADD, wan
     return (list(adds) if want_costs else None), (list(muls) if want_costs else None), (b.adds, b.muls, b.seed), st.as_dict()
 
 
+def cse_batch_search(firsts, seconds, p, seed0, per_problem, cost_mode=capi.COST_SUM_THEN_ADD):
+    """Many independent restart searches in one call (`plo_cse_batch_search`): firsts = [(m,n,rowptr,col,val), ...], seconds the
+    same for the chained search of pairs, or None; candidate j of problem q has seed seed0 + q*per_problem + j.  Returns
+    ([(best adds, best muls, best seed) per problem], [status per problem], stats); a problem the wave kernel refuses has its
+    code in status and (2^32-1, 2^32-1, 2^64-1) as best."""
+    L = capi.lib()
+    nprob = len(firsts)
+    if seconds is not None and len(seconds) != nprob:
+        raise ValueError("firsts and seconds differ in length")
+    keep = []
+
+    def array(mats):
+        arr = (capi.CSR * max(len(mats), 1))()
+        for k, (m, n, rp, col, val) in enumerate(mats):
+            a = ((ctypes.c_uint32 * len(rp))(*rp), (ctypes.c_uint32 * max(len(col), 1))(*col), (ctypes.c_uint32 * max(len(val), 1))(*val))
+            keep.append(a)
+            arr[k] = capi.CSR(m, n, a[0], a[1], a[2])
+        return arr
+    A = array(firsts)
+    B = array(seconds) if seconds is not None else None
+    bests, status, st = (capi.Best * max(nprob, 1))(), (ctypes.c_int32 * max(nprob, 1))(), capi.Stats()
+    capi.check(L.plo_cse_batch_search(nprob, A, B, p, seed0, per_problem, cost_mode, bests, status, ctypes.byref(st)))
+    return [(b.adds, b.muls, b.seed) for b in bests[:nprob]], list(status[:nprob]), st.as_dict()
+
+
 def kernel_search(M, p, seed0, nrestarts, per_block=1, cost_mode=capi.COST_SUM_THEN_ADD, want_costs=True):
     """The kernel method with decomposition, images and both Optimizer calls on the device (`plo_kernel_search`):
     M = (m, n, rowptr, col, val).  Returns (adds, muls, info, (best adds, best muls, best seed), stats); info[c] =
