@@ -182,6 +182,30 @@ int plo_cse_chain_batch(uint32_t npairs, const plo_csr_t *firsts, const plo_csr_
 int plo_cse_batch_search(uint32_t nprob, const plo_csr_t *firsts, const plo_csr_t *seconds, uint32_t p, uint64_t seed0,
                          uint32_t per_problem, int cost_mode, plo_best_t *bests, int32_t *status, plo_stats_t *stats);
 
+/* The kernel method (plo_kernel_search with per_block = 1) on nprob matrices in one call, one minimum each.
+ * Restart j of problem q (0 <= j < per_problem) has seed seed0 + q*per_problem + j, which is also the seed of its decomposition.
+ * bests[q] = the minimum under (cost key of cost_mode, seed) over the problem's own seeds, with the winner's split under every cost
+ * mode and the absolute seed; status[q] = PLO_OK, or the code plo_kernel_search gives that matrix:
+ *   PLO_E_UNSUPPORTED  zero dimensional kernel, zero matrix, more than 128 rows, more than 64 columns, more than 64 dependent rows;
+ *   PLO_E_CAPACITY     more than 64 rows with an entry other than +-1, a pair key too wide, Dep's image does not fit the LDS, or its
+ *                      tables are still too small at scale 32;
+ *   PLO_E_INTERNAL     a device decomposition that contradicts the host's rank (ERR_KDEC).
+ * For any status but PLO_OK bests[q] is +infinity (2^32-1, 2^32-1, 2^64-1) and the other problems are not affected.
+ * One workgroup per problem (plo::kmethod_batch_kernel), one launch per bucket of LDS footprints (row starts + region + scratch, the
+ * classes of plo_cse_batch_search), 8, 4, 2 or 1 waves per workgroup by LDS and at most twice per_problem.  Before the search ONE
+ * sizing launch decomposes the first min(per_problem, 64) restarts of every problem and Dep's image is laid out from their largest
+ * entry and pair counts (+60 %, 0.75 x); a problem whose hard bounds (dependent rows x rank entries, dependent rows x rank (rank - 1) / 2
+ * pairs) are small -- at most 32 pairs, or an image that does not enlarge the wave's region -- is laid out from those and not sampled
+ * (a call with only such problems has no sizing launch).  No result depends on the sample: a restart with more entries or triples than
+ * laid out is reported by the device and only that problem is laid out again (scale 2, 4, .. 32: hard bound for the entries, scale x
+ * the pairs for the table) and launched again alone.  stats->launches counts the sizing launch too, stats->candidates the search
+ * candidates, those of repeated problems again; the shape fields are the last search launch's.  Environment: PLO_BATCH_GRID and
+ * PLO_BATCH_STATS as for plo_cse_batch_search; the PLO_KMETHOD_* knobs of plo_kernel_search act on every sampled problem.
+ * PLO_E_ARG, before any use of the device: a null array, nprob == 0, per_problem == 0, an even modulus, one below 3 or of 2^31 and
+ * more, cost_mode outside 0..2, more than 2^32-1 candidates, a defective matrix. */
+int plo_kernel_batch_search(uint32_t nprob, const plo_csr_t *mats, uint32_t p, uint64_t seed0, uint32_t per_problem,
+                            int cost_mode, plo_best_t *bests, int32_t *status, plo_stats_t *stats);
+
 
 /* The kernel method of bin/optimizer -K with EVERYTHING on the device (plo::kmethod_kernel): restart c (seed seed0 + c) is one
  * pass of the loop of KernelOptimiser, include/plinopt_optimize.inl:1299-1340 -- a nullspace decomposition of M

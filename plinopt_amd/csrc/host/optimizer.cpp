@@ -228,19 +228,6 @@ template <class F> bool ab_method(const F &f, const SparseMat<typename F::Elt> &
     }, nullptr, o.verbose, prog);                                                                           // :1180-1184
 }
 
-// program text of the kernel method for one decomposition and one seed (include/plinopt_optimize.inl:836-872)
-template <class F> std::string kernel_text(const F &f, const KernelDecomp<F> &kd, uint64_t seed, Ops &ops) {
-    std::ostringstream os;
-    input2temps(os, kd.Free, 'i', 't');                                                                    // :836
-    CandRng rng(seed);
-    Replay<F> RF(f, kd.Free, rng, os, 'o', 't', 'r'); Ops fo = RF.optimizer();                             // :841
-    input2temps(os, kd.Dep, 'o', 'v');                                                                     // :859
-    Replay<F> RK(f, kd.Dep, rng, os, 'x', 'v', 'g'); Ops ko = RK.optimizer();                              // :864
-    for (size_t j = 0; j < kd.dep.size(); ++j) os << 'o' << kd.dep[j] << ":=" << 'x' << j << ";\n";       // :871-874
-    ops = {fo.first + ko.first, fo.second + ko.second};
-    return os.str();
-}
-
 // KernelOptimiser :1288-1353 with this build's decomposition rule.  The restarts are spent as blocks of --kernel-block
 // seeds: block d uses the decomposition drawn from its first seed, and every seed of the block is one run of the two
 // Optimizer calls on it (the reference draws a new decomposition for every restart; with a per-restart elimination on

@@ -856,6 +856,19 @@ template <class F> bool kernel_decomp_order(const F &f, const SparseMat<typename
     return true;
 }
 
+// program text of the kernel method for one decomposition and one seed (include/plinopt_optimize.inl:836-872)
+template <class F> std::string kernel_text(const F &f, const KernelDecomp<F> &kd, uint64_t seed, std::pair<size_t, size_t> &ops) {
+    std::ostringstream os;
+    input2temps(os, kd.Free, 'i', 't');                                                                    // :836
+    CandRng rng(seed);
+    Replay<F> RF(f, kd.Free, rng, os, 'o', 't', 'r'); const auto fo = RF.optimizer();                      // :841
+    input2temps(os, kd.Dep, 'o', 'v');                                                                     // :859
+    Replay<F> RK(f, kd.Dep, rng, os, 'x', 'v', 'g'); const auto ko = RK.optimizer();                       // :864
+    for (size_t j = 0; j < kd.dep.size(); ++j) os << 'o' << kd.dep[j] << ":=" << 'x' << j << ";\n";       // :871-874
+    ops = {fo.first + ko.first, fo.second + ko.second};
+    return os.str();
+}
+
 // cmpOpCount, include/plinopt_optimize.h:53-64 (mode 0 default, 1 OPTIMIZE_ADDITIONS, 2 OPTIMIZE_SUMS)
 inline bool cmp_op_count(std::pair<size_t, size_t> a, std::pair<size_t, size_t> b, int mode = 0) {
     if (mode == 1) return a.first < b.first || (a.first == b.first && a.second < b.second);

@@ -2,14 +2,15 @@
 // bin/pruner -- re-optimizes the sub-programs of a straight-line program: what the reference's bin/prune.sh does by
 // calling bin/mirabelle.sh (its first, "D", attempt) for every temporary variable or every ordered pair of them, as one
 // tool.  For each selection the window around it is cut out of the program, turned into a small matrix, searched by N
-// restarts of Optimizer (-D) and of the LU chain (-G), and reported when the best sub-program found is cheaper than
-// the lines it came from.  DESIGN.md 2.11 has the definition and the departures from the scripts.
+// restarts of Optimizer (-D), of the kernel method (-K) and of the LU chain (-G), and reported when the best sub-program
+// found is cheaper than the lines it came from.  DESIGN.md 2.11 has the definition and the departures from the scripts.
+// With no method flag the methods are -D -G (the reference's mirabelle.sh runs optimizer's default, -D -K -G).
 //
-//   pruner [-O N] [-q p] [-v] [-l regex] [-D] [-G] [--seed S] [--gpu 0|1] [--apply] P.slp
+//   pruner [-O N] [-q p] [-v] [-l regex] [-D] [-K] [-G] [--seed S] [--gpu 0|1] [--apply] P.slp
 //
 // With -q p (an odd prime below 2^31) and --gpu 1 all windows of a method go to the device in ONE call
-// (plo_cse_batch_search: one workgroup per window, one minimum each); a window the wave kernel refuses runs on the
-// host.  Without -q, with a larger modulus or with --gpu 0 the same definition runs on the host (OpenMP).  stdout is
+// (plo_cse_batch_search, and plo_kernel_batch_search for -K: one workgroup per window, one minimum each); a window
+// the device code refuses runs on the host.  Without -q, with a larger modulus or with --gpu 0 the same definition runs on the host (OpenMP).  stdout is
 // the same either way; statistics are `#` lines on stderr.
 // ===========================================================================
 #include "plo_host.hpp"
@@ -29,10 +30,11 @@ namespace {
 struct HipLib {
     void *h = open_hip_lib(); bool ok = h != nullptr;
     PLO_SYM(init, plo_init); PLO_SYM(last_error, plo_last_error); PLO_SYM(batch_search, plo_cse_batch_search);
+    PLO_SYM(kernel_batch_search, plo_kernel_batch_search);
 };
 
 struct Options {
-    size_t loops = 100; uint64_t q = 0, seed0 = 0; bool singles = false, direct = false, lu = false, apply = false; int gpu = 1;
+    size_t loops = 100; uint64_t q = 0, seed0 = 0; bool singles = false, direct = false, kernel = false, lu = false, apply = false; int gpu = 1;
     std::string pattern, file;
 };
 
@@ -125,6 +127,24 @@ template <class F> Ops lu_text(const F &f, const LUFactors<F> &lu, uint64_t seed
     return {uo.first + lo.first, uo.second + lo.second};
 }
 
+// -K: restart `seed` of the kernel method on M, decomposition and both Optimizer calls from that seed (plo_oracle_kernel_restart)
+template <class F> Ops kernel_restart_text(const F &f, const SparseMat<typename F::Elt> &M, uint64_t seed, std::ostream &os) {
+    KernelDecomp<F> kd; Ops ops{0, 0};
+    if (!kernel_decomp(f, M, seed, kd)) throw std::runtime_error("zero dimensional kernel");      // (decided once per window: the rank does not depend on the order)
+    os << kernel_text(f, kd, seed, ops);
+    return ops;
+}
+// The replay of the kernel method defines a dependent output twice (`o3:=0;` from Free's emptied row, later `o3:=x0;`; nothing reads
+// it in between: Dep's columns are basis rows): the text with the last definition of every variable only
+std::string last_definitions(const std::string &text) {
+    std::vector<std::string> lines; std::istringstream is(text); std::string line;
+    while (std::getline(is, line)) lines.push_back(line);
+    std::set<std::string> later; std::vector<bool> keep(lines.size(), true);
+    for (size_t k = lines.size(); k-- > 0;) { const auto c = lines[k].find(":="); if (c != std::string::npos && !later.insert(lines[k].substr(0, c)).second) keep[k] = false; }
+    std::string out; for (size_t k = 0; k < lines.size(); ++k) if (keep[k]) out += lines[k] + "\n";
+    return out;
+}
+
 // A replayed program without its copies (`t0:=i0;`), zero lines and temporaries nothing reads, in token lines
 std::vector<std::vector<std::string>> tidy(const std::string &text) {
     std::vector<std::vector<std::string>> lines; std::istringstream is(text); std::string line;
@@ -147,7 +167,7 @@ std::vector<std::vector<std::string>> tidy(const std::string &text) {
     return keep;
 }
 
-struct Result { Best d, g; bool improved = false; Ops after{0, 0}; std::vector<std::vector<std::string>> repl; };    // repl: the replacement in the program's names
+struct Result { Best d, k, g; bool improved = false; Ops after{0, 0}; std::vector<std::vector<std::string>> repl; };    // repl: the replacement in the program's names
 
 template <class F> int run(const F &f, const Options &o, const std::vector<PLine> &P) {
     using Mat = SparseMat<typename F::Elt>;
@@ -175,6 +195,14 @@ template <class F> int run(const F &f, const Options &o, const std::vector<PLine
     std::vector<Mat> mats(nw); std::vector<LUFactors<F>> lus(nw);
 #pragma omp parallel for schedule(dynamic, 8)
     for (long long w = 0; w < (long long)nw; ++w) { mats[w] = window_matrix(f, P, wins[w]); if (o.lu) lus[w] = sparse_lu(f, mats[w]); }
+    // -K: the windows whose matrix has a kernel of positive dimension
+    std::vector<size_t> with_kernel;
+    if (o.kernel) {
+        std::vector<char> has(nw, 0);
+#pragma omp parallel for schedule(dynamic, 8)
+        for (long long w = 0; w < (long long)nw; ++w) { KernelDecomp<F> kd; has[w] = kernel_decomp(f, mats[w], o.seed0 + (uint64_t)w * o.loops, kd) ? 1 : 0; }
+        for (size_t w = 0; w < nw; ++w) if (has[w]) with_kernel.push_back(w);
+    }
     std::clog << "# windows: " << nw << " kept, " << skipped << " skipped (no output); " << N << " restarts per window and method" << std::endl;
 
     // ---- search: window w uses the seeds seed0 + w*N + j
@@ -185,41 +213,45 @@ template <class F> int run(const F &f, const Options &o, const std::vector<PLine
             const size_t w = which[k]; Best b;
             for (size_t j = 0; j < N; ++j) {
                 std::ostringstream sink; const uint64_t seed = o.seed0 + w * N + j;
-                b.offer(method == 'D' ? direct_text(f, mats[w], seed, sink) : lu_text(f, lus[w], seed, sink), seed);
+                b.offer(method == 'D' ? direct_text(f, mats[w], seed, sink) : method == 'K' ? kernel_restart_text(f, mats[w], seed, sink) : lu_text(f, lus[w], seed, sink), seed);
             }
-            (method == 'D' ? res[w].d : res[w].g) = b;
+            (method == 'D' ? res[w].d : method == 'K' ? res[w].k : res[w].g) = b;
         }
     };
     std::vector<size_t> all(nw); for (size_t w = 0; w < nw; ++w) all[w] = w;
     bool on_gpu = false;
     if constexpr (std::is_same<F, ZpField>::value) on_gpu = o.gpu > 0 && nw > 0 && N > 0;
-    for (char method : {'D', 'G'}) {
-        if (!(method == 'D' ? o.direct : o.lu)) continue;
-        std::vector<size_t> host = all;
-        if constexpr (std::is_same<F, ZpField>::value) if (on_gpu) {
+    for (char method : {'D', 'K', 'G'}) {
+        if (!(method == 'D' ? o.direct : method == 'K' ? o.kernel : o.lu)) continue;
+        const std::vector<size_t> &mine = method == 'K' ? with_kernel : all;          // the windows of this method
+        std::vector<size_t> host = mine;
+        if constexpr (std::is_same<F, ZpField>::value) if (on_gpu && !mine.empty()) {
             static HipLib L;                                                              // no silent fallback: --gpu 0 selects the host loop
             if (!L.ok) { std::cerr << "# \033[1;31mERROR: cannot use the GPU: library missing\033[0m" << std::endl; return 2; }
             if (L.init(0) != PLO_OK) { std::cerr << "# \033[1;31mERROR: cannot use the GPU: " << L.last_error() << "\033[0m" << std::endl; return 2; }
             std::vector<Csr> A, B; std::vector<plo_csr_t> va, vb;
+            // (-K too passes every window, so that problem w has the seeds seed0 + w*N + j of the other methods: a window without a kernel is refused by its rank
+            // on the host side of the call, before anything of it reaches the device)
             for (size_t w = 0; w < nw; ++w) {
-                if (method == 'D') A.push_back(csr(mats[w])); else { A.push_back(csr(lus[w].U)); B.push_back(csr(lus[w].L)); }
+                if (method == 'G') { A.push_back(csr(lus[w].U)); B.push_back(csr(lus[w].L)); } else A.push_back(csr(mats[w]));
             }
             for (auto &c : A) va.push_back(c.view());
             for (auto &c : B) vb.push_back(c.view());
             std::vector<plo_best_t> bests(nw); std::vector<int32_t> status(nw); plo_stats_t st{};
             const auto t0 = std::chrono::steady_clock::now();
-            const int rc = L.batch_search((uint32_t)nw, va.data(), method == 'D' ? nullptr : vb.data(), (uint32_t)o.q, o.seed0, (uint32_t)N, PLO_COST_SUM_THEN_ADD, bests.data(), status.data(), &st);
+            const int rc = method == 'K' ? L.kernel_batch_search((uint32_t)nw, va.data(), (uint32_t)o.q, o.seed0, (uint32_t)N, PLO_COST_SUM_THEN_ADD, bests.data(), status.data(), &st)
+                                         : L.batch_search((uint32_t)nw, va.data(), method == 'D' ? nullptr : vb.data(), (uint32_t)o.q, o.seed0, (uint32_t)N, PLO_COST_SUM_THEN_ADD, bests.data(), status.data(), &st);
             const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             if (rc != PLO_OK) { std::cerr << "# \033[1;31mERROR: -" << method << " GPU search failed: " << L.last_error() << "\033[0m" << std::endl; return 2; }
             host.clear();
-            for (size_t w = 0; w < nw; ++w) {
+            for (size_t w : mine) {
                 if (status[w] != PLO_OK) { host.push_back(w); continue; }
-                Best b; b.offer({bests[w].adds, bests[w].muls}, bests[w].seed); (method == 'D' ? res[w].d : res[w].g) = b;
+                Best b; b.offer({bests[w].adds, bests[w].muls}, bests[w].seed); (method == 'D' ? res[w].d : method == 'K' ? res[w].k : res[w].g) = b;
             }
-            std::clog << "# GPU: -" << method << " one plo_cse_batch_search call over " << nw << " windows: " << st.candidates << " candidates, " << st.launches << " launches, kernel "
+            std::clog << "# GPU: -" << method << " one " << (method == 'K' ? "plo_kernel_batch_search" : "plo_cse_batch_search") << " call over " << mine.size() << " windows: " << st.candidates << " candidates, " << st.launches << " launches, kernel "
                       << st.kernel_ms << " ms, wall " << wall << " s (" << (wall > 0 ? 100.0 * (wall - st.kernel_ms / 1000.0) / wall : 0.0) << " % on the host), "
                       << (wall > 0 ? st.candidates / wall : 0.0) << " candidates/s" << std::endl;
-            if (!host.empty()) std::clog << "# refused: -" << method << " " << host.size() << " windows the wave kernel does not take run on the host" << std::endl;
+            if (!host.empty()) std::clog << "# refused: -" << method << " " << host.size() << " windows the " << (method == 'K' ? "kernel-method" : "wave") << " kernel does not take run on the host" << std::endl;
         }
         const auto t0 = std::chrono::steady_clock::now();
         host_search(method, host);
@@ -235,15 +267,18 @@ template <class F> int run(const F &f, const Options &o, const std::vector<PLine
 #pragma omp parallel for schedule(dynamic, 8)
     for (long long w = 0; w < (long long)nw; ++w) {
         Result &R = res[w]; const Window &W = wins[w];
-        const bool useg = R.g.have && (!R.d.have || cmp_op_count(R.g.ops, R.d.ops));
-        const Best &b = useg ? R.g : R.d;
+        // best of D, K, G under cmpOpCount, the earlier method winning ties
+        char use = 'D'; const Best *pb = &R.d;
+        if (R.k.have && (!pb->have || cmp_op_count(R.k.ops, pb->ops))) { use = 'K'; pb = &R.k; }
+        if (R.g.have && (!pb->have || cmp_op_count(R.g.ops, pb->ops))) { use = 'G'; pb = &R.g; }
+        const Best &b = *pb;
         if (!b.have) continue;
         R.after = b.ops;
         R.improved = b.ops.first + b.ops.second < W.before.first + W.before.second;
         if (!R.improved) continue;
         std::ostringstream os;
-        const Ops ops = useg ? lu_text(f, lus[w], b.seed, os) : direct_text(f, mats[w], b.seed, os);
-        auto lines = tidy(os.str());
+        const Ops ops = use == 'G' ? lu_text(f, lus[w], b.seed, os) : use == 'K' ? kernel_restart_text(f, mats[w], b.seed, os) : direct_text(f, mats[w], b.seed, os);
+        auto lines = tidy(use == 'K' ? last_definitions(os.str()) : os.str());
         std::string plain; for (auto &tk : lines) plain += text_of(tk);
         SlpEval<F> ev(f); std::istringstream is(plain); ev.run(is);
         if (ops != b.ops || !same_matrix(f, ev.matrix('o', mats[w].rowdim(), mats[w].coldim()), mats[w])) {
@@ -267,6 +302,7 @@ template <class F> int run(const F &f, const Options &o, const std::vector<PLine
             const Window &W = wins[w]; const Result &R = res[w];
             std::cout << W.label() << " [" << W.out.size() << 'x' << W.in.size() << "]: " << W.before.first << '|' << W.before.second;
             if (R.d.have) std::cout << " D " << R.d.ops.first << '|' << R.d.ops.second << " [seed " << R.d.seed << ']';
+            if (R.k.have) std::cout << " K " << R.k.ops.first << '|' << R.k.ops.second << " [seed " << R.k.seed << ']';
             if (R.g.have) std::cout << " G " << R.g.ops.first << '|' << R.g.ops.second << " [seed " << R.g.seed << ']';
             const long dif = (long)(W.before.first + W.before.second) - (long)(R.after.first + R.after.second);      // mirabelle.sh:139-175
             if (R.improved) std::cout << " IMPROVEMENT";
@@ -335,12 +371,14 @@ int main(int argc, char **argv)
         else if (a == "--gpu" && more()) o.gpu = atoi(argv[++i]);
         else if (a == "-v") o.singles = true;
         else if (a == "-D") o.direct = true;
+        else if (a == "-K") o.kernel = true;
         else if (a == "-G") o.lu = true;
         else if (a == "--apply") o.apply = true;
-        else if (a[0] == '-') { std::clog << "Usage: " << argv[0] << " [-O N] [-q p] [-v] [-l regex] [-D] [-G] [--seed S] [--gpu 0|1] [--apply] P.slp\n"; return a == "-h" ? 0 : 2; }
+        else if (a[0] == '-') { std::clog << "Usage: " << argv[0] << " [-O N] [-q p] [-v] [-l regex] [-D] [-K] [-G] [--seed S] [--gpu 0|1] [--apply] P.slp\n"
+                                            "  methods: -D Optimizer, -K kernel method, -G LU chain; none given: -D -G (the reference's scripts run -D -K -G)\n"; return a == "-h" ? 0 : 2; }
         else o.file = a;
     }
-    if (!o.direct && !o.lu) o.direct = o.lu = true;
+    if (!o.direct && !o.kernel && !o.lu) o.direct = o.lu = true;
     if (o.gpu < 0 || o.gpu > 1) { std::cerr << "# \033[1;31mERROR: --gpu takes 0 or 1 (one device)\033[0m" << std::endl; return 2; }
     try {
         std::ifstream in(o.file);

@@ -9,6 +9,7 @@
 #include "plo_cse_wave.hip"
 #include "plo_cse_batch.hip"
 #include "plo_kmethod.hip"
+#include "plo_kmethod_batch.hip"
 #include "plo_cse_big.hip"
 #include "plo_cob.hip"
 #include "plo_tril.hip"
@@ -1511,6 +1512,13 @@ struct BatchSlot {
 // Buckets of plo_cse_batch_search by that footprint: up to 4, 8, 16, 32, 64 KiB and the rest of the LDS
 constexpr uint32_t BATCH_BUCKETS = 6;
 uint32_t batch_bucket(uint32_t foot) { uint32_t b = 0; while (b + 1 < BATCH_BUCKETS && foot > (4096u << b)) ++b; return b; }
+// Waves per workgroup of the batch kernels: 8, 4, 2 or 1, the most whose need(w) bytes fit the LDS -- the waves of a workgroup are all the parallelism one problem
+// gets -- and no more than twice its candidates
+template <class Need> uint32_t batch_waves(Need need, uint32_t per_problem, size_t lds_max) {
+    uint32_t W = 8;
+    while (W > 1u && (need(W) > lds_max || W / 2u >= per_problem)) W /= 2u;
+    return W;
+}
 
 // fn(k) for 0 <= k < n on host threads (no OpenMP runtime in this library: the callers bring their own)
 template <class Fn> void on_host_threads(size_t n, Fn fn) {
@@ -1623,12 +1631,10 @@ int plo_cse_batch_search(uint32_t nprob, const plo_csr_t *firsts, const plo_csr_
                 }
                 const size_t count = b1 - b0;
                 J.nprob = (uint32_t)count;
-                // Waves per workgroup: 8, 4, 2 or 1, the most that fit the LDS -- the waves of a workgroup are all the parallelism one problem gets -- and
-                // no more than twice its candidates.  One workgroup per problem, handed out by the hardware as workgroups retire, so that cheap and dear
+                // Waves per workgroup: batch_waves.  One workgroup per problem, handed out by the hardware as workgroups retire, so that cheap and dear
                 // problems balance themselves; the stride loop of the kernel only turns under the grid knob (and past 2^31 - 1 problems).
                 const auto need = [&](uint32_t w) { return 64u + J.rs1max + J.rs2max + w * J.region; };
-                uint32_t W = 8;
-                while (W > 1u && (need(W) > lds_max || W / 2u >= per_problem)) W /= 2u;
+                const uint32_t W = batch_waves(need, per_problem, lds_max);
                 const uint32_t lds = need(W);
                 uint32_t per_cu = 1;
                 if (const int rc = occupancy_for((const void *)plo::cse_batch_kernel, W, lds, &per_cu)) return rc;
@@ -1759,12 +1765,28 @@ uint32_t kmethod_scratch_layout(plo::KPlan &K, uint32_t depc_bytes, bool depc_in
     return K.off_vc + K.m * (K.n + 1u + K.rank + 1u) * 4u;
 }
 
+// A wave's region for a sizing launch, before Dep is laid out: M's image, the elimination arrays and, behind them, the combinations
+void kmethod_sizing_region(plo::KPlan &K, uint32_t vc_end, uint32_t depc_bytes, bool depc_inside) {
+    K.region = round_up(std::max(K.PM.region_bytes, vc_end), 16);
+    if (depc_inside) { const uint32_t at = K.region; K.region = at + depc_bytes; K.off_depc = -(int32_t)depc_bytes; }
+}
+// k when p = 2^k - 1, else 0 (KPlan::mers)
+uint32_t mersenne_exponent(uint32_t p) { for (uint32_t k = 2; k < 31; ++k) if (p == (1u << k) - 1u) return k; return 0; }
+// rank and dependent rows of M modulo p, and what the kernel method's device code refuses of them
+int kmethod_ranks(const plo_csr_t *M, uint32_t p, uint32_t *R, uint32_t *ndeps) {
+    *R = rank_mod_p(M, p); *ndeps = M->m - *R;
+    if (*ndeps == 0) return fail(PLO_E_UNSUPPORTED, "zero dimensional kernel");
+    if (*ndeps > 64) return fail(PLO_E_UNSUPPORTED, "more than 64 dependent rows: Dep's ProgramGen keeps one row per lane");
+    if (*R == 0) return fail(PLO_E_UNSUPPORTED, "zero matrix");
+    return PLO_OK;
+}
+const char *const KMETHOD_SHAPE = "device decomposition needs at most 128 rows and 64 columns";
+
 // The sizing launch: Dep's pair count and entries, maxima over a sample of the decompositions
 // (ord: the walk over prescribed row orders -- the sample is `norders` orders at equal distances over the whole range of the call)
 int kmethod_sample(plo::KPlan &K, uint64_t seed0, uint64_t nrestarts, uint32_t vc_end, uint32_t depc_bytes, bool depc_inside, plo_stats_t *st, uint32_t *pairs_max, uint32_t *ent_max,
                    const plo::KOrd *ord = nullptr, uint64_t norders = 0) {
-    K.region = round_up(std::max(K.PM.region_bytes, vc_end), 16);
-    if (depc_inside) { const uint32_t at = K.region; K.region = at + depc_bytes; K.off_depc = -(int32_t)depc_bytes; }
+    kmethod_sizing_region(K, vc_end, depc_bytes, depc_inside);
     uint32_t lds = 0;
     const uint32_t W = pick_waves([&](uint32_t w) { return K.PM.rs_bytes + w * (K.region + K.scratch_bytes); }, false, g_lds_max, &lds);
     if (!W) return fail(PLO_E_CAPACITY, "kernel-method state does not fit LDS");
@@ -1824,10 +1846,8 @@ int kernel_search_run(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t t
 {
     CallScope call(st); st = call.st;
     if (best) { best->adds = best->muls = 0xFFFFFFFFu; best->seed = ~0ull; }
-    const uint32_t m = M->m, n = M->n, R = rank_mod_p(M, p), ndeps = m - R;
-    if (ndeps == 0) return fail(PLO_E_UNSUPPORTED, "zero dimensional kernel");
-    if (ndeps > 64) return fail(PLO_E_UNSUPPORTED, "more than 64 dependent rows: Dep's ProgramGen keeps one row per lane");
-    if (R == 0) return fail(PLO_E_UNSUPPORTED, "zero matrix");
+    const uint32_t m = M->m, n = M->n; uint32_t R = 0, ndeps = 0;
+    if (const int rc = kmethod_ranks(M, p, &R, &ndeps)) return rc;
 
     const KmKnobs knobs;
     const uint32_t depc_bytes = round_up(ndeps * R * 4u, 16);
@@ -1849,7 +1869,7 @@ int kernel_search_run(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t t
         int rc = build_plan(&tmp, &img);
         if (rc != PLO_OK) return rc;
         K.PM = tmp.P; K.m = m; K.n = n; K.rank = R; K.ndeps = ndeps; K.per_block = per_block;
-        K.mers = 0; for (uint32_t kk = 2; kk < 31; ++kk) if (p == (1u << kk) - 1u) K.mers = kk;
+        K.mers = mersenne_exponent(p);
         const uint32_t vc_end = kmethod_scratch_layout(K, depc_bytes, depc_inside);
         HIPCHK(hipMalloc((void **)&d_img.p, img.size() + 64)); HIPCHK(hipMemcpy(d_img, img.data(), img.size(), hipMemcpyHostToDevice));
         K.PM.tmpl = (const uint64_t *)d_img.p;
@@ -1912,7 +1932,7 @@ int plo_kernel_search(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint64_t n
     if (const int rc = require_device(NOINIT_CSE)) return rc;
     if (p < 3 || p >= 0x80000000u || !(p & 1u)) return fail(PLO_E_ARG, "modulus must be an odd prime below 2^31");
     if (const char *bad = csr_defect(M, p)) return fail(PLO_E_ARG, bad);
-    if (M->m == 0 || M->m > 128 || M->n == 0 || M->n > 64) return fail(PLO_E_UNSUPPORTED, "device decomposition needs at most 128 rows and 64 columns");
+    if (M->m == 0 || M->m > 128 || M->n == 0 || M->n > 64) return fail(PLO_E_UNSUPPORTED, KMETHOD_SHAPE);
     if (nrestarts > 0xFFFFFFFFull) return fail(PLO_E_ARG, "at most 2^32-1 restarts per call");
     return kernel_search_run(M, p, seed0, nrestarts, nrestarts, per_block, cost_mode, adds, muls, info, best, st, nullptr);
 }
@@ -1928,11 +1948,200 @@ int plo_kernel_search_orders(const plo_csr_t *M, uint32_t p, uint64_t seed0, uin
     if (const int rc = require_device(NOINIT_CSE)) return rc;
     if (p < 3 || p >= 0x80000000u || !(p & 1u)) return fail(PLO_E_ARG, "modulus must be an odd prime below 2^31");
     if (const char *bad = csr_defect(M, p)) return fail(PLO_E_ARG, bad);
-    if (M->n == 0 || M->n > 64) return fail(PLO_E_UNSUPPORTED, "device decomposition needs at most 128 rows and 64 columns");
+    if (M->n == 0 || M->n > 64) return fail(PLO_E_UNSUPPORTED, KMETHOD_SHAPE);
     // launches of at most 2^25 candidates (the device packs key << 32 | candidate, and no launch should hold a shared device for long); PLO_KORD_CHUNK: test knob, fewer
     const uint64_t chunk = (uint64_t)std::min<long>(std::max<long>(env_knob("PLO_KORD_CHUNK").value_or(1l << 25), 1l), 1l << 25);
     const KOrdReq ord{first, count, sub};
     return kernel_search_run(M, p, seed0, count * sub, chunk, 1u, cost_mode, adds, muls, info, best, st, &ord);
+}
+
+} // extern "C"
+namespace {
+// Host side of one problem of plo_kernel_batch_search
+struct KmSlot {
+    uint32_t scale = 1;                  // 1: Dep's image from the sample of the sizing launch; 2, 4, .. 32: the hard bound for its entries and scale x the pairs for its
+                                         // table, M's table by max(2, scale) -- the growth rule of kernel_search_run, per problem
+    bool fixed = false;                  // Dep from the hard bounds from the start (scale 2): no sample, never short of entries, and the knobs of the sample do not reach it
+    uint32_t R = 0, ndeps = 0, depc_bytes = 0, vc_end = 0, pairs_max = 0, ent_max = 0;
+    plo::KPlan K{};
+    std::vector<uint8_t> img; size_t img_off = 0;
+    int rc = PLO_OK; std::string why;
+};
+// rank (once), plan and image of M at S.scale and the scratch layout; S.rc / S.why: what plo_kernel_search would refuse
+void kbatch_build(KmSlot &S, const plo_csr_t *M, uint32_t p, bool depc_inside)
+{
+    S.rc = PLO_OK; S.why.clear();
+    if (S.R + S.ndeps == 0) {
+        if (M->m == 0 || M->m > 128 || M->n == 0 || M->n > 64) { S.rc = PLO_E_UNSUPPORTED; S.why = KMETHOD_SHAPE; return; }
+        if ((S.rc = kmethod_ranks(M, p, &S.R, &S.ndeps)) != PLO_OK) { S.why = g_err; return; }
+        S.depc_bytes = round_up(S.ndeps * S.R * 4u, 16);
+    }
+    plo_plan tmp; tmp.cap_scale = std::max(2u, S.scale);
+    set_matrix(&tmp, M, p);
+    if ((S.rc = build_plan(&tmp, &S.img)) != PLO_OK) { S.why = g_err; return; }
+    plo::KPlan &K = S.K;
+    K = plo::KPlan{};
+    K.PM = tmp.P; K.m = M->m; K.n = M->n; K.rank = S.R; K.ndeps = S.ndeps; K.per_block = 1u; K.mers = mersenne_exponent(p);
+    S.vc_end = kmethod_scratch_layout(K, S.depc_bytes, depc_inside);
+    kmethod_sizing_region(K, S.vc_end, S.depc_bytes, depc_inside);
+}
+} // namespace
+extern "C" {
+
+// The kernel method on many matrices in one call, one minimum each (plo::kmethod_batch_kernel, one workgroup per problem).
+// The sizing launch decomposes the first min(per_problem, 64) of each problem's own restarts; a problem whose hard bounds are small
+// (at most 32 pairs: the 64-slot minimum table holds them; or an image that does not enlarge the wave's region) is laid out from those
+// and not sampled.  Results do not depend on either: a restart with more entries or triples than laid out reports ERR_TABLE and the
+// problem is run again with the next scale.
+int plo_kernel_batch_search(uint32_t nprob, const plo_csr_t *mats, uint32_t p, uint64_t seed0, uint32_t per_problem,
+                            int cost_mode, plo_best_t *bests, int32_t *status, plo_stats_t *st)
+{
+    if (!mats || !bests || !status || nprob == 0 || per_problem == 0) return fail(PLO_E_ARG, "bad argument");
+    if (cost_mode < 0 || cost_mode > 2) return fail(PLO_E_ARG, "unknown cost mode");
+    if (p < 3 || p >= 0x80000000u || !(p & 1u)) return fail(PLO_E_ARG, "modulus must be an odd prime below 2^31");
+    if ((uint64_t)nprob * per_problem > 0xFFFFFFFFull) return fail(PLO_E_ARG, "at most 2^32-1 candidates per call");
+    for (uint32_t q = 0; q < nprob; ++q)
+        if (const char *bad = csr_defect(&mats[q], p)) return fail(PLO_E_ARG, "problem " + std::to_string(q) + ": " + bad);
+    if (const int rc = require_device(NOINIT_CSE)) return rc;
+    CallScope call(st); st = call.st;
+    for (uint32_t q = 0; q < nprob; ++q) { bests[q].adds = bests[q].muls = 0xFFFFFFFFu; bests[q].seed = ~0ull; status[q] = PLO_OK; }
+    const KmKnobs knobs;
+    const bool depc_inside = !knobs.depc_scratch;
+    const std::optional<long> grid_cap = env_knob("PLO_BATCH_GRID");
+    const bool batch_stats = env_knob("PLO_BATCH_STATS").has_value();
+    const size_t lds_max = g_lds_max;
+    const uint32_t nsample = std::min(per_problem, 64u);
+    DevBuf<unsigned long long> d_keys; DevBuf<uint32_t> d_adds, d_muls, d_err;
+    HIPCHK(hipMalloc((void **)&d_keys.p, nprob * 8ull)); HIPCHK(hipMalloc((void **)&d_adds.p, nprob * 4ull));
+    HIPCHK(hipMalloc((void **)&d_muls.p, nprob * 4ull)); HIPCHK(hipMalloc((void **)&d_err.p, nprob * 4ull));
+    HIPCHK(hipMemsetAsync(d_keys, 0xFF, nprob * 8ull, g_stream));
+    std::vector<KmSlot> S(nprob);
+    std::vector<uint32_t> todo(nprob), err(nprob);
+    for (uint32_t q = 0; q < nprob; ++q) todo[q] = q;
+    const auto slot_of = [&](uint32_t q) { return S[q].K.region + S[q].K.scratch_bytes; };
+    const auto fits = [&](uint32_t q) { return 64ull + S[q].K.PM.rs_bytes + slot_of(q) <= lds_max; };
+    for (bool first = true; !todo.empty(); first = false) {
+        on_host_threads(todo.size(), [&](size_t k) { const uint32_t q = todo[k]; kbatch_build(S[q], &mats[q], p, depc_inside); });
+        std::vector<uint32_t> live;
+        size_t total = 0;
+        for (const uint32_t q : todo) {
+            if (S[q].rc == PLO_OK && !fits(q)) { S[q].rc = PLO_E_CAPACITY; S[q].why = "kernel-method state does not fit LDS"; }
+            if (S[q].rc == PLO_E_CAPACITY || S[q].rc == PLO_E_UNSUPPORTED) { status[q] = S[q].rc; continue; }     // this problem alone is refused
+            if (S[q].rc != PLO_OK) return fail(S[q].rc, "problem " + std::to_string(q) + ": " + S[q].why);
+            S[q].img_off = total; total += round_up((uint32_t)S[q].img.size(), 64);
+            live.push_back(q);
+        }
+        if (live.empty()) break;
+        // one device buffer for the images of M of all problems
+        std::vector<uint8_t> blob(total + 64, 0);
+        for (const uint32_t q : live) std::memcpy(blob.data() + S[q].img_off, S[q].img.data(), S[q].img.size());
+        DevBuf<uint8_t> d_img;
+        HIPCHK(hipMalloc((void **)&d_img.p, blob.size()));
+        HIPCHK(hipMemcpy(d_img, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        // The launches over `order`, none across a boundary of `cuts`: one per stretch, unless the largest row starts and the largest slot -- of different problems --
+        // no longer fit the LDS together (each problem alone fits).  sizing: the decompositions of the sample into d_sz, else the search.
+        uint32_t *d_sz = nullptr;
+        const auto run = [&](const std::vector<uint32_t> &order, const std::vector<size_t> &cuts, bool sizing) -> int {
+            std::vector<plo::KBatchProb> probs(order.size());
+            for (size_t k = 0; k < order.size(); ++k) { probs[k].K = S[order[k]].K; probs[k].K.PM.tmpl = (const uint64_t *)(d_img.p + S[order[k]].img_off); probs[k].q = order[k]; }
+            DevBuf<plo::KBatchProb> d_probs;
+            HIPCHK(hipMalloc((void **)&d_probs.p, probs.size() * sizeof(plo::KBatchProb)));
+            HIPCHK(hipMemcpy(d_probs, probs.data(), probs.size() * sizeof(plo::KBatchProb), hipMemcpyHostToDevice));
+            const void *fn = sizing ? (const void *)plo::kmethod_batch_size_kernel : (const void *)plo::kmethod_batch_kernel;
+            for (size_t c = 0; c + 1 < cuts.size(); ++c)
+                for (size_t b0 = cuts[c], b1; b0 < cuts[c + 1]; b0 = b1) {
+                    plo::KBatchJob J{}; J.probs = d_probs.p + b0; J.per = per_problem; J.nsample = nsample; J.cost_mode = (uint32_t)cost_mode; J.seed0 = seed0;
+                    J.keys = d_keys; J.adds = d_adds; J.muls = d_muls; J.err = d_err; J.sz = d_sz;
+                    for (b1 = b0; b1 < cuts[c + 1]; ++b1) {
+                        const uint32_t rs = std::max(J.rsmax, S[order[b1]].K.PM.rs_bytes), sl = std::max(J.slot, slot_of(order[b1]));
+                        if (b1 > b0 && 64ull + rs + sl > lds_max) break;
+                        J.rsmax = rs; J.slot = sl;
+                    }
+                    const size_t count = b1 - b0;
+                    J.nprob = (uint32_t)count;
+                    const auto need = [&](uint32_t w) { return 64u + J.rsmax + w * J.slot; };
+                    const uint32_t W = batch_waves(need, sizing ? nsample : per_problem, lds_max), lds = need(W);
+                    uint32_t per_cu = 1;
+                    if (const int rc = occupancy_for(fn, W, lds, &per_cu)) return rc;
+                    uint64_t grid = std::min<uint64_t>(count, 0x7FFFFFFFull);
+                    if (grid_cap && *grid_cap > 0) grid = std::min<uint64_t>(grid, (uint64_t)*grid_cap);
+                    const LaunchShape shape{grid, lds, W, 0};
+                    const double ms0 = st->kernel_ms;
+                    const int rc = timed_launch(st, sizing ? nullptr : &shape, [&] {
+                        if (sizing) hipLaunchKernelGGL(plo::kmethod_batch_size_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, J);
+                        else hipLaunchKernelGGL(plo::kmethod_batch_kernel, dim3((uint32_t)grid), dim3(W * 64), lds, g_stream, J);
+                    });
+                    if (rc != PLO_OK) return rc;
+                    if (batch_stats) fprintf(stderr, "# kernel batch: %s, scale %u: %zu problems, %u waves per workgroup, %u LDS bytes, %u workgroups per CU, grid %llu, %.3f ms\n",
+                                             sizing ? "sizing" : "search", S[order[b0]].scale, count, W, lds, per_cu, (unsigned long long)grid, st->kernel_ms - ms0);
+                    if (!sizing) st->candidates += (uint64_t)count * per_problem;
+                }
+            return PLO_OK;
+        };
+        if (first) {
+            // who is sampled: not the problems whose hard bounds (ndeps x rank entries, ndeps x rank (rank - 1) / 2 pairs) are small
+            std::vector<uint32_t> sampled;
+            for (const uint32_t q : live) {
+                KmSlot &X = S[q];
+                const uint32_t hard_ent = X.ndeps * X.R, hard_pairs = X.ndeps * X.R * (X.R - 1u) / 2u;
+                plo::KPlan T = X.K;
+                X.fixed = kmethod_dep_layout(T, knobs, 2, hard_pairs, hard_ent, X.vc_end, X.depc_bytes, depc_inside) == PLO_OK
+                          && (hard_pairs <= 32u || T.region <= X.K.region);
+                if (X.fixed) { X.scale = 2; X.pairs_max = hard_pairs; X.ent_max = hard_ent; } else sampled.push_back(q);
+            }
+            if (!sampled.empty()) {
+                DevBuf<uint32_t> sz;
+                HIPCHK(hipMalloc((void **)&sz.p, nprob * 16ull)); HIPCHK(hipMemsetAsync(sz, 0, nprob * 16ull, g_stream));
+                d_sz = sz.p;
+                if (const int rc = run(sampled, {0, sampled.size()}, true)) return rc;
+                std::vector<uint32_t> h(nprob * 4ull);
+                HIPCHK(hipMemcpy(h.data(), sz, nprob * 16ull, hipMemcpyDeviceToHost));
+                d_sz = nullptr;
+                for (const uint32_t q : sampled) {
+                    if (h[4u * q + 2u]) { status[q] = PLO_E_INTERNAL; continue; }      // ERR_KDEC: a decomposition that contradicts the host's rank
+                    S[q].pairs_max = h[4u * q]; S[q].ent_max = h[4u * q + 1u];
+                    if (knobs.pairs_div) S[q].pairs_max /= (uint32_t)std::max(1l, *knobs.pairs_div);   // test knob: undersized first table, as in kernel_search_run
+                }
+            }
+        }
+        // Dep's image and the wave's region of every problem at its scale, then the buckets by footprint (row starts + region + scratch)
+        std::vector<uint32_t> bucket[BATCH_BUCKETS];
+        for (const uint32_t q : live) {
+            if (status[q] != PLO_OK) continue;
+            KmSlot &X = S[q];
+            const int rc = kmethod_dep_layout(X.K, knobs, X.scale, X.pairs_max, X.ent_max, X.vc_end, X.depc_bytes, depc_inside);
+            if (rc == PLO_OK && !fits(q)) { status[q] = PLO_E_CAPACITY; continue; }
+            if (rc == PLO_E_CAPACITY) { status[q] = rc; continue; }
+            if (rc != PLO_OK) return fail(rc, "problem " + std::to_string(q) + ": " + g_err);
+            bucket[batch_bucket(X.K.PM.rs_bytes + slot_of(q))].push_back(q);
+        }
+        std::vector<uint32_t> order; std::vector<size_t> cuts{0};
+        for (const auto &b : bucket) if (!b.empty()) { order.insert(order.end(), b.begin(), b.end()); cuts.push_back(order.size()); }
+        if (order.empty()) break;
+        HIPCHK(hipMemsetAsync(d_err, 0, nprob * 4ull, g_stream));
+        if (const int rc = run(order, cuts, false)) return rc;
+        HIPCHK(hipMemcpy(err.data(), d_err, nprob * 4ull, hipMemcpyDeviceToHost));
+        // a full table or more entries of Dep than laid out is that problem's alone: only those are laid out again, with the next scale, and launched again
+        std::vector<uint32_t> next;
+        for (const uint32_t q : order) {
+            if (!err[q]) continue;
+            if (err[q] == plo::ERR_KDEC) { status[q] = PLO_E_INTERNAL; continue; }
+            if (err[q] != plo::ERR_TABLE) { const int rc = device_error((int)err[q]); return fail(rc, "problem " + std::to_string(q) + ": " + g_err); }
+            if (S[q].scale >= 32u) { status[q] = PLO_E_CAPACITY; continue; }
+            S[q].scale *= 2u; next.push_back(q);
+        }
+        todo = std::move(next);
+    }
+    std::vector<unsigned long long> keys(nprob); std::vector<uint32_t> adds(nprob), muls(nprob);
+    HIPCHK(hipMemcpy(keys.data(), d_keys, nprob * 8ull, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(adds.data(), d_adds, nprob * 4ull, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(muls.data(), d_muls, nprob * 4ull, hipMemcpyDeviceToHost));
+    for (uint32_t q = 0; q < nprob; ++q) {
+        if (status[q] != PLO_OK) continue;
+        if (keys[q] == ~0ull) return fail(PLO_E_INTERNAL, "problem " + std::to_string(q) + ": no result");
+        bests[q].adds = adds[q]; bests[q].muls = muls[q]; bests[q].seed = seed0 + (uint64_t)q * per_problem + (keys[q] & 0xFFFFFFFFull);
+    }
+    return call.done(PLO_OK);
 }
 
 } // extern "C"

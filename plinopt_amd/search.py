@@ -235,6 +235,24 @@ def kernel_search_orders(M, p, seed0, first, count, sub=1, cost_mode=capi.COST_S
     return (list(adds[:nc]) if want_costs else None), (list(muls[:nc]) if want_costs else None), inf, (b.adds, b.muls, b.seed), st.as_dict()
 
 
+def kernel_batch_search(mats, p, seed0, per_problem, cost_mode=capi.COST_SUM_THEN_ADD):
+    """The kernel method on many matrices in one call (`plo_kernel_batch_search`): mats = [(m,n,rowptr,col,val), ...]; restart j of
+    problem q has seed seed0 + q*per_problem + j, for its decomposition too (`kernel_search(..., per_block=1)`).  Returns
+    ([(best adds, best muls, best seed) per problem], [status per problem], stats); a problem the device code refuses has its
+    code in status and (2^32-1, 2^32-1, 2^64-1) as best."""
+    L = capi.lib()
+    nprob = len(mats)
+    keep, arr = [], (capi.CSR * max(nprob, 1))()
+    for k, (m, n, rp, col, val) in enumerate(mats):
+        a = ((ctypes.c_uint32 * len(rp))(*rp), (ctypes.c_uint32 * max(len(col), 1))(*col), (ctypes.c_uint32 * max(len(val), 1))(*val))
+        keep.append(a)
+        arr[k] = capi.CSR(m, n, a[0], a[1], a[2])
+    bests, status, st = (capi.Best * max(nprob, 1))(), (ctypes.c_int32 * max(nprob, 1))(), capi.Stats()
+    capi.check(L.plo_kernel_batch_search(nprob, arr, p, seed0, per_problem, cost_mode, bests, status, ctypes.byref(st)))
+    del keep
+    return [(b.adds, b.muls, b.seed) for b in bests[:nprob]], list(status[:nprob]), st.as_dict()
+
+
 def kernel_search_multi(M, p, seed0, nrestarts, devices, cost_mode=capi.COST_SUM_THEN_ADD):
     """`plo_kernel_search_multi`: the restart loop of the kernel method over the listed devices from this process (one host thread
     and one device per contiguous shard, minimum by the RCCL MIN all-reduces).  Returns ((adds, muls, seed), stats)."""
