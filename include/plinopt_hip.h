@@ -492,6 +492,28 @@ int  plo_dep_plan_create_q(const plo_qcsr_t *M, const int64_t *cnum, const int64
 void plo_dep_plan_destroy(plo_dep_plan_t *plan);
 int  plo_dep_search(plo_dep_plan_t *plan, uint32_t row0, uint32_t row1, plo_dep_hit_t *hits, uint64_t cap, uint64_t *nhits, plo_stats_t *stats);
 
+/* ---- The Brent equations of a triple: what the reference's MMchecker (include/plinopt_library.inl:473-558) samples at one random
+ * point, checked here one by one.  L (r x mk), R (r x kn), P (mn x r) as rational CSR; with x = a k + b, y = b' n + c, z = a' n + c',
+ * equation e = (x kn + y) mn + z asks  sum_t L[t][x] R[t][y] P[z][t] = [a = a'][b = b'][c = c']  modulo q, 2 <= q < 2^31, prime or
+ * not (a proof over Q takes a few primes: bin/MMchecker).  A pair is x kn + y; plo_brent_check covers the pairs
+ * [pair0, pair1), that is the equations [pair0 mn, pair1 mn), in as many launches as the plan's pairs per launch ask for, and
+ * reports how many of them are violated, the smallest violated e (~0 when none), the residue found there and the 0 or 1 expected;
+ * stats->candidates is the number of equations checked.  The result is exact and does not depend on scheduling.
+ * Refusals, each with its own text; the argument checks come before any device call, the missing plo_init (PLO_E_HIP) after them:
+ * PLO_E_ARG for a null pointer, for L.n != m k, R.n != k n, P.m != m n, L.m != R.m or L.m != P.n, for q < 2 or q >= 2^31, for an
+ * unsorted row (or any other defect of a CSR), for a denominator that is no unit modulo q, for an empty pair range or one beyond
+ * mk kn.  PLO_E_CAPACITY: mk, kn or mn above 16384 (14-bit indices: 2^28 pairs at most), r above 2^20, or a matrix of 2^31 entries
+ * or more; 32x32x32 of rank 15096 is well inside.
+ * plo_brent_plan_info: out[0] sums per wave in LDS (the chunk: min(mn, 4096), or PLO_BRENT_CHUNK, a test knob), [1] chunks per pair,
+ * [2] waves per workgroup, [3] pairs per launch, [4] LDS bytes per workgroup, [5] mk, [6] kn, [7] mn.  One device per call. */
+typedef struct { uint64_t violated, first; uint32_t value, expected; } plo_brent_result_t;   /* first = ~0 when none */
+typedef struct plo_brent_plan plo_brent_plan_t;
+int  plo_brent_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P,
+                             uint32_t m, uint32_t k, uint32_t n, uint32_t q, plo_brent_plan_t **plan);
+int  plo_brent_check(plo_brent_plan_t *plan, uint64_t pair0, uint64_t pair1, plo_brent_result_t *res, plo_stats_t *stats);
+int  plo_brent_plan_info(plo_brent_plan_t *plan, uint32_t out[8]);
+void plo_brent_plan_destroy(plo_brent_plan_t *plan);
+
 /* Pack / unpack the (cost, seed) word used by the grid reduction and by the
  * single 8-byte MIN all-reduce across ranks (the `#pragma omp critical`
  * best-so-far of include/plinopt_optimize.inl:1214-1237).  seed_off is the

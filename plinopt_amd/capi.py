@@ -29,6 +29,7 @@ EXPORTS = [
     "plo_orbit_plan_create_cse", "plo_orbit_search_multi_cse", "plo_orbit_plan_info",
     "plo_orbit_plan_create_growth", "plo_orbit_growth_many", "plo_orbit_growth_search", "plo_orbit_growth_search_multi",
     "plo_dep_plan_create_q", "plo_dep_plan_destroy", "plo_dep_search",
+    "plo_brent_plan_create_q", "plo_brent_plan_destroy", "plo_brent_plan_info", "plo_brent_check",
     "plo_pack_cost",
 ]
 
@@ -99,6 +100,11 @@ class DepHit(ctypes.Structure):
     """plo_dep_hit_t of include/plinopt_hip.h"""
     _fields_ = [("size", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("col", ctypes.c_uint32), ("residue", ctypes.c_uint32),
                 ("rows", ctypes.c_uint16 * DEP_MAX_LEVEL), ("coef", ctypes.c_uint8 * DEP_MAX_LEVEL)]
+
+
+class BrentResult(ctypes.Structure):
+    """plo_brent_result_t of include/plinopt_hip.h"""
+    _fields_ = [("violated", ctypes.c_uint64), ("first", ctypes.c_uint64), ("value", ctypes.c_uint32), ("expected", ctypes.c_uint32)]
 
 
 class PloError(RuntimeError):
@@ -217,6 +223,13 @@ def lib():
         L.plo_dep_plan_destroy.argtypes = [ctypes.c_void_p]
         L.plo_dep_plan_destroy.restype = None
         L.plo_dep_search.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(DepHit), ctypes.c_uint64, u64p, ctypes.POINTER(Stats)]
+        if hasattr(L, "plo_brent_check"):               # (an older build named by PLO_HIP_LIB, as above)
+            L.plo_brent_plan_create_q.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                  ctypes.POINTER(ctypes.c_void_p)]
+            L.plo_brent_plan_destroy.argtypes = [ctypes.c_void_p]
+            L.plo_brent_plan_destroy.restype = None
+            L.plo_brent_plan_info.argtypes = [ctypes.c_void_p, u32p]
+            L.plo_brent_check.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(BrentResult), ctypes.POINTER(Stats)]
         L.plo_multi_comm_inits.restype = ctypes.c_uint64
         L.plo_pack_cost.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32]
         L.plo_pack_cost.restype = ctypes.c_uint64

@@ -22,6 +22,7 @@
 // --candidate s|base DIR writes the three matrices of one candidate to DIR/{L,R,P}.sms.
 // ==========================================================================
 #include "plo_orbit.hpp"
+#include "plo_brent.hpp"
 #include "plo_dl.hpp"
 #include <chrono>
 #include <filesystem>
@@ -62,13 +63,12 @@ template <class F> void write_triple(const F &f, const OrbitTriple<F> &T, const 
 template <class F> int mm_report(const F &f, const OrbitTriple<F> &T) {
     bool ok = false; std::string why;
     try { ok = orbit_mm_check(f, T); } catch (const std::exception &e) { why = e.what(); }
-    const std::string shape = std::to_string(T.m) + 'x' + std::to_string(T.k) + 'x' + std::to_string(T.n);
     if (ok) {
         OrbitCount c = orbit_candidate(f, T, ORBIT_BASE, ORBIT_DENSITY, ORBIT_ACT_TRIANGULAR, OrbitCse());
-        std::clog << "# \033[1;32mSUCCESS: correct " << shape << " (" << c.nnz << ',' << c.nno << ") Matrix-Multiplication over " << f.name() << " \033[0m" << std::endl;
+        std::clog << mm_success_line(T.m, T.k, T.n, c.nnz, c.nno, f.name()) << std::endl;          // (the wording is bin/MMchecker's too: plo_brent.hpp)
         return 0;
     }
-    std::cerr << "# \033[1;31m****** ERROR, not a " << shape << " MM algorithm over " << f.name() << (why.empty() ? "" : " (check failed: " + why + ")") << "******\033[0m" << std::endl;
+    std::cerr << mm_error_line(T.m, T.k, T.n, f.name(), why) << std::endl;
     return 1;
 }
 
@@ -204,24 +204,6 @@ template <class F> int orbit_run(const F &f, const QMat &QL, const QMat &QR, con
     if (o.cse) std::clog << ", " << o.loops * 3 * z.sub << " Optimizer runs (sub " << z.sub << ")";
     std::clog << std::endl;
     return 0;
-}
-
-// deterministic Miller-Rabin below 2^64 (the first twelve primes as bases)
-bool is_prime(uint64_t n) {
-    if (n < 2) return false;
-    static const uint64_t B[12] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37};
-    for (uint64_t q : B) { if (n == q) return true; if (n % q == 0) return false; }
-    uint64_t d = n - 1; int s = 0; while (!(d & 1)) { d >>= 1; ++s; }
-    auto mul = [&](uint64_t a, uint64_t b) { return (uint64_t)((unsigned __int128)a * b % n); };
-    for (uint64_t a : B) {
-        uint64_t x = 1, b = a % n;
-        for (uint64_t e = d; e; e >>= 1) { if (e & 1) x = mul(x, b); b = mul(b, b); }
-        if (x == 1 || x == n - 1) continue;
-        bool comp = true;
-        for (int i = 1; i < s && comp; ++i) { x = mul(x, x); if (x == n - 1) comp = false; }
-        if (comp) return false;
-    }
-    return true;
 }
 
 int refuse(const std::string &why) { std::cerr << "# \033[1;31mERROR: " << why << "\033[0m\n"; return 2; }

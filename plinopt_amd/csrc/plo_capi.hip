@@ -18,6 +18,7 @@
 #include "plo_orbit_cse.hip"
 #include "plo_orbit_growth.hip"
 #include "plo_dep.hip"
+#include "plo_brent.hip"
 #include "../../include/plinopt_hip.h"
 
 #include <algorithm>
@@ -3261,6 +3262,158 @@ int plo_dep_search(plo_dep_plan_t *pl, uint32_t row0, uint32_t row1, plo_dep_hit
         else if (found > PLO_DEP_MAX_HITS) rc = fail(PLO_E_CAPACITY, std::to_string(found) + " hits, more than 2^24 in one call: take fewer top rows");
         else if (found > cap) rc = fail(PLO_E_CAPACITY, std::to_string(found) + " hits for a buffer of " + std::to_string(cap));
         else std::sort(hits, hits + found, dep_before);
+    }
+    return call.done(rc);
+}
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------- Brent equations
+struct plo_brent_plan {
+    plo::BrentPlan P{};
+    void *d_img = nullptr; unsigned long long *d_res = nullptr;      // d_res: the count of violated equations, then the packed minimum
+    uint32_t waves_per_wg = 4, lds_bytes = 0, pairs_per_launch = 0, mk = 0;
+    uint64_t algo_bytes = 0;
+};
+
+namespace {
+#define PLO_BRENT_MAX_DIM 16384u
+#define PLO_BRENT_MAX_RANK (1u << 20)
+#define PLO_BRENT_MAX_CHUNK 4096u
+// wave steps (one t of an intersection, or 64 entries of a row of P^T) that one launch may take by the bound below: on the order of 0.1 s
+#define PLO_BRENT_LAUNCH_STEPS (1ull << 28)
+
+// A matrix by the other index: the (row, residue) lists of its columns, rows increasing; entries that vanish modulo q are dropped.
+// False when a denominator is no unit.
+struct BrentCols { std::vector<uint32_t> ptr, idx, val; };
+bool brent_cols(const plo_qcsr_t *A, uint32_t q, BrentCols &C) {
+    C.ptr.assign((size_t)A->n + 1u, 0u);
+    std::vector<uint32_t> res(A->rowptr[A->m]);
+    for (uint32_t e = 0; e < A->rowptr[A->m]; ++e) {
+        if (!residue_of(A->num[e], A->den ? A->den[e] : 1, q, res[e])) return false;
+        if (res[e]) ++C.ptr[A->col[e] + 1u];
+    }
+    for (uint32_t j = 0; j < A->n; ++j) C.ptr[j + 1u] += C.ptr[j];
+    C.idx.resize(C.ptr[A->n]); C.val.resize(C.ptr[A->n]);
+    std::vector<uint32_t> at(C.ptr.begin(), C.ptr.end() - 1);
+    for (uint32_t i = 0; i < A->m; ++i)
+        for (uint32_t e = A->rowptr[i]; e < A->rowptr[i + 1]; ++e)
+            if (res[e]) { const uint32_t s = at[A->col[e]]++; C.idx[s] = i; C.val[s] = res[e]; }
+    return true;
+}
+} // namespace
+
+extern "C" {
+int plo_brent_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, uint32_t m, uint32_t k, uint32_t n, uint32_t q, plo_brent_plan_t **plan)
+{
+    if (!L || !R || !P || !plan) return fail(PLO_E_ARG, "null argument");
+    if (m == 0 || k == 0 || n == 0) return fail(PLO_E_ARG, "m, k and n must be positive");
+    if ((uint64_t)m * k != L->n || (uint64_t)k * n != R->n || (uint64_t)m * n != P->m || L->m != R->m || L->m != P->n)
+        return fail(PLO_E_ARG, "shapes " + std::to_string(L->m) + "x" + std::to_string(L->n) + ", " + std::to_string(R->m) + "x" + std::to_string(R->n) + ", " +
+                               std::to_string(P->m) + "x" + std::to_string(P->n) + " are not r x mk, r x kn, mn x r for " + std::to_string(m) + "x" + std::to_string(k) + "x" + std::to_string(n));
+    if (q < 2u || q >= (1u << 31)) return fail(PLO_E_ARG, "modulus " + std::to_string(q) + " outside 2 .. 2^31 - 1");
+    for (const plo_qcsr_t *A : {L, R, P}) if (const char *d = qcsr_defect(A)) return fail(PLO_E_ARG, d);
+    const uint32_t r = L->m, mk = L->n, kn = R->n, mn = P->m;
+    if (mk > PLO_BRENT_MAX_DIM || kn > PLO_BRENT_MAX_DIM || mn > PLO_BRENT_MAX_DIM) return fail(PLO_E_CAPACITY, "mk, kn or mn above 16384");
+    if (r > PLO_BRENT_MAX_RANK) return fail(PLO_E_CAPACITY, "rank above 2^20");
+    for (const plo_qcsr_t *A : {L, R, P}) if (A->rowptr[A->m] >= (1u << 31)) return fail(PLO_E_CAPACITY, "a matrix of 2^31 entries or more");
+    BrentCols cl, cr, cp;
+    for (const auto &pr : {std::make_pair(L, &cl), std::make_pair(R, &cr), std::make_pair(P, &cp)})
+        if (!brent_cols(pr.first, q, *pr.second)) return fail(PLO_E_ARG, "a denominator is no unit modulo " + std::to_string(q));
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
+
+    plo_brent_plan *pl = new plo_brent_plan();
+    plo::BrentPlan &Q = pl->P;
+    Q.k = k; Q.n = n; Q.kn = kn; Q.mn = mn; Q.q = q; Q.mu = (~0ull) / q;
+    pl->mk = mk;
+    const uint32_t chunk_max = std::min(mn, PLO_BRENT_MAX_CHUNK);
+    Q.chunk = chunk_max;
+    if (const auto c = env_knob("PLO_BRENT_CHUNK")) Q.chunk = (uint32_t)std::min<long>(std::max<long>(*c, 1), chunk_max);   // test knob: several chunks on a small mn
+    Q.nchunks = (mn + Q.chunk - 1u) / Q.chunk;
+    pl->lds_bytes = round_up(4u * Q.chunk * pl->waves_per_wg, 16);
+    // Pairs per launch: a pair takes, per chunk, at most min(wL[x], wR[y]) steps for its t, wX the steps 1 + ceil(|row t of P^T| / 64)
+    // summed over a column, besides the bisections of its column of L and the clearing and comparing of the chunk
+    std::vector<uint32_t> wp(r);
+    for (uint32_t t = 0; t < r; ++t) wp[t] = 1u + (cp.ptr[t + 1u] - cp.ptr[t] + 63u) / 64u;
+    auto heaviest = [&](const BrentCols &C, uint32_t cols, uint64_t *longest) {
+        uint64_t best = 0; *longest = 0;
+        for (uint32_t j = 0; j < cols; ++j) {
+            uint64_t w = 0;
+            for (uint32_t e = C.ptr[j]; e < C.ptr[j + 1u]; ++e) w += wp[C.idx[e]];
+            best = std::max(best, w); *longest = std::max<uint64_t>(*longest, C.ptr[j + 1u] - C.ptr[j]);
+        }
+        return best;
+    };
+    uint64_t longl = 0, longr = 0;
+    const uint64_t wl = heaviest(cl, mk, &longl), wr = heaviest(cr, kn, &longr);
+    const uint64_t per_pair = (uint64_t)Q.nchunks * (std::min(wl, wr) + (longl + 63u) / 64u * 24u + 2u * ((Q.chunk + 63u) / 64u) + 1u);
+    uint64_t ppl = std::max<uint64_t>(1, PLO_BRENT_LAUNCH_STEPS / per_pair);
+    ppl = std::min<uint64_t>(ppl, 0xFFFFFFFFull / mn);                                  // (pair - pair0) mn + z stays below 2^32 in the packed minimum
+    if (const auto c = env_knob("PLO_BRENT_PAIRS")) ppl = (uint64_t)std::min<long>(std::max<long>(*c, 1), (long)ppl);   // test knob: several launches on a small input
+    pl->pairs_per_launch = (uint32_t)std::min<uint64_t>(ppl, (uint64_t)mk * kn);
+    pl->algo_bytes = 8ull * (cl.idx.size() + cr.idx.size() + cp.idx.size());
+
+    // the image: nine arrays of 32-bit words
+    const std::vector<uint32_t> *arr[9] = {&cl.ptr, &cl.idx, &cl.val, &cr.ptr, &cr.idx, &cr.val, &cp.ptr, &cp.idx, &cp.val};
+    size_t off[9], words = 0;
+    for (int j = 0; j < 9; ++j) { off[j] = words; words += (arr[j]->size() + 3u) / 4u * 4u; }
+    std::vector<uint32_t> img(std::max<size_t>(words, 4), 0u);
+    for (int j = 0; j < 9; ++j) if (!arr[j]->empty()) memcpy(img.data() + off[j], arr[j]->data(), 4u * arr[j]->size());
+    if (hipMalloc(&pl->d_img, 4u * img.size()) != hipSuccess || hipMemcpy(pl->d_img, img.data(), 4u * img.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc((void **)&pl->d_res, 16) != hipSuccess ||
+        hipFuncSetAttribute((const void *)plo::brent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4u * PLO_BRENT_MAX_CHUNK * pl->waves_per_wg)) != hipSuccess) {   // the largest any plan asks for: plans do not lower it under each other
+        plo_brent_plan_destroy(pl); return fail(PLO_E_HIP, "device setup of the Brent plan failed");
+    }
+    const uint32_t *d = (const uint32_t *)pl->d_img;
+    Q.lcp = d + off[0]; Q.lt = d + off[1]; Q.lv = d + off[2];
+    Q.rcp = d + off[3]; Q.rt = d + off[4]; Q.rv = d + off[5];
+    Q.prp = d + off[6]; Q.pz = d + off[7]; Q.pv = d + off[8];
+    *plan = pl;
+    return PLO_OK;
+}
+
+void plo_brent_plan_destroy(plo_brent_plan_t *pl)
+{
+    if (pl) { dev_free(pl->d_img, pl->d_res); delete pl; }
+}
+
+int plo_brent_plan_info(plo_brent_plan_t *pl, uint32_t out[8])
+{
+    if (!pl || !out) return fail(PLO_E_ARG, "null argument");
+    out[0] = pl->P.chunk; out[1] = pl->P.nchunks; out[2] = pl->waves_per_wg; out[3] = pl->pairs_per_launch;
+    out[4] = pl->lds_bytes; out[5] = pl->mk; out[6] = pl->P.kn; out[7] = pl->P.mn;
+    return PLO_OK;
+}
+
+int plo_brent_check(plo_brent_plan_t *pl, uint64_t pair0, uint64_t pair1, plo_brent_result_t *res, plo_stats_t *stats)
+{
+    if (!pl || !res) return fail(PLO_E_ARG, "null argument");
+    const uint64_t npairs = (uint64_t)pl->mk * pl->P.kn;
+    if (pair0 >= pair1 || pair1 > npairs) return fail(PLO_E_ARG, "pairs " + std::to_string(pair0) + " .. " + std::to_string(pair1) + ": an empty range or one beyond the " + std::to_string(npairs) + " pairs");
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
+    CallScope call(stats); plo_stats_t *st = call.st;
+    const plo::BrentPlan &Q = pl->P;
+    *res = plo_brent_result_t{0, ~0ull, 0, 0};
+    int rc = PLO_OK;
+    for (uint64_t p0 = pair0; rc == PLO_OK && p0 < pair1;) {
+        const uint64_t cnt = std::min<uint64_t>(pl->pairs_per_launch, pair1 - p0);
+        if (hipMemsetAsync(pl->d_res, 0, 8, g_stream) != hipSuccess || hipMemsetAsync(pl->d_res + 1, 0xFF, 8, g_stream) != hipSuccess) { rc = fail(PLO_E_HIP, "clearing the Brent result words"); break; }
+        plo::BrentJob J{}; J.pair0 = p0; J.npairs = cnt; J.count = pl->d_res; J.first = pl->d_res + 1;
+        const uint64_t grid = (cnt + pl->waves_per_wg - 1u) / pl->waves_per_wg;
+        rc = timed_launch(pl, grid, cnt * Q.mn, st, [&] {
+            hipLaunchKernelGGL(plo::brent_kernel, dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+        });
+        unsigned long long w[2] = {0, 0};
+        if (rc == PLO_OK && hipMemcpy(w, pl->d_res, 16, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back of the Brent result words");
+        if (rc != PLO_OK) break;
+        if (w[0]) {
+            if (res->violated == 0) { res->first = p0 * Q.mn + (w[1] >> 32); res->value = (uint32_t)w[1]; }   // launches go by increasing pair
+            res->violated += w[0];
+        }
+        p0 += cnt;
+    }
+    if (rc == PLO_OK && res->violated) {
+        const uint64_t z = res->first % Q.mn, pair = res->first / Q.mn, x = pair / Q.kn, y = pair % Q.kn;
+        res->expected = (x % Q.k == y / Q.n && z == (x / Q.k) * Q.n + y % Q.n) ? 1u : 0u;
     }
     return call.done(rc);
 }

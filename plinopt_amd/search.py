@@ -608,3 +608,41 @@ class DepPlan:
         capi.check(rc)
         self.last_stats = st.as_dict()
         return [(tuple(h.rows[:h.size]), (None,) + tuple(h.coef[1:h.size]), h.kind, h.col, h.residue) for h in hits[:nh.value]]
+
+
+class BrentPlan:
+    """Mirror of the exact matrix-multiplication check of bin/MMchecker (plo_brent_*): L (r x mk), R (r x kn), P (mn x r), each
+    (rows, columns, rowptr, col, num[, den]), and the shape (m, k, n); every Brent equation modulo q (2 <= q < 2^31, prime or
+    not).  `check(pair0, pair1)` covers the pairs x kn + y of [pair0, pair1) (default: all) and returns (violated, first,
+    value, expected): the number of violated equations, the smallest one e = (x kn + y) mn + z (None when there is none), the
+    residue found there and the 0 or 1 it should be.  `info()` is `plo_brent_plan_info`."""
+
+    def __init__(self, L, R, P, m, k, n, q, device=None):
+        lib = capi.lib()
+        if device is not None:
+            capi.check(lib.plo_init(device))
+        self._h = None
+        self._csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
+        h = ctypes.c_void_p()
+        capi.check(lib.plo_brent_plan_create_q(*[ctypes.byref(c) for c, _ in self._csr], m, k, n, q, ctypes.byref(h)))
+        self._h = h
+        self.npairs = m * k * k * n
+        self.last_stats = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                capi.lib().plo_brent_plan_destroy(self._h); self._h = None
+        except Exception:
+            pass
+
+    def info(self):
+        out = (ctypes.c_uint32 * 8)()
+        capi.check(capi.lib().plo_brent_plan_info(self._h, out))
+        return dict(zip(("chunk", "chunks", "waves_per_wg", "pairs_per_launch", "lds_bytes", "mk", "kn", "mn"), out))
+
+    def check(self, pair0=0, pair1=None):
+        res, st = capi.BrentResult(), capi.Stats()
+        capi.check(capi.lib().plo_brent_check(self._h, pair0, self.npairs if pair1 is None else pair1, ctypes.byref(res), ctypes.byref(st)))
+        self.last_stats = st.as_dict()
+        return res.violated, (res.first if res.violated else None), res.value, res.expected
