@@ -721,7 +721,7 @@ void print_big_stats(const plo_plan *pl)
     { unsigned long long gp[16] = {0};
       if (hipMemcpyFromSymbol(gp, HIP_SYMBOL(plo::g_prof), sizeof gp) != hipSuccess) memset(gp, 0, sizeof gp);
       if (gp[3]) fprintf(stderr, "#   sweep of the steps with >= 256 rows, all candidates: %llu trips by %llu wave-sweeps; cycles per trip: chunk wait + stores %.0f, aggregation of both chunks %.0f, rest of the loop %.0f; per wave-sweep %.0f cycles, %.1f trips; probe rounds per trip %.2f, active lanes per trip %.1f\n", gp[3], gp[5], (double)gp[0] / gp[3], (double)gp[1] / gp[3], (double)gp[2] / gp[3], (double)gp[4] / gp[5], (double)gp[3] / gp[5], (double)gp[6] / gp[3], (double)gp[7] / gp[3]);
-      if (gp[3] && pl->B.defer && pl->B.mode == 2u) fprintf(stderr, "#   aggregation of a trip (lane 0 of every wave, big steps), cycles: ratio-id lookup %.0f, pair read %.0f, compare-and-swap %.0f, bitmap + count %.0f\n", (double)gp[14] / gp[3], (double)gp[8] / gp[3], (double)gp[9] / gp[3], (double)gp[10] / gp[3]);
+      if (gp[3] && pl->B.defer && pl->B.mode == 2u) fprintf(stderr, "#   aggregation of a trip (lane 0 of every wave, big steps), cycles: ratio-id lookup %.0f, pair read %.0f, compare-and-swap %.0f, count %.0f\n", (double)gp[14] / gp[3], (double)gp[8] / gp[3], (double)gp[9] / gp[3], (double)gp[10] / gp[3]);
       if ((gp[14] || gp[15]) && !pl->B.defer) fprintf(stderr, "#   flush 1, all candidates: entries whose pair with a has a as SECOND column %llu, with b %llu\n", gp[14], gp[15]);
       if (gp[11]) fprintf(stderr, "#   flush 1 of the steps with >= 256 rows: %llu wave-trips by %llu wave-flushes; cycles per trip: fetch + decode %.0f, probe loads %.0f, stores + bookkeeping %.0f; per wave-flush %.0f cycles, %.1f trips\n", gp[11], gp[13], (double)gp[8] / gp[11], (double)gp[9] / gp[11], (double)gp[10] / gp[11], (double)gp[12] / gp[13], (double)gp[11] / gp[13]);
     }

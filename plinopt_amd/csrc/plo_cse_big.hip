@@ -50,8 +50,13 @@
 //              mode 2 with deferred updates takes the entries of its next 64 rows as ONE sequence, 64 per trip (the flat sweep:
 //              the lane's row from mark words, the row's record by four ds_bpermute, entries requested two trips ahead, two
 //              unconditional stores, one ratio-identifier lookup indexed by position (left or right of the a entry), one
-//              aligned-pair probe of the aggregation table: agg_add_rid_bm, a single-exit loop over pair indices).
-//   flush      pass 1 (retirements): every lane walks its share of the slot list on
+//              aligned-pair probe of the aggregation table: agg_add_rid_bm, a single-exit loop over pair indices).  That sweep keeps
+//              NO record of the slots it claims -- no list, no counter, and since the hash/bitmap change no bitmap either (5 vector
+//              and 1 LDS instruction per probe round, on nearly every trip): a claimed slot is one whose key word is not empty.
+//   flush      deferred updates with ratio identifiers: ONE pass; a thread owns 8 aligned pairs of slots of the aggregation table
+//              (pair tid + u x threads: the lanes of a wave read consecutive words), reads their key words once (eight 8-byte LDS
+//              reads) and works through the ones that hold a key, emptying them.
+//              The other instances: pass 1 (retirements): every lane walks its share of the slot list on
 //              its own (next entry as soon as both keys are settled); every table slot
 //              has ONE writer in this pass, so the new frequency is a plain store of
 //              the probed word.  Pass 2 (insertions, after a barrier): CAS claims.
@@ -461,14 +466,14 @@ __device__ __forceinline__ bool agg_add_rid(uint32_t *aggk, uint32_t *aggc32, ui
     return done;
 }
 
-// The same probe loop for the staged sweep (mode 2 with deferred updates): a claimed slot sets its bit in a bitmap with a
-// fire-and-forget atomic -- no counter with a returned value, no slot list (two LDS round trips less on the claim path).
+// The same probe loop for the staged sweep (mode 2 with deferred updates): a claim leaves no trace but the key itself -- no counter
+// with a returned value, no slot list, no bitmap; the flush finds the claimed slots by their keys (the name is from the bitmap's time).
 // hshift = 33 - aggbits, the shift that turns the hash into a PAIR index: the sweep hands it over in a vector register (below).
-__device__ __forceinline__ bool agg_add_rid_bm(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, uint32_t *bm, uint32_t hshift, uint32_t *iters = nullptr) {
+__device__ __forceinline__ bool agg_add_rid_bm(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, uint32_t hshift, uint32_t *iters = nullptr) {
     // aligned pairs of slots (one ds_read_b64, the two counts share a word); the hash is a 24-bit product (full rate).
     // ONE slot of the pair matters: the first when it holds the key or is empty (slots of a pair fill in order, so an empty first slot rules
     // the second one out), else the second.  Hit and claim end in the same count update, the loop has one exit, and all it carries is the
-    // pair's index (pair, count word and bitmap bit are each one shift-and-add from it) and the probes left.  Written as "hit: return /
+    // pair's index (pair and count word are each one shift-and-add from it) and the probes left.  Written as "hit: return /
     // claim: return or again / next pair" the compiler kept a state word and a copy of every carried value per exit: 43 vector and 50
     // scalar instructions a round with every block visited -- which most trips do, some lane always claims -- against 23 and 28.
     const uint32_t pmask = (1u << (aggbits - 1u)) - 1u;
@@ -484,7 +489,6 @@ __device__ __forceinline__ bool agg_add_rid_bm(uint32_t *aggk, uint32_t *aggc32,
         if (kt == 0xFFFFFFFFu) {
             const uint32_t sec = first ? 0u : 1u;
             const uint32_t old = wg_cas((uint32_t *)((unsigned long long *)aggk + pi) + sec, 0xFFFFFFFFu, key);
-            if (old == 0xFFFFFFFFu) { const uint32_t t = 2u * pi + sec; wg_or(&bm[t >> 5], 1u << (t & 31u)); }
             mine = old == 0xFFFFFFFFu || old == key;       // (else somebody took the slot for another key: look at both again)
         }
         if (mine) wg_add(&aggc32[pi], first ? 1u : 0x10000u);
@@ -495,9 +499,9 @@ __device__ __forceinline__ bool agg_add_rid_bm(uint32_t *aggk, uint32_t *aggc32,
 
 #ifdef PLO_BIG_PROFILE
 // First round of the same probe, written without a loop, with a clock after every LDS round trip (profile build): acc[0] pair read,
-// [1] compare-and-swap, [2] bitmap + count.  Returns true when the key is NOT settled (both slots hold other keys, or the claim lost
+// [1] compare-and-swap, [2] count.  Returns true when the key is NOT settled (both slots hold other keys, or the claim lost
 // to another key): the caller sends those lanes, ~0.2 % of them, through the loop.
-__device__ __forceinline__ bool agg_add_rid_first_prof(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, uint32_t *bm, unsigned long long *acc) {
+__device__ __forceinline__ bool agg_add_rid_first_prof(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, unsigned long long *acc) {
     const unsigned long long c0 = clock64();
     const uint32_t s = ((uint32_t)__umul24(key, 0x9E3779u) >> (32u - aggbits)) & ~1u;
     const unsigned long long kk = __hip_atomic_load((unsigned long long *)(aggk + s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -508,8 +512,7 @@ __device__ __forceinline__ bool agg_add_rid_first_prof(uint32_t *aggk, uint32_t 
     uint32_t old = 0u;
     if (tryc) old = wg_cas(&aggk[t], 0xFFFFFFFFu, key);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long c2 = clock64();
-    const bool fresh = tryc && old == 0xFFFFFFFFu, ok = hit || fresh || (tryc && old == key);
-    if (fresh) wg_or(&bm[t >> 5], 1u << (t & 31u));
+    const bool ok = hit || (tryc && (old == 0xFFFFFFFFu || old == key));
     if (ok) wg_add(&aggc32[s >> 1], sec ? 0x10000u : 1u);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long c3 = clock64();
     acc[0] += c1 - c0; acc[1] += c2 - c1; acc[2] += c3 - c2;
@@ -922,8 +925,7 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
     // slots claimed in the aggregation table by the running sweep (the flush walks this list, not the table): mode 2 has room
     // for every slot; the other modes keep a short list in the tie-selection buffer, idle during the sweeps, and walk the
     // table when a step claims more
-    constexpr bool FAST = MODE == 2 && DEFER;                                  // staged aggregation with deferred claims, bitmap of claimed slots
-    uint32_t *aggbm = (uint32_t *)sh.sel;                                       // FAST: one bit per aggregation slot (2^aggbits <= 2^14 bits; the tie-selection buffer is idle during the sweeps)
+    constexpr bool FAST = MODE == 2 && DEFER;                                  // staged aggregation with deferred claims; the flush finds the claimed slots by their keys
     uint16_t *agglist = (MODE == 2 && !DEFER) ? TB.list : (uint16_t *)sh.sel; const uint32_t listcap = (MODE == 2 && !DEFER) ? (1u << aggbits) : PLO_AGG_LIST;   // (DEFER: the Bloom filter has the place of mode 2's full list)
     const A64 spill{ws, ws_off<O>(P.o_spill)}; const uint32_t spillcap = PW(nnz) + 64u;   // new-column pairs of entries that found no room in LDS (a step touches every entry at most once)
     const A32 multc{ws, ws_off<O>(P.o_multc)}, multv{ws, ws_off<O>(P.o_multv)};
@@ -1186,14 +1188,15 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
         const bool swap = gload32(&ucount[a]) < gload32(&ucount[b]);      // :70-88
         const uint32_t l0 = swap ? b : a, l1 = swap ? a : b;
         if (tid == 0) { sh.naff = 0; sh.aggn = 0; sh.nspill = 0; sh.keepn = 0; }      // (nothing here uses `swap`: the two counts stay in flight while the row lists are walked)
-        if constexpr (FAST) { for (uint32_t w = tid; w < ((1u << aggbits) + 31u) / 32u; w += nth) aggbm[w] = 0u; }      // (the tie pick used the buffer)
         BSYNC();
 #define RL(v_, k_) ((uint32_t)__builtin_amdgcn_readlane((int)(v_), (int)(k_)))
+        A32 wlst; uint32_t lc;                                               // the walked list and its column: the compaction behind the search's barrier works from these
         {   // rows holding the triple: walk the shorter row list of the two columns
             const A32 la = a < n ? tl + tptr[a] : ncr + ncrptr[a - n], lb = b < n ? tl + tptr[b] : ncr + ncrptr[b - n];
             const uint32_t na = gload32(&clen[a]), nb = gload32(&clen[b]);          // live lengths: what earlier walks left of the lists
             const bool walk_a = na <= nb;
             const A32 lst = walk_a ? la : lb; const uint32_t ln = walk_a ? na : nb;
+            wlst = lst; lc = walk_a ? a : b;
             if (tid == 0) sh.nsearched += ln;
             // Two rows per thread and trip, both columns of both rows searched in lock step: the four binary searches have
             // their loads in flight together (8 dependent memory round trips for two rows instead of 36).  A search keeps
@@ -1267,11 +1270,10 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
         }
         PLO_BIG_FENCE(); BSYNC();
         const uint32_t naff = sh.naff;
-        {   // the walked list, compacted (it is read next in a later step, many barriers from here)
-            const uint32_t nk = sh.keepn, lc = gload32(&clen[a]) <= gload32(&clen[b]) ? a : b;
-            const A32 dst = lc < n ? tl + tptr[lc] : ncr + ncrptr[lc - n];
-            for (uint32_t k = tid; k < nk; k += nth) dst[k] = keep[k];
-            BSYNC();                                                           // (every thread has read both lengths)
+        {   // the walked list, compacted (it and its length are read next in a later step, many barriers from here: neither length has
+            // changed since the head of the search, so the list is the one walked -- no second look at the lengths and the list's base)
+            const uint32_t nk = sh.keepn;
+            for (uint32_t k = tid; k < nk; k += nth) wlst[k] = keep[k];
             if (tid == 0) clen[lc] = nk;
         }
         PLO_STAMP(2);
@@ -1306,12 +1308,12 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
 #ifdef PLO_BIG_PROFILE
                     if constexpr (FAST) {
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); prt += clock64() - cr0;
-                        const bool pend = agg_add_rid_first_prof(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm, pq);
+                        const bool pend = agg_add_rid_first_prof(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, pq);
                         if (!__builtin_amdgcn_ballot_w64(pend)) return;
-                        if (!pend || agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm, aggsh, &probe_iters)) return;
+                        if (!pend || agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggsh, &probe_iters)) return;
                     }
 #else
-                    if constexpr (FAST) { if (!noagg) { if (__builtin_expect(agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggbm, aggsh), 1)) return; } }
+                    if constexpr (FAST) { if (!noagg) { if (__builtin_expect(agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggsh), 1)) return; } }
 #endif
                     else if (agg_add_rid(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, &sh.aggn, agglist, listcap)) return;
                     const uint32_t vib = (rw >> PLO_RW_VIB) & 31u;
@@ -1584,17 +1586,27 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                 if (sl == 0xFFFFFFFFu || (uint32_t)(v & PLO_GVMASK) != M) { wg_max(&sh.errflag, (uint32_t)BERR_TABLE); wg_max(&sh.derr, 202u); }
                 else { gstore64(&tab[sl], v - (uint64_t)M); retired(key, M, M); }
             }
-            const uint32_t nent = sh.aggn, nslot = FAST ? (1u << aggbits) / 16u : nent <= listcap ? nent : (1u << aggbits);     // few entries: walk the slot list, not the table (FAST: the bitmap, 16 slots per thread and round)
+            const uint32_t nent = sh.aggn, nslot = FAST ? (1u << aggbits) / 16u : nent <= listcap ? nent : (1u << aggbits);     // few entries: walk the slot list, not the table (FAST: the whole table, 16 slots per thread and round)
             uint32_t nhot = 0;
             for (uint32_t s0 = 0; s0 < nslot; s0 += nth) {
               const uint32_t e_ = s0 + tid;
               uint32_t bits_ = 0;
               if constexpr (FAST) {
-                  if (e_ < nslot) bits_ = (aggbm[e_ >> 1] >> ((e_ & 1u) << 4)) & 0xFFFFu;
+                  // The thread's 16 slots of this round, a bit per slot that holds a key (the sweep keeps no record of its claims): the
+                  // aligned PAIRS 8 s0 + tid + u nth, u = 0..7, so that the lanes of a wave read consecutive 8-byte words -- no bank
+                  // conflict.  (16 consecutive slots per thread put the lanes 64 bytes apart: a 16-way conflict on every read of a table
+                  // that is read whole in every step; measured: 0.7 % of the loaded throughput)
+                  const uint32_t npair = 1u << (aggbits - 1u);
+#pragma unroll
+                  for (uint32_t u = 0; u < 8u; ++u) {
+                      const uint32_t q = s0 * 8u + u * nth + tid; const bool in = q < npair;
+                      const uint2 kq2 = ((const uint2 *)aggk)[in ? q : 0u];
+                      bits_ |= in ? ((kq2.x != 0xFFFFFFFFu ? 1u : 0u) | (kq2.y != 0xFFFFFFFFu ? 2u : 0u)) << (2u * u) : 0u;
+                  }
               }
               for (bool more_ = true; more_;) {
                 bool valid; uint32_t s;
-                if constexpr (FAST) { valid = bits_ != 0u; s = valid ? e_ * 16u + (uint32_t)__builtin_ctz(bits_) : 0u; bits_ &= bits_ - 1u; }
+                if constexpr (FAST) { valid = bits_ != 0u; const uint32_t j_ = valid ? (uint32_t)__builtin_ctz(bits_) : 0u; s = valid ? 2u * (s0 * 8u + (j_ >> 1) * nth + tid) + (j_ & 1u) : 0u; bits_ &= bits_ - 1u; }
                 else { valid = e_ < nslot; s = valid ? (nent <= listcap ? (uint32_t)agglist[e_] : e_) : 0u; }
                 uint32_t c = 0, x = 0, y = 0, d = 0;
                 if constexpr (MODE == 2) {
