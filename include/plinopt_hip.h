@@ -249,7 +249,9 @@ int plo_kernel_search_multi(const plo_csr_t *M, uint32_t p, uint64_t seed0, uint
  * matrix being sparsified (dense, row major, residues mod p), Cand the n x n matrix whose rows 0..row-1 are the
  * rows already chosen; candidate (i,j,k,l) is the row w with w[offsetblock+t] = coeffs[(i,j,k,l)[t]] (positions
  * >= n dropped, :305-310).  Result: the first candidate in lexicographic (i,j,k,l) order that is independent of
- * the chosen rows and maximises (zeros(TM^T w), zeros(w)), if it beats (w0,w1) strictly; index = ((i*C+j)*C+k)*C+l. */
+ * the chosen rows and maximises (zeros(TM^T w), zeros(w)), if it beats (w0,w1) strictly; index = ((i*C+j)*C+k)*C+l.
+ * TM, Cand and coeffs are taken modulo p, so a coefficient congruent to 0 counts as a zero of w; any w0 < 0 is beaten by every
+ * candidate, (w0 >= 0, w1 < 0) by every (w0, .), and (w0, w1 > n) by no (w0, .). */
 typedef struct {
     int32_t  zeros_v, zeros_w;   /* score of the winner (or the incoming w0,w1 when nothing beats them) */
     uint64_t index;              /* flattened (i,j,k,l) */

@@ -2191,8 +2191,10 @@ void cob_prepare(uint32_t n, uint32_t m, const uint32_t *TM, const uint32_t *Can
     for (uint32_t c = 0; c < R.qn; ++c) for (uint32_t t = 0; t < 4; ++t) R.nb[(size_t)t * R.qn + c] = cols[c][t];
     R.tmb.assign(4 * (size_t)m, 0);
     for (uint32_t t = 0; t < fb; ++t) for (uint32_t j = 0; j < m; ++j) R.tmb[(size_t)t * m + j] = TM[(size_t)(offsetblock + t) * m + j] % p;
-    const int64_t thr = w0 < 0 ? -1 : (int64_t)w0 * (n + 1) + std::max(w1, 0);
-    R.init = ((unsigned long long)(thr + 1) << 32) | 0xFFFFFFFFull;
+    // a candidate (zv,zw), 0 <= zw <= n, has the high word zv*(n+1)+zw+1 and beats (w0,w1) in the lexicographic order iff that exceeds
+    // w0*(n+1)+w1+1 with w1 clamped to [-1,n]: (w0,-1) is beaten by every (w0,zw), (w0,w1>n) by none; every candidate beats w0 < 0
+    const int64_t thr = w0 < 0 ? 0 : (int64_t)w0 * (n + 1) + std::min<int64_t>(std::max<int64_t>(w1, -1), n) + 1;
+    R.init = ((unsigned long long)thr << 32) | 0xFFFFFFFFull;
 }
 void cob_decode(unsigned long long w, unsigned long long init, uint32_t n, int32_t w0, int32_t w1, plo_cob_best_t *out)
 {
@@ -2267,7 +2269,8 @@ int plo_cob_search_batch(uint32_t nprob, uint32_t n, uint32_t m, uint32_t row, u
     for (uint32_t q = 0; q < nlive; ++q) {
         const uint32_t k = live[q], C = prob[k].ncoeffs, p = prob[k].p;
         memcpy(up.data() + 2 * q, &R[k].init, 8);
-        memcpy(up.data() + off[q][0], R[k].tmb.data(), R[k].tmb.size() * 4); memcpy(up.data() + off[q][1], R[k].nb.data(), R[k].nb.size() * 4); memcpy(up.data() + off[q][2], prob[k].coeffs, (size_t)C * 4);
+        memcpy(up.data() + off[q][0], R[k].tmb.data(), R[k].tmb.size() * 4); memcpy(up.data() + off[q][1], R[k].nb.data(), R[k].nb.size() * 4);
+        for (uint32_t x = 0; x < C; ++x) up[off[q][2] + x] = prob[k].coeffs[x] % p;      // (residues, as TM and Cand: zeros(w) counts them)
         plo::CobJob &J = B.J[q];
         J.n = n; J.m = m; J.qn = R[k].qn; J.fb = R[k].fb; J.C = C; J.p = p; J.mu = (~0ull) / p; J.first = 0; J.total = (uint64_t)C * C * C * C;
         J.tm = cx.cob_buf + off[q][0]; J.nb = cx.cob_buf + off[q][1]; J.coeffs = cx.cob_buf + off[q][2]; J.best = (unsigned long long *)cx.cob_buf + q;
@@ -2308,7 +2311,8 @@ int plo_cob_search_range(uint32_t n, uint32_t m, const uint32_t *TM, const uint3
     const size_t o_tm = 2, o_nb = o_tm + tmb.size(), o_cf = o_nb + nb.size(), words = o_cf + ncoeffs;
     if (const int rc = cob_scratch(words)) return rc;
     std::vector<uint32_t> up(words);
-    memcpy(up.data(), &init, 8); memcpy(up.data() + o_tm, tmb.data(), tmb.size() * 4); memcpy(up.data() + o_nb, nb.data(), nb.size() * 4); memcpy(up.data() + o_cf, coeffs, (size_t)ncoeffs * 4);
+    memcpy(up.data(), &init, 8); memcpy(up.data() + o_tm, tmb.data(), tmb.size() * 4); memcpy(up.data() + o_nb, nb.data(), nb.size() * 4);
+    for (uint32_t x = 0; x < ncoeffs; ++x) up[o_cf + x] = coeffs[x] % p;      // (residues, as TM and Cand: zeros(w) counts them)
     uint32_t *d_tm = cx.cob_buf + o_tm, *d_nb = cx.cob_buf + o_nb, *d_cf = cx.cob_buf + o_cf; unsigned long long *d_best = (unsigned long long *)cx.cob_buf;
     plo::CobJob J{}; J.n = n; J.m = m; J.qn = qn; J.fb = fb; J.C = ncoeffs; J.p = p; J.mu = (~0ull) / p; J.first = first; J.total = total;
     J.tm = d_tm; J.nb = d_nb; J.coeffs = d_cf; J.best = d_best;
