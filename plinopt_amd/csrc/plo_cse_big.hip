@@ -47,10 +47,12 @@
 //              of the entry that the new column's entry inherits (chosen by the +-1 counts, :70-88, ONCE per row), placed as in a
 //              packed entry | the value indices of both removed entries.  Other modes: 32 bytes with the two packed entries.
 //   sweep      a wave owns every 8th rewritten row; modes 0/1 and the eager mode 2 take two rows per trip, a 64-lane chunk each;
-//              mode 2 with deferred updates takes the entries of its next 64 rows as ONE sequence, 64 per trip (the flat sweep:
-//              the lane's row from mark words, the row's record by four ds_bpermute, entries requested two trips ahead, two
-//              unconditional stores, one ratio-identifier lookup indexed by position (left or right of the a entry), one
-//              aligned-pair probe of the aggregation table: agg_add_rid_bm, a single-exit loop over pair indices).  That sweep keeps
+//              mode 2 with deferred updates takes the entries of its next 64 rows as ONE sequence of PAIRS of entries (2j, 2j + 1 of
+//              a row, whose length counts rounded up to even), 64 pairs = 128 entries per trip (the flat sweep: the lane's row from
+//              mark words, the row's record by four ds_bpermute, all once per pair; ONE 8-byte load per lane at a 4-byte aligned
+//              address, requested a trip ahead; per entry an unconditional store, a ratio-identifier lookup indexed by position
+//              (left or right of the a entry) and an aligned-pair probe of the aggregation table: agg_add_rid_bm, a single-exit
+//              loop over pair indices; the odd slot of a row of odd length is inactive).  That sweep keeps
 //              NO record of the slots it claims -- no list, no counter, and since the hash/bitmap change no bitmap either (5 vector
 //              and 1 LDS instruction per probe round, on nearly every trip): a claimed slot is one whose key word is not empty.
 //   flush      deferred updates with ratio identifiers: ONE pass; a thread owns 8 aligned pairs of slots of the aggregation table
@@ -103,7 +105,7 @@ struct BigPlan {
              o_tl, o_clen, o_keep;            // per-candidate row lists of the input columns (compacted as they are walked), live length per column, scratch
     // deferred cold updates (DEFER, see "deferred" below): hot table + partitioned store + update log instead of one big table
     uint32_t defer, pbits, capp, plcap, logcap, logtrig, hwin, hotbits_min, hotbits_max, lgrp;
-    uint32_t fwin;                        // entries per window of the flat sweep (2048 = 32 trips: the marks of a window are 32 words per wave; a test knob makes it smaller)
+    uint32_t fwin;                        // entries per window of the flat sweep (2048 = 1024 pairs = 16 trips; the marks of a window are 32 words per wave, one per trip; a test knob makes it smaller)
     const uint64_t *st0; const uint32_t *pcount0;     // store image: 2^pbits partitions of capp entries (key48<<16 | count16), entries per partition
     uint64_t o_store, o_pcount, o_ptail, o_log, o_plog, o_hot;
     uint32_t wide;                        // the slice's front region (everything but the table / store, which comes last) passes 4 GiB: kernels with 64-bit offsets
@@ -496,29 +498,6 @@ __device__ __forceinline__ bool agg_add_rid_bm(uint32_t *aggk, uint32_t *aggc32,
         if (mine || left == 0u) return mine;
     }
 }
-
-#ifdef PLO_BIG_PROFILE
-// First round of the same probe, written without a loop, with a clock after every LDS round trip (profile build): acc[0] pair read,
-// [1] compare-and-swap, [2] count.  Returns true when the key is NOT settled (both slots hold other keys, or the claim lost
-// to another key): the caller sends those lanes, ~0.2 % of them, through the loop.
-__device__ __forceinline__ bool agg_add_rid_first_prof(uint32_t *aggk, uint32_t *aggc32, uint32_t aggbits, uint32_t key, unsigned long long *acc) {
-    const unsigned long long c0 = clock64();
-    const uint32_t s = ((uint32_t)__umul24(key, 0x9E3779u) >> (32u - aggbits)) & ~1u;
-    const unsigned long long kk = __hip_atomic_load((unsigned long long *)(aggk + s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    const uint32_t k0 = (uint32_t)kk, k1 = (uint32_t)(kk >> 32);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long c1 = clock64();
-    const bool hit0 = k0 == key, hit = hit0 || k1 == key, emp0 = k0 == 0xFFFFFFFFu, tryc = !hit && (emp0 || k1 == 0xFFFFFFFFu);
-    const uint32_t sec = hit ? (hit0 ? 0u : 1u) : (emp0 ? 0u : 1u), t = s + sec;
-    uint32_t old = 0u;
-    if (tryc) old = wg_cas(&aggk[t], 0xFFFFFFFFu, key);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long c2 = clock64();
-    const bool ok = hit || (tryc && (old == 0xFFFFFFFFu || old == key));
-    if (ok) wg_add(&aggc32[s >> 1], sec ? 0x10000u : 1u);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long c3 = clock64();
-    acc[0] += c1 - c0; acc[1] += c2 - c1; acc[2] += c3 - c2;
-    return !ok;
-}
-#endif
 
 // packed row entry: column (15 bits) | +-1 flag (bit 15) | value index (16 bits)
 #define PLO_ECOL(e_) ((e_) & 0x7FFFu)
@@ -1287,34 +1266,22 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
             // rw (mode 2): the row's record word, PLO_RW_*: via and vib, the value indices of the row's two removed entries (they name v_a and v_b);
             // above: the entry lies right of the a entry (c > a) -- the sweeps know that from the positions, no column compare
 #ifdef PLO_BIG_PROFILE
-            uint32_t probe_iters = 0; unsigned long long pq[3] = {0, 0, 0}, prt = 0;
+            uint32_t probe_iters = 0; unsigned long long prt = 0;
 #endif
             // The hash's shift count lives in a vector register through the sweep: it is the one scalar of the trip's straight path
             // that found no scalar register (a v_readlane per trip), and the kernel has vector registers to spare for one word.
             uint32_t aggsh = 33u - aggbits; asm("" : "+v"(aggsh));
             const uint32_t agg_dual = MODE == 2 ? 0u : PW(agg_dual), logcap = DEFER ? PW(logcap) : 0u;       // (plan words of this phase; none is read inside the trip:
             // the kernel-argument pointer would have to be at hand there, and it is a spilled pair)
-            auto retire_entry = [&](uint32_t e, uint32_t rw, bool above, uint2 VA, uint2 VB, bool noagg = false) {      // noagg: the LDS table had no room for it (already tried)
+            auto retire_entry = [&](uint32_t e, uint32_t rw, bool above, uint2 VA, uint2 VB) {
                 const uint32_t c = PLO_ECOL(e);
                 // x = v_a/v_c (c < a) or v_c/v_a (c > a) names both retired pairs; y = v_a/v_c names the pair with the new column
                 // (x itself, or 1/x: kept beside x in the entry when the bits allow, so that the flush needs no inversion)
                 uint32_t x, y, q2, ins;                                        // q2: ratio of the pair with b; ins: ratio of the pair with the new column (both only on the fallback path)
                 if constexpr (MODE == 2) {
                     const uint32_t vi = PLO_EVI(e), via = rw >> PLO_RW_VIA;
-#ifdef PLO_BIG_PROFILE
-                    const unsigned long long cr0 = clock64();
-#endif
                     const uint32_t xid = rtid[((above ? vi : via) * PLO_RSTRIDE) | (above ? via : vi)];      // one lookup, no branch
-#ifdef PLO_BIG_PROFILE
-                    if constexpr (FAST) {
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); prt += clock64() - cr0;
-                        const bool pend = agg_add_rid_first_prof(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, pq);
-                        if (!__builtin_amdgcn_ballot_w64(pend)) return;
-                        if (!pend || agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggsh, &probe_iters)) return;
-                    }
-#else
-                    if constexpr (FAST) { if (!noagg) { if (__builtin_expect(agg_add_rid_bm(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, aggsh), 1)) return; } }
-#endif
+                    if constexpr (FAST) { }          // (the flat sweep comes here from retire_pair, for an entry whose key found no room in the LDS table)
                     else if (agg_add_rid(aggk, aggc32, aggbits, (c << PLO_RIDB) | xid, &sh.aggn, agglist, listcap)) return;
                     const uint32_t vib = (rw >> PLO_RW_VIB) & 31u;
                     const uint32_t bc = rval[rtid[vib * PLO_RSTRIDE + vi]];                                  // v_b / v_c
@@ -1371,6 +1338,38 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                 const uint32_t idx = wg_add(&sh.nspill, 1u);
                 if (idx < spillcap) spill[idx] = BKEY(c, lm, ins); else wg_max(&sh.errflag, (uint32_t)BERR_TABLE);
             };
+            // The flat sweep's unit: the two entries e0, e1 of a lane's pair (act0 / act1: the entry is retired; at least one is).  Both
+            // ratio identifiers are looked up first (two LDS reads in flight, one wait) -- via is shared, `above` differs only in a pair
+            // that holds position pa -- then each key goes through the probe loop; an entry whose key found no room goes the way of
+            // retire_entry's direct retirement.  (ONE loop that settles both keys of a lane one after the other was built and measured:
+            // 1,077 against 1,076 candidates/s, inside the runs' spread -- DESIGN.md 2.2, profiles/sweep_pairs_variants.patch.)
+            auto retire_pair = [&](uint32_t e0, uint32_t e1, bool act0, bool act1, uint32_t rw, bool above0, bool above1) {
+                if constexpr (FAST) {
+                    const uint32_t via = rw >> PLO_RW_VIA, vi0 = PLO_EVI(e0), vi1 = PLO_EVI(e1);
+#ifdef PLO_BIG_PROFILE
+                    const unsigned long long cr0 = clock64();
+#endif
+                    const uint32_t xid0 = rtid[((above0 ? vi0 : via) * PLO_RSTRIDE) | (above0 ? via : vi0)];
+                    const uint32_t xid1 = rtid[((above1 ? vi1 : via) * PLO_RSTRIDE) | (above1 ? via : vi1)];
+#ifdef PLO_BIG_PROFILE
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); prt += clock64() - cr0;
+#endif
+                    const uint32_t key0 = (PLO_ECOL(e0) << PLO_RIDB) | xid0, key1 = (PLO_ECOL(e1) << PLO_RIDB) | xid1;
+#ifdef PLO_BIG_PROFILE
+                    uint32_t *const it_ = &probe_iters;
+#else
+                    uint32_t *const it_ = nullptr;
+#endif
+                    // (bit 0: e0 found no room; bit 1: e1 did)
+                    uint32_t fail = 0u;
+                    if (act0 && !agg_add_rid_bm(aggk, aggc32, aggbits, key0, aggsh, it_)) fail |= 1u;
+                    if (act1 && !agg_add_rid_bm(aggk, aggc32, aggbits, key1, aggsh, it_)) fail |= 2u;
+                    if (__builtin_expect(fail != 0u, 0)) {
+                        if (fail & 1u) retire_entry(e0, rw, above0, make_uint2(0, 0), make_uint2(0, 0));
+                        if (fail & 2u) retire_entry(e1, rw, above1, make_uint2(0, 0), make_uint2(0, 0));
+                    }
+                }
+            };
             // The sweep proper.  A wave owns the rows wave, wave + nwaves, ... of the step and first loads the records of its
             // next 64 rows, ONE PER LANE (a record = row start, the two positions, and the two removed entries or, in mode 2, the word PLO_RW_*), reading
             // them back with v_readlane: no trip waits for a record -> row dependency.  Prefetches are unconditional
@@ -1390,8 +1389,15 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
             // comes from the lane that loaded it (ds_bpermute).
             // Stores of a trip reach back at most two positions and never into the next trip's entries (requested a trip
             // earlier), so no load sees a store.
+            // The UNIT of the sequence is a PAIR of entries 2j, 2j + 1 of one row (a row has 104 entries on average: what a lane does
+            // per row -- its row, the record fetch, the address, the load, leaving the probe loop -- is paid once per two entries):
+            // a row contributes its length rounded up to even, so a pair never spans rows; E, S, T, the marks, qlo and v_mbcnt count
+            // pairs and a trip covers 128 entries.  The odd slot of a row of odd length is inactive (position >= length); its half of
+            // the 8-byte load reads a word that exists, the next row's first entry or a spare word behind the array.  Row starts have
+            // either parity, so the load is 4-byte aligned only (EntPair).
+            struct __attribute__((packed, aligned(4))) EntPair { uint32_t x, y; };
             uint64_t *fm = sh.sel + 256u + 32u * wave;                  // (the bitmap of claimed slots takes at most the first 2 KB)
-            const uint32_t FW = PW(fwin);
+            const uint32_t FW = PW(fwin) >> 1;                            // pairs per window (fwin, in entries, is a multiple of 64: a window of the smallest knob values ends in the middle of its last trip)
             const uint32_t dump = PW(nnz) + 64u + lane;                   // (the entry array has 128 spare words)
             for (uint32_t k0 = 0; k0 < nrw; k0 += 64u) {
                 const bool have = k0 + lane < nrw;
@@ -1399,22 +1405,24 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                 const uint4 R0 = *(const uint4 *)(aff + 4u * qq);
                 const uint32_t Lr = have ? (R0.z & PLO_RW_LEN) : 0u;
                 const uint32_t RZ = R0.z;                               // the record word: the trips take via and vib from it
-                const uint32_t E = wave_incl_scan(Lr), S = E - Lr, T = RL(E, 63);
-                const uint32_t safe = RL(R0.y, 0);
+                const uint32_t Lp = (Lr + 1u) >> 1;                     // pairs of the row
+                const uint32_t E = wave_incl_scan(Lp), S = E - Lp, T = RL(E, 63);
+                const uint32_t safe = RL(R0.y, 0);                      // (a row has at least two entries: a whole pair can be read there)
                 uint32_t qlo = 0;
                 for (uint32_t w0 = 0; w0 < T; w0 += FW) {
                     if (w0 && tid == 0) ++sh.nwin;
                     if (lane < 32u) __hip_atomic_store(&fm[lane], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     __atomic_signal_fence(__ATOMIC_SEQ_CST); __builtin_amdgcn_wave_barrier();
-                    if (have && E >= w0 && E - w0 < FW) wg_or((unsigned long long *)&fm[(E - w0) >> 6], 1ull << (E & 63u));
+                    if (have && E >= w0 && E - w0 < FW) wg_or((unsigned long long *)&fm[(E - w0) >> 6], 1ull << ((E - w0) & 63u));
                     __atomic_signal_fence(__ATOMIC_SEQ_CST); __builtin_amdgcn_wave_barrier();
                     const uint64_t mreg = __hip_atomic_load(&fm[lane & 31u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     const uint32_t mrl = (uint32_t)mreg, mrh = (uint32_t)(mreg >> 32);
-                    const uint32_t ntw = ((T - w0 < FW ? T - w0 : FW) + 63u) >> 6;
+                    const uint32_t Tw = T - w0 < FW ? T : w0 + FW, ntw = (Tw - w0 + 63u) >> 6;      // the window's end in the sequence, its trips
                     // Trip t_: the row of each lane (advances qlo), the row's record fetched from the lane that holds it -- four
-                    // ds_bpermute in flight together, one wait -- and the request for the entry.  A mark at bit i says "a row ended
-                    // before position i": rows ended at or below a lane = bit 0 + v_mbcnt of the mask shifted right by one.
-                    auto prep = [&](uint32_t t_, uint32_t &ad_, uint32_t &z_, uint32_t &pp_, uint32_t &rz_, uint32_t &e_) {
+                    // ds_bpermute in flight together, one wait -- and the request for the lane's pair of entries (z_: the position of
+                    // its first, even).  A mark at bit i says "a row ended before pair i": rows ended at or below a lane = bit 0 +
+                    // v_mbcnt of the mask shifted right by one.
+                    auto prep = [&](uint32_t t_, uint32_t &ad_, uint32_t &z_, uint32_t &pp_, uint32_t &rz_, EntPair &e_) {
                         const bool ok = t_ < ntw;                          // (the trip after the window's last one is requested nowhere and marks nothing)
                         const uint32_t ml_ = RL(mrl, t_ & 31u), mh_ = RL(mrh, t_ & 31u);      // (read unconditionally, then selected: behind `ok ?` each readlane sat in a branch of its own)
                         const uint32_t ml = ok ? ml_ : 0u, mh = ok ? mh_ : 0u;
@@ -1424,62 +1432,51 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                         const uint32_t rb_ = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)R0.y), S_ = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)S);
                         pp_ = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)R0.x); rz_ = (uint32_t)__builtin_amdgcn_ds_bpermute(qa, (int)RZ);
                         const uint32_t f_ = w0 + (t_ << 6) + lane;
-                        z_ = f_ - S_; ad_ = rb_ + z_;
-                        e_ = ent[ok && f_ < T ? ad_ : safe];
+                        z_ = (f_ - S_) << 1; ad_ = rb_ + z_;
+                        e_ = *(const EntPair *)&ent[f_ < Tw ? ad_ : safe];          // (a trip past the window's last one lies behind Tw)
                     };
-#if !defined(PLO_BIG_PROFILE)
-                    // Round 4 (default): entries are requested TWO trips ahead and the loop is unrolled three times, so that the three sets
-                    // of trip registers (address, position in the row, the row's record words, the entry) rotate by NAME.  The one-ahead loop
-                    // below ends in `ec = en`: a copy of the entry requested at the top of the same trip, i.e. a wait for that load at the
-                    // bottom of every trip -- a load had one trip body (~1,500 cycles) to come back, and with 512 workgroups in flight it
-                    // takes longer (a first two-ahead version that kept the copies gained nothing: the copy of the newest set waited just
-                    // the same).  A store of a trip goes at most two positions below the storing entry's own address, which the same or an
-                    // earlier trip has loaded: no load of a later trip, however early, sees it.  816 -> 840-846 candidates/s A/B on one box,
-                    // a candidate alone 436 -> 421 ms (profiles/r04_ab_config5.txt); three trips ahead (four sets): 832, the registers spill.
-                    auto body3 = [&](uint32_t t, uint32_t adc, uint32_t zc, uint32_t ppc, uint32_t rzc, uint32_t ec) {
-                        const uint32_t pa = ppc & 0xFFFFu, pb = ppc >> 16;
-                        const bool in = w0 + (t << 6) + lane < T, act = in && zc != pa && zc != pb;
-                        // (the UNCONDITIONAL store: see the one-ahead loop below)
-                        ent[act && zc > pa ? adc - 1u - (zc > pb ? 1u : 0u) : dump] = ec;
-                        if (act) retire_entry(ec, rzc, zc > pa, make_uint2(0, 0), make_uint2(0, 0));
-                    };
-                    uint32_t a0_, z0_, p0_, r0_, e0_, a1_, z1_, p1_, r1_, e1_, a2_, z2_, p2_, r2_, e2_;
-                    prep(0u, a0_, z0_, p0_, r0_, e0_); prep(1u, a1_, z1_, p1_, r1_, e1_);
-                    __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0): see the one-ahead loop below
-                    for (uint32_t t = 0;;) {
-                        prep(t + 2u, a2_, z2_, p2_, r2_, e2_); body3(t, a0_, z0_, p0_, r0_, e0_); if (++t >= ntw) break;
-                        prep(t + 2u, a0_, z0_, p0_, r0_, e0_); body3(t, a1_, z1_, p1_, r1_, e1_); if (++t >= ntw) break;
-                        prep(t + 2u, a1_, z1_, p1_, r1_, e1_); body3(t, a2_, z2_, p2_, r2_, e2_); if (++t >= ntw) break;
-                    }
-#else
-                    uint32_t adc, zc, ppc, rzc, ec; prep(0u, adc, zc, ppc, rzc, ec);
-                    // (the wait counters of the loop header merge both incoming edges: with the first entry still in flight here every
-                    // trip would wait for all but one memory operation, i.e. for the stores of the trip before)
-                    __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0)
-                    for (uint32_t t = 0; t < ntw; ++t) {
-                        uint32_t adn, zn, ppn, rzn, en; prep(t + 1u, adn, zn, ppn, rzn, en);
+                    // A trip's work on its pairs.  The row is rewritten in the same pass (:96-110): entries right of the first removed
+                    // position shift left by one, right of the second by two (the new column's entry goes last, at the end of the
+                    // batch: below).  TWO 4-byte stores, one per entry: the two entries of a pair shift alike whenever both are
+                    // stored, but an 8-byte store for that case needs a 4-byte one beside it for the pairs that hold a removed
+                    // position or the odd slot, with a selected entry and address of its own (profiles/sweep_pairs_budget.txt).  The
+                    // stores are UNCONDITIONAL (idle lanes write to a dump word behind the entries): behind a branch the compiler
+                    // cannot count them and waits for every store of the trip (vmcnt(0)) before it uses the pair requested ahead.
+                    // A store goes at most two positions below its entry and never forward, to a position that the same trip or an
+                    // earlier one has loaded: no load of a later trip, however early, sees it.
+                    auto body = [&](uint32_t t, uint32_t adc, uint32_t zc, uint32_t ppc, uint32_t rzc, EntPair ec) {
 #ifdef PLO_BIG_PROFILE
                         const unsigned long long t0_ = clock64();
 #endif
-                        const uint32_t pa = ppc & 0xFFFFu, pb = ppc >> 16;
-                        const bool in = w0 + (t << 6) + lane < T, act = in && zc != pa && zc != pb;
-                        // the row is rewritten in the same pass (:96-110): entries right of the first removed position shift left
-                        // (the new column's entry goes last, at the end of the batch: below).  The store is UNCONDITIONAL (idle
-                        // lanes write to a dump word behind the entries): behind a branch the compiler cannot count it and waits
-                        // for every store of the trip (vmcnt(0)) before it uses the entry requested a trip ahead.
-                        ent[act && zc > pa ? adc - 1u - (zc > pb ? 1u : 0u) : dump] = ec;
+                        const uint32_t pa = ppc & 0xFFFFu, pb = ppc >> 16, z1 = zc + 1u;
+                        const bool in = w0 + (t << 6) + lane < Tw;
+                        const bool act0 = in && zc != pa && zc != pb, act1 = in && z1 < (rzc & PLO_RW_LEN) && z1 != pa && z1 != pb;
+                        ent[act0 && zc > pa ? adc - 1u - (zc > pb ? 1u : 0u) : dump] = ec.x;
+                        ent[act1 && z1 > pa ? adc - (z1 > pb ? 1u : 0u) : dump] = ec.y;
 #ifdef PLO_BIG_PROFILE
                         __builtin_amdgcn_wave_barrier(); const unsigned long long t1_ = clock64(); probe_iters = 0;
 #endif
-                        if (act) retire_entry(ec, rzc, zc > pa, make_uint2(0, 0), make_uint2(0, 0));
+                        if (act0 || act1) retire_pair(ec.x, ec.y, act0, act1, rzc, zc > pa, z1 > pa);
 #ifdef PLO_BIG_PROFILE
                         {   __builtin_amdgcn_wave_barrier(); const unsigned long long t2_ = clock64(); pw0 += t1_ - t0_; pw1 += t2_ - t1_; pw2 += t0_ - tl_; tl_ = t2_; ++ptr;
                             uint32_t mx = probe_iters; for (int o = 1; o < 64; o <<= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)mx, o); mx = u > mx ? u : mx; }
-                            pit += mx; pact += (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(act)); tl_ = clock64(); }
+                            pit += mx; pact += (unsigned long long)(__builtin_popcountll(__builtin_amdgcn_ballot_w64(act0)) + __builtin_popcountll(__builtin_amdgcn_ballot_w64(act1))); tl_ = clock64(); }
 #endif
-                        adc = adn; zc = zn; ppc = ppn; rzc = rzn; ec = en;
+                    };
+                    // Pairs are requested ONE trip ahead and the loop is unrolled twice, so that the two sets of trip registers (address,
+                    // position in the row, the row's record words, the pair) rotate by NAME: a loop that ends in copies `current = next`
+                    // waits at its bottom for the load requested at its top (round 4: 816 -> 840-846 candidates/s without the copies,
+                    // nothing with them).  Single entries were requested two trips ahead from three sets; a trip of pairs is nearly
+                    // twice as long, and two ahead measured the same as one (1,074-1,076 against 1,076-1,078 candidates/s).
+                    uint32_t a0_, z0_, p0_, r0_, a1_, z1_, p1_, r1_; EntPair e0_, e1_;
+                    prep(0u, a0_, z0_, p0_, r0_, e0_);
+                    // (the wait counters of the loop header merge both incoming edges: with the first pairs still in flight here every
+                    // trip would wait for all but one memory operation, i.e. for the stores of the trip before)
+                    __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0)
+                    for (uint32_t t = 0;;) {
+                        prep(t + 1u, a1_, z1_, p1_, r1_, e1_); body(t, a0_, z0_, p0_, r0_, e0_); if (++t >= ntw) break;
+                        prep(t + 1u, a0_, z0_, p0_, r0_, e0_); body(t, a1_, z1_, p1_, r1_, e1_); if (++t >= ntw) break;
                     }
-#endif
                 }
                 // The new column's entry goes last (len and the +-1 counters were updated by the search): ONE store per row, by the
                 // lane that holds the row's record, not a test and a store in every trip (one lane in a hundred had anything to
@@ -1549,7 +1546,7 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
                 }
             }
 #ifdef PLO_BIG_PROFILE
-            if (lane == 0 && M >= 256u) { atomicAdd(&sh.pw[0], pw0); atomicAdd(&sh.pw[1], pw1); atomicAdd(&sh.pw[2], pw2); atomicAdd(&sh.pw[3], ptr); atomicAdd(&sh.pw[4], clock64() - ts_); atomicAdd(&sh.pw[5], 1ull); atomicAdd(&sh.pw[6], pit); atomicAdd(&sh.pw[7], pact); atomicAdd(&sh.pw[8], pq[0]); atomicAdd(&sh.pw[9], pq[1]); atomicAdd(&sh.pw[10], pq[2]); atomicAdd(&sh.pw[14], prt); }
+            if (lane == 0 && M >= 256u) { atomicAdd(&sh.pw[0], pw0); atomicAdd(&sh.pw[1], pw1); atomicAdd(&sh.pw[2], pw2); atomicAdd(&sh.pw[3], ptr); atomicAdd(&sh.pw[4], clock64() - ts_); atomicAdd(&sh.pw[5], 1ull); atomicAdd(&sh.pw[6], pit); atomicAdd(&sh.pw[7], pact); atomicAdd(&sh.pw[14], prt); }
 #endif
         }
 #undef RL
