@@ -351,7 +351,9 @@ int build_plan(plo_plan *pl, std::vector<uint8_t> *img_out = nullptr)
     pl->pairs0 = pairs0; pl->distinct0 = pm.size();
     pl->algo_bytes = 8ull * nnz + 12ull * pairs0 + 8ull;   // B_cand, SURVEY.md 8(d)
     uint32_t cap = 64;
-    while (cap < (pl->cap_scale * (uint32_t)pm.size() * 3u) / 4u + 16u) cap <<= 1;   // 1.5x the initial triples (cap_scale starts at 2); a full table is detected on the device and the launch repeated with more
+    while (cap < (2u * (uint32_t)pm.size() * 3u) / 4u + 16u) cap <<= 1;   // 1.5x the initial triples; a full table is detected on the device and the launch repeated with more
+    cap *= pl->cap_scale / 2u;              // cap_scale starts at 2 and doubles per repeat: every repeat has twice the slots.  (Sized from cap_scale x the triples, a repeat of a matrix of few
+                                            // pairs kept its 64 slots: ProgramGen's (column, |v|) keys, which the triples do not bound, then filled the same table in every repeat.)
     if (env_knob("PLO_WAVE_CAP_TIGHT")) {   // test knob: the first table just holds the initial triples and one empty slot (the insertion loop below ends), so that
         cap = 64;                           // a candidate whose live triples grow takes the repeat path; 64 slots at least, the kernel scans the table a wave at a time
         while (cap < (uint32_t)pm.size() + 1u) cap <<= 1;

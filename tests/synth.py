@@ -801,8 +801,9 @@ def wave_plan(m, n, rows, p, cap_scale=2, tight=False):
             cap *= 2
         cap *= cap_scale // 2
     else:
-        while cap < cap_scale * len(triples) * 3 // 4 + 16:
+        while cap < 2 * len(triples) * 3 // 4 + 16:
             cap *= 2
+        cap *= cap_scale // 2                                    # every repeat has twice the slots
     if cap > 65536:
         return "PLO_E_CAPACITY"
     multcap = 0 if unit else naive // 2 + 8
@@ -956,4 +957,287 @@ def chain_cases():
     _chain_case(out, "1984x2_second", "refuse", tiny, u1984, refusal=C)
     _chain_case(out, "gen65x2_first", "refuse", g65, tiny, refusal=C)
     _chain_case(out, "gen65x2_second", "refuse", tiny, g65, refusal=C)
+    return out
+
+
+# ======================================================================================================================
+# Edge-shape cases for the one-wave CSE kernel itself (plo_cse_wave.hip run_candidate / program_gen_general through CSEPlan:
+# cost_many, search, the -E walk and the plan's own table-full relaunch).  No golden costs: the oracle (oracle/plo_oracle.c)
+# scores every case in milliseconds, tests/test_cse_cases_host.py holds each case to the property it was built for and
+# tests/test_gpu_cse_edges.py the kernel to the oracle; tests/golden/cse_cases.json pins names, shapes and matrices.
+#
+# Every case states the branch boundary it sits on and asserts it here, from the matrix alone: the number of triples of
+# maximal frequency (the tie pick's three paths: 1, <= 64, > 64), the rows that hold both columns of the first step against
+# G = 64 >> lpr_log2 (one trip or the two sweeps), the (column, |v|) keys of ProgramGen against the slots of the pair table
+# they share, the mask words, the row-length class, the key width.  Where a property needed a search over generator seeds
+# (22 x 40 matrices of maximal frequency 2 with 63..66 tied triples are some 0.01 % of the seeds) the seed found is the
+# constant below.
+# ======================================================================================================================
+CSE_PRIME = CHAIN_PRIME
+CSE_MODULI = [3, 5, 7, 65521, 65537, 2147483629, 2147483647]
+CSE_RUN, CSE_TIE_RUN = (0, 8), (0, 16)                           # the (seed0, n) run: 16 seeds where the costs must vary
+CSE_SEEDS = [2 ** 64 - 1, 2 ** 63, 2 ** 40 + 7, 5, 5]            # the explicit list: the ends, above 2^40, one seed twice
+CSE_ENUM = 64                                                    # schedule indices walked from 0 and from CSE_ENUM_FAR
+CSE_ENUM_FAR = 10 ** 12 + 12345
+CSE_GEN = [1, -1, 2, 3]
+CSE_TIE_SEED = 0xC5E0000                                         # 22 x 40, seven +-1 per row: offset -> tied triples (frequency 2)
+CSE_TIE_UNIT = {63: 1510, 64: 60977, 65: 5083, 66: 42557}
+CSE_TIE_BLOCKS = {128: (3821, 58750), 129: (10684, 58750)}       # two such blocks on the diagonal: 60 + 68 and 61 + 68
+CSE_TIE_GEN_SEED, CSE_TIE_GEN = 0xC5E6000, {63: 1, 64: 2, 65: 1, 66: 3}   # the general construction: the first draws whose costs take five values over 16 seeds
+CSE_TIE_FEW = {1: 0xC5E1000 + 7919 * 12, 2: 0xC5E1000 + 7919 * 12 + 51}   # 12 x 40: one and two triples of frequency 3
+
+
+def cse_triples(rows, p):
+    """{(column a, column b, ratio): rows that hold it} of the initial pair table (listpairs), a < b"""
+    t = {}
+    for r in rows:
+        e = sorted((j, v % p) for j, v in r.items() if v % p)
+        for x in range(len(e)):
+            for y in range(x + 1, len(e)):
+                k = (e[x][0], e[y][0], e[y][1] * pow(e[x][1], -1, p) % p)
+                t[k] = t.get(k, 0) + 1
+    return t
+
+
+def cse_top(rows, p):
+    """(maximal frequency, the triples that have it in map order)"""
+    t = cse_triples(rows, p)
+    mf = max(list(t.values()) + [0])
+    return mf, sorted(k for k, v in t.items() if v == mf)
+
+
+def cse_group(maxlen):
+    """(lpr_log2, G): lanes per row and rows per trip of the sweeps, as build_plan sets them from the longest row"""
+    lpr = max(2, _clog2(max(maxlen, 1)))
+    return lpr, 64 >> lpr
+
+
+def cse_pgen_keys(rows, p):
+    """the (column, |v|) keys that ProgramGen's pass A1 inserts into the pair table's slots when no CSE step ran before"""
+    return {(j, min(v % p, p - v % p)) for r in rows for j, v in r.items() if v % p not in (0, 1, p - 1)}
+
+
+def _cse_case(out, name, family, n, rows, p=CSE_PRIME, run=CSE_RUN, enum=0, refusal=None, **prop):
+    """rows: one {column: signed value} per row; the case holds the residues.  prop: what the case was built for"""
+    m = len(rows)
+    assert all(0 <= j < n and v % p for r in rows for j, v in r.items()), name
+    rows = [{j: v % p for j, v in r.items()} for r in rows]
+    plan = wave_plan(m, n, rows, p)
+    assert (plan if isinstance(plan, str) else None) == refusal, (name, plan)
+    mf, top = cse_top(rows, p)
+    maxlen = max(len(r) for r in rows)
+    lpr, G = cse_group(maxlen)
+    c = SimpleNamespace(name="cse_%s_%s" % (family, name), family=family, m=m, n=n, rows=rows, p=p, csr=(m, n) + to_csr(rows, p), plan=plan,
+                        hbm=refusal is not None, run=run, seeds=[] if refusal else list(CSE_SEEDS), enum=enum, maxfreq=mf, T=len(top), top=top,
+                        maxlen=maxlen, lpr_log2=lpr, G=G, keys=len(cse_pgen_keys(rows, p)), prop=prop, sha256=_sha(km_text(m, n, p, rows)))
+    assert not (enum and refusal) and c.name not in [x.name for x in out], c.name
+    out.append(c)
+    return c
+
+
+def _unit_rows(seed, m, n=40, k=7, shift=0):
+    rng = random.Random(seed)
+    return [{shift + j: _pick(rng, [1, -1]) for j in _sample(rng, range(n), k)} for _ in range(m)]
+
+
+def _holders(rows, a, b):
+    return [i for i, r in enumerate(rows) if a in r and b in r]
+
+
+def _forced(c, share, ratio):
+    """the first step is forced: (0, 1, ratio) is the only triple of frequency >= 2, and `share` rows hold it"""
+    t = cse_triples(c.rows, c.p)
+    assert c.top == [(0, 1, ratio % c.p)] and c.maxfreq == share and sorted(t.values())[-2] == 1, c.name
+
+
+def _group_rows(rng, L, share, vals, ratio, other=None):
+    """`share` rows of L entries with columns 0 and 1 at `ratio`, the other L - 2 entries of each row in columns of its own;
+    other: the ratio of one more row that holds both columns, put in the middle of the rows"""
+    rows, n = [], 2
+    for i in range(share + (other is not None)):
+        u = _pick(rng, vals)
+        r = {0: u, 1: u * (other if other is not None and i == share // 2 else ratio)}
+        for _ in range(L - 2):
+            r[n] = _pick(rng, vals)
+            n += 1
+        rows.append(r)
+    return n, rows
+
+
+def _near_rows(rng, k, vals):
+    """k rows of 64 entries over the same 64 columns that differ from the first in three entries each"""
+    base = {j: _pick(rng, vals) for j in range(64)}
+    rows = [dict(base)]
+    for _ in range(k - 1):
+        r = dict(base)
+        for j in _sample(rng, range(64), 3):
+            r[j] = -r[j]
+        rows.append(r)
+    return 64, rows
+
+
+def _factor_rows():
+    """two rows over 64 columns without one triple in common (the quotients r1[j] / r0[j] are pairwise distinct, so no CSE step
+    runs), no (column, |v|) twice, every |v| of 2..9 several times in each row and under both signs: FactorOutRows at LPR = 64"""
+    vals = [s * a for a in range(2, 10) for s in (1, -1)]
+    every = [(x, y) for x in vals for y in vals if abs(x) != abs(y)]
+    random.Random(0xFAC7).shuffle(every)
+    pairs, seen = [], set()
+    for x, y in every:
+        if F(y, x) not in seen and len(pairs) < 64:
+            seen.add(F(y, x))
+            pairs.append((x, y))
+    assert len(pairs) == 64
+    rows = [{j: xy[0] for j, xy in enumerate(pairs)}, {j: xy[1] for j, xy in enumerate(pairs)}]
+    for r in rows:
+        for a in range(2, 10):
+            assert sum(v == a for v in r.values()) >= 1 and sum(v == -a for v in r.values()) >= 1 and sum(abs(v) == a for v in r.values()) >= 3, (a, r)
+    return 64, rows
+
+
+def cse_cases():
+    """89 matrices at the branch boundaries of run_candidate and program_gen_general, two of them sent to the HBM family."""
+    rng = random.Random(0xC5E)
+    out = []
+    P = CSE_PRIME
+    # ---- tie: the triples of maximal frequency at the start: 1, 2 (rank by readlane), 63, 64 (a full wave of ties), 65, 66, 128, 129
+    # (bisection on the key, tie list in blocks of 64).  +-1: random rows; the costs vary with the seed.  -E on 63/64/65: the
+    # maximal frequency is 2, so the children of the root are these same triples
+    for T, s in sorted(CSE_TIE_FEW.items()):
+        c = _cse_case(out, "unit_T%d" % T, "tie", 40, _unit_rows(s, 12), run=CSE_TIE_RUN)
+        assert (c.T, c.maxfreq) == (T, 3), (c.name, c.T, c.maxfreq)
+    for T, s in sorted(CSE_TIE_UNIT.items()):
+        c = _cse_case(out, "unit_T%d" % T, "tie", 40, _unit_rows(CSE_TIE_SEED + s, 22), run=CSE_TIE_RUN, enum=CSE_ENUM if T <= 65 else 0)
+        assert (c.T, c.maxfreq) == (T, 2), (c.name, c.T, c.maxfreq)
+    for T, (s1, s2) in sorted(CSE_TIE_BLOCKS.items()):
+        c = _cse_case(out, "unit_T%d" % T, "tie", 80, _unit_rows(CSE_TIE_SEED + s1, 22) + _unit_rows(CSE_TIE_SEED + s2, 22, shift=40), run=CSE_TIE_RUN)
+        assert (c.T, c.maxfreq) == (T, 2), (c.name, c.T, c.maxfreq)
+    # general: two identical rows of 11 entries (55 triples of frequency 2) and k - 55 identical pairs of two-entry rows in columns of their own
+    for k, s in sorted(CSE_TIE_GEN.items()):
+        r2 = random.Random(CSE_TIE_GEN_SEED + 100 * k + s)
+        first = {j: _pick(r2, [2, 3, -2, 1]) for j in range(11)}
+        rows, n = [dict(first), dict(first)], 11
+        for _ in range(k - 55):
+            r = {n: _pick(r2, [2, 3, -2, 1]), n + 1: _pick(r2, [2, 3, -2, 1])}
+            rows += [dict(r), dict(r)]
+            n += 2
+        c = _cse_case(out, "gen_T%d" % k, "tie", n, rows, run=CSE_TIE_RUN, enum=CSE_ENUM if k <= 65 else 0)
+        assert (c.T, c.maxfreq) == (k, 2) and not c.plan.unit, (c.name, c.T, c.maxfreq)
+    # ---- group: the first step rewrites exactly G, and exactly G + 1, rows (G = 64 >> lpr_log2 rows per trip: at most G rows holding
+    # both columns take the one-trip path, more the two sweeps).  The step is forced.  General: one more row holds both columns at
+    # another ratio (in the mask, not rewritten), so G rows of the triple already take the sweeps; Gm1 is the one-trip path with such a row
+    for L in (4, 8, 16, 32):
+        lpr, G = cse_group(L)
+        for share, tag in ((G, "G"), (G + 1, "G1")):
+            n, rows = _group_rows(rng, L, share, [1, -1], 1)
+            c = _cse_case(out, "L%d_unit_%s" % (L, tag), "group", n, rows, share=share, mask=share)
+            _forced(c, share, 1)
+            assert c.G == G and c.maxlen == L and len(_holders(c.rows, 0, 1)) == share and c.plan.unit
+        for share, tag in ((G - 1, "Gm1"), (G, "G"), (G + 1, "G1")):
+            if share < 2:
+                continue
+            n, rows = _group_rows(rng, L, share, [1, -1, 2, -2], 3, other=2)
+            c = _cse_case(out, "L%d_gen_%s" % (L, tag), "group", n, rows, share=share, mask=share + 1)
+            _forced(c, share, 3)
+            assert c.G == G and c.maxlen == L and len(_holders(c.rows, 0, 1)) == share + 1 and not c.plan.unit
+    # L = 64: G = 1, every step takes the sweeps, one row per trip.  (Rows of 64 entries in columns of their own do not fit the LDS.)
+    for k in (2, 3):
+        for fl, vals in (("unit", [1, -1]), ("gen", CSE_GEN)):
+            c = _cse_case(out, "L64_%s_%drows" % (fl, k), "group", *_near_rows(rng, k, vals), share=k, mask=k)
+            assert c.G == 1 and c.maxlen == 64 and c.maxfreq == k and c.plan.unit == (fl == "unit")
+    # ---- rowlen: the lpr_log2 classes at their boundaries, and a row count that is no multiple of G: the last trip of the r0 += G
+    # loops (ProgramGen) is partial.  A row of 65 entries goes to the HBM family
+    for L, m in ((4, 19), (5, 11), (8, 11), (9, 7), (16, 7), (17, 5), (32, 5), (33, 3), (64, 3)):
+        lpr, G = cse_group(L)
+        lens = [max(2, L - i * L // m) for i in range(m)]
+        for fl, vals in (("unit", [1, -1]), ("gen", CSE_GEN)):
+            c = _cse_case(out, "L%d_%s" % (L, fl), "rowlen", L + 2, _rows(rng, L + 2, lens, vals))
+            assert c.maxlen == L and (c.lpr_log2, c.G) == (lpr, G) and (G == 1 or m % G) and c.maxfreq >= 2 and c.plan.unit == (fl == "unit")
+    assert sorted({c.lpr_log2 for c in out if c.family == "rowlen"}) == [2, 3, 4, 5, 6]
+    c = _cse_case(out, "L65_unit", "rowlen", 70, _rows(rng, 70, [65, 3, 2], [1, -1]), refusal="PLO_E_CAPACITY")
+    assert c.maxlen == 65
+    # ---- mw: +-1 matrices of 63 .. 129 rows (one, two and three mask words), and one whose first step rewrites 40 rows: 34 in word 0
+    # up to row 63 (more than G = 8 of them: several trips inside a word) and 6 in word 1 from row 64
+    for m in (63, 64, 65, 128, 129):
+        c = _cse_case(out, "%dx5" % m, "mw", *_dense(rng, m, 5, [1, -1], 0.8))
+        assert c.plan.mw == (m + 63) // 64 and c.plan.unit
+    rows = []
+    for i in range(100):
+        r = {j: _pick(rng, [1, -1]) for j in range(2, 7) if rng.random() < 0.6}
+        if 30 <= i < 70:
+            r[0] = r[1] = _pick(rng, [1, -1])
+        rows.append(r)
+    c = _cse_case(out, "straddle_100x7", "mw", 7, rows, share=40)
+    held = _holders(c.rows, 0, 1)
+    assert c.top == [(0, 1, 1)] and c.maxfreq == 40 and held == list(range(30, 70)) and c.plan.mw == 2 and c.G == 8
+    # ---- pgen_table: ProgramGen's (column, |v|) keys against the slots of the pair table, which build_plan sizes from the triples.
+    # a, b: exactly full (tab_find on a table without an empty slot); c: 84 keys for 64 slots; d: b with rows 0 and 1 sharing column 0 --
+    # Triangle finds the quotient 6 / -2 = -3 in row 1 and records the SIGNED -2 in `multiples`: key 129 of 128 slots; e: two pairs, 66
+    # keys -- the slots that twice the triples ask for are 64 again: the repeat must double the slots, not the estimate
+    c = _cse_case(out, "a_64x1", "pgen_table", 64, [{i: 2 + i} for i in range(64)], costs=(0, 64), launches=1)
+    assert (c.plan.cap, c.keys, c.plan.distinct) == (64, 64, 0)
+    c = _cse_case(out, "b_64x2", "pgen_table", 128, [{2 * i: 2 + 2 * i, 2 * i + 1: 3 + 2 * i} for i in range(64)], costs=(64, 128), launches=1)
+    assert (c.plan.cap, c.keys, c.plan.distinct, c.maxfreq) == (128, 128, 64, 1)
+    rows = [{2 * i: 2 + 2 * i, 2 * i + 1: 3 + 2 * i} for i in range(20)] + [{40 + i: 50 + i} for i in range(44)]
+    c = _cse_case(out, "c_20x2_44x1", "pgen_table", 84, rows, costs=(20, 84), launches=2)
+    assert (c.plan.cap, c.keys, c.plan.distinct, c.maxfreq) == (64, 84, 20, 1) and wave_plan(c.m, c.n, c.rows, P, cap_scale=4).cap == 128
+    rows = [{0: -2, 1: 5}, {0: 6, 2: 3}] + [{2 * i - 1: 5 + 2 * i, 2 * i: 6 + 2 * i} for i in range(2, 64)]
+    c = _cse_case(out, "d_triangle", "pgen_table", 127, rows, launches=2)
+    assert (c.plan.cap, c.keys, c.plan.distinct, c.maxfreq) == (128, 128, 64, 1) and wave_plan(c.m, c.n, c.rows, P, cap_scale=4).cap == 256
+    q = c.rows[1][0] * pow(c.rows[0][0], -1, P) % P               # the couple (row 0, row 1) of column 0 and its quotient in row 1
+    assert P - q == c.rows[1][2] == 3 and c.rows[0][0] == P - 2 and (0, P - 2) not in cse_pgen_keys(c.rows, P)
+    rows = [{0: 2, 1: 3}, {2: 4, 3: 5}] + [{4 + i: 6 + i} for i in range(62)]
+    c = _cse_case(out, "e_2x2_62x1", "pgen_table", 66, rows, costs=(2, 66), launches=2)
+    assert (c.plan.cap, c.keys, c.plan.distinct) == (64, 66, 2) and wave_plan(c.m, c.n, c.rows, P, cap_scale=4).cap == 128
+    # ---- pgen_shape: ProgramGen for general coefficients at full width
+    for m in (63, 64):                                           # one row per lane in Triangle, the last lane idle / busy
+        c = _cse_case(out, "gen%dx6" % m, "pgen_shape", *_dense(rng, m, 6, [1, -1, 2, 3, -2], 0.8), random=True)
+        assert not c.plan.unit and c.plan.mw == 1
+    # column 0 is non +-1 in all 64 rows, |v| = 2 .. 65 (nothing for FactorOutColumns); every odd row holds the quotient of its entry by the
+    # row's above in a column of its own: Triangle fires on the couples (0, 1), (2, 3), ... 32 times in column 0, after the first one through
+    # the `found` shortcut; every eighth pivot is negative (a new key of `multiples`)
+    rows = []
+    for i in range(64):
+        a = (i + 2) * (-1 if i % 8 == 0 else 1)
+        r = {0: a, 1 + i: 1}
+        if i % 2:
+            r[1 + i] = a * pow(rows[-1][0], -1, P) % P * (-1 if i % 4 == 1 else 1)
+        rows.append(r)
+    c = _cse_case(out, "triangle_64", "pgen_shape", 65, rows, couples=32)
+    assert c.maxfreq == 1 and all(v % P not in (1, P - 1) for r in c.rows for j, v in r.items() if j == 0 or j % 2 == 0) and c.keys + 8 <= c.plan.cap
+    # the never-reset `found`: after the couple (0, 1) only the first couple of what is left is looked at -- rows 2 and 3, which have no
+    # quotient, and not rows 2 and 4, which have one: 6 multiplications, 5 for a scan that starts over
+    rows = [{0: 2, 1: 1}, {0: 3, 2: 3 * pow(2, -1, P)}, {0: 5, 3: 1}, {0: 7, 4: 1}, {0: 11, 5: 11 * pow(5, -1, P)}]
+    c = _cse_case(out, "triangle_found", "pgen_shape", 6, rows, costs=(5, 6))
+    assert c.maxfreq == 1 and c.rows[4][5] * c.rows[2][0] % P == c.rows[4][0] and c.rows[3][4] == 1
+    c = _cse_case(out, "factor_rows_2x64", "pgen_shape", *_factor_rows())
+    assert c.maxfreq == 1 and c.maxlen == 64 and c.G == 1 and c.keys == 128
+    # 22 blocks of two proportional rows over four columns of their own: three steps per block, each with a ratio that is no +-1 and a
+    # column l1 of its own -- 66 multipliers when ProgramGen starts (the s0 += 64 loops over the multiplier list take two trips), and
+    # 132 tied triples at the start.  The dense 30 x 8 matrix over 2 .. 39 has some 800 triples of which few repeat
+    rows = []
+    for b in range(22):
+        w = _sample(rng, range(2, 40), 4)
+        k = _pick(rng, [-1, 2, 3])
+        rows += [{4 * b + j: w[j] for j in range(4)}, {4 * b + j: k * w[j] for j in range(4)}]
+    c = _cse_case(out, "mult66_blocks", "pgen_shape", 88, rows, multipliers=66)
+    assert (c.T, c.maxfreq) == (132, 2) and sum(len(r) - 1 for r in c.rows) >= 130
+    c = _cse_case(out, "dense30x8", "pgen_shape", *_dense(rng, 30, 8, list(range(2, 40))))
+    assert sum(len(r) - 1 for r in c.rows) >= 130
+    # ---- moduli: rb from 2 to 31 bits (at 3 every residue is +-1), both branches of fmul, and the key of exactly 51 bits
+    mu, mg = _dense(rng, 10, 7, [1, -1], 0.8), _dense(rng, 10, 7, [1, -1, 2, 3, 5, 6], 0.8)
+    for p in CSE_MODULI:
+        _cse_case(out, "unit_mod%d" % p, "moduli", *mu, p=p)
+        c = _cse_case(out, "gen_mod%d" % p, "moduli", mg[0], [{j: (v if v % p else 1) for j, v in r.items()} for r in mg[1]], p=p)
+        assert c.plan.unit == (p == 3)
+    big = 2147483629
+    one = [{1020: 1, 1021: -1}] + [{j: 1} for j in (0, 511, 1019, 1021, 1020, 7, 1000)]
+    c = _cse_case(out, "key51_8x1022", "moduli", 1022, one, p=big)
+    assert c.plan.NC == 1024 and 2 * _clog2(c.plan.NC) + _clog2(big) == 51
+    pool = [0, 1, 500, 994, 995, 996, 997, 998, 999]               # the same width with steps: 22 new columns 1000 .. 1021 at the most
+    c = _cse_case(out, "key51_8x1000", "moduli", 1000, _rows(rng, 1000, [7, 7, 7, 7, 6, 6, 6, 6], [1, -1], pool), p=big)
+    assert c.plan.NC == 1024 and c.maxfreq >= 2
+    c = _cse_case(out, "key53_8x1023", "moduli", 1023, [{1021: 1, 1022: -1}] + one[1:], p=big, refusal="PLO_E_CAPACITY")
+    assert 1023 + 0 + 2 == 1025 and 2 * _clog2(1025) + _clog2(big) == 53
+    assert all(not c.hbm or c.plan == "PLO_E_CAPACITY" for c in out)
     return out

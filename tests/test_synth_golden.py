@@ -5,6 +5,7 @@ give the goldens' counts on every case -- the cases the device refuses included,
 `bin/trilplacer` has no `--costs`: its host engine is held to the trilinear goldens through the winner it prints for seeds
 0..7; `bin/optimizer -K` prints no per-restart counts of the decomposition the goldens record, so the kernel method's host
 path is not held to them here."""
+import importlib.util
 import json
 import os
 import re
@@ -392,3 +393,17 @@ def test_host_trilplacer_search_on_ties_prints_the_golden_winner(name, tmp_path)
     T = next(t for t in TRIL_GOLD["tie"] if t["name"] == name)
     base, win = host_tril_winner(TRIL_TIE[name], T["seed0"], T["n"], str(tmp_path))
     assert win is not None and [win[0], win[1], win[2]] == T["search"], name
+
+
+# ---------------------------------------------------------------------------------------------------- the one-wave CSE kernel
+def test_cse_generators_reproduce_the_pinned_cases():
+    """names, shapes and matrices of synth.cse_cases() (tests/golden/make_cse_cases.py); the oracle scores them live"""
+    spec = importlib.util.spec_from_file_location("make_cse_cases", os.path.join(GOLDEN, "make_cse_cases.py"))
+    make_cse_cases = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make_cse_cases)
+    gold = json.load(open(os.path.join(GOLDEN, "cse_cases.json")))["cases"]
+    cases = synth.cse_cases()
+    assert [e["name"] for e in gold] == [c.name for c in cases] and len(cases) == 89
+    for e, c in zip(gold, cases):
+        assert e == make_cse_cases.entry(c), e["name"]
+    assert [e["name"] for e in gold if "refusal" in e] == ["cse_rowlen_L65_unit", "cse_moduli_key53_8x1023"]
