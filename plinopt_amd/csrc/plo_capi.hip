@@ -710,6 +710,7 @@ void print_big_stats(const plo_plan *pl)
     if (pl->B.defer && ncand) fprintf(stderr, "# big kernel, deferred updates: per candidate %.1f merges (%.2f forced by log/hot pressure), %.0f log records, %.0f hot-table updates; last candidate, merge us: hot->log %u, partition pass %u, sum + write back %u, window %u\n",
             (double)hs[BS_SUM_FULLSCANS] / ncand, (double)hs[BS_SUM_FORCED_MERGES] / ncand, ((double)hs[BS_SUM_LOG_HI] * 4294967296.0 + hs[BS_SUM_LOG_LO]) / ncand, (double)hs[BS_SUM_HOTOPS] / ncand, mg[0], mg[1], mg[2], mg[3]);
     if (pl->B.defer && hs[BS_LAST_MERGE_GROUPS]) fprintf(stderr, "#   merge, sum + write back of the last candidate: %u groups; us: sum (loads + table) %u, scan + write back %u, clear + bounds %u\n", hs[BS_LAST_MERGE_GROUPS], ms[0], ms[1], ms[3]);
+    if (pl->B.defer && hs[BS_OR_MERGE_TABLES]) fprintf(stderr, "#   merge, summing-table sizes of the launch's groups (OR of 1 << lb): 0x%x\n", hs[BS_OR_MERGE_TABLES]);
     fprintf(stderr, "# big kernel (last candidate): steps %u, full scans %u, level rebuilds %u; phase us: level %u select %u rows %u sweep1 %u flush1 %u sweep2 %u flush2 %u tail %u\n",
             hs[BS_LAST_STEPS], hs[BS_LAST_FULLSCANS], hs[BS_LAST_REBUILDS], ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6], ph[7]);
     fprintf(stderr, "# big kernel (last candidate): image load + CSE phase %u us, ProgramGen %u us\n", hs[BS_LAST_CSE_US], hs[BS_LAST_PGEN_US]);

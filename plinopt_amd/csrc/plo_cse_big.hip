@@ -127,6 +127,7 @@ enum BigStat {
     BS_LAST_LOAD_US = 12,           // image load alone
     BS_SUM_MERGE_GROUPS = 13,       // the merge: groups of partitions summed
     BS_SUM_MERGE_LOOP = 14,         // the merge: records loaded behind the prefetch
+    BS_OR_MERGE_TABLES = 15,        // the merge: OR of the summing-table sizes (1 << lb) over the groups of the launch
     BS_PROF_SWEEP1_US = 16, BS_PROF_SWEEP2_US = 20, BS_PROF_STEPS = 24,     // PLO_BIG_PROFILE, 4 words each: by rows per step (>=256, 64.., 16.., <16)
     BS_PROF_FALLBACK1 = 28, BS_PROF_FALLBACK2 = 29, BS_PROF_FLUSHED1 = 30, BS_PROF_FLUSHED2 = 31,
     BS_SUM_STEPS = 32, BS_SUM_FULLSCANS = 33, BS_SUM_REBUILDS = 34, BS_SUM_BISECTIONS = 35, BS_SUM_SPILLED = 36, BS_SUM_LISTOVER = 37,
@@ -524,7 +525,7 @@ struct BigShared {
     uint32_t a, b, r, aggn, nspill, keepn; uint64_t kprime; uint64_t selkey;
     uint32_t nbisect, spilltot, listover, nwin, nsearched;   // nwin: windows of the flat sweep beyond the first of a batch of rows (thread 0's wave); nsearched: rows walked by the row search   // diagnostics: tie picks by bisection, entries through the spill list, sweeps whose slot list overflowed
     uint32_t logn, hotn, hotbits, nforced, hotops, logtot_lo, logtot_hi;   // DEFER: log fill, claimed hot slots, hot table size; diagnostics: merges forced by log/hot pressure, updates served by the hot table, log entries written
-    uint32_t derr; unsigned long long tmg[4], tmb[4]; uint32_t ngrp, nloop; uint32_t outcnt[64];           // DEFER merge: live entries written back per partition of the current group
+    uint32_t derr, lbmask; unsigned long long tmg[4], tmb[4]; uint32_t ngrp, nloop; uint32_t outcnt[64];           // DEFER merge: live entries written back per partition of the current group
     uint32_t cblk[512];            // level-M triple counts per block of 64 first columns (NCmax <= 32768)
     unsigned long long tph[8];     // phase clocks (100 MHz ticks): level, select, rows, sweep1, flush1, sweep2, flush2, tail
     unsigned long long tpg[7], tld; // ProgramGen: table fill + flags, expand + A1, A2, A3 + B + count, Triangle set-up, Triangle, D; tld: the image load
@@ -560,9 +561,10 @@ struct BigShared {
 //           are small) is summed in an LDS hash table (counts biased by 2^15: records arrive in any order), live
 //           triples (frequency >= 2) are written back compactly and counted per level; the new window [theta', M] is
 //           chosen on the exact histogram and its triples move to the hot table.  All of it is streaming traffic.
-//           A group costs two barriers: its records -- four per thread, counted across the group's partitions -- are
-//           requested while the table of the group before is scanned; the table is cleared once per merge and the
-//           scan empties every slot it reads.
+//           A group costs two barriers: its records -- six per thread, counted across the group's partitions: 3072, a whole
+//           group of the default plan -- are requested while the table of the group before is scanned; the table is cleared
+//           once per merge; the scan reads a thread's 16 slots up front, empties every slot that held a key and runs its
+//           body once per live triple (1.4 per thread), not once per slot.
 // Frequencies never rise after the step that creates a triple, so a cold triple stays cold until the next merge and the
 // hot table always holds every triple of frequency >= theta: levels >= theta of hist[] stay exact, lower levels are
 // not maintained between merges (never read: a scan that would go below theta triggers the merge).
@@ -575,7 +577,9 @@ struct BigShared {
 #define PLO_DMREG_WORDS 16384u      /* Bloom filter + scratch region = the merge's 64 KB of LDS */
 #define PLO_DPMAX 2048u             /* partitions: counters, offsets and tails of the partition pass live behind the staging buffer */
 #define PLO_LEMPTY (~0ull)
+#define PLO_DSLOTS ((1u << PLO_DLB) / PLO_BIG_THREADS)        /* slots of the summing table per thread: one bit each in the scan's mask */
 static_assert(PLO_DPMAX <= 4u * PLO_BIG_THREADS && PLO_DCH % PLO_BIG_THREADS == 0u && 2u * PLO_DCH + 3u * PLO_DPMAX <= PLO_DMREG_WORDS, "merge layout");
+static_assert((1u << PLO_DLB) % (8u * PLO_BIG_THREADS) == 0u && PLO_DSLOTS <= 32u, "the scan of the summing table reads eight slots per thread at a time");
 
 __device__ __forceinline__ uint64_t dmix(uint64_t key) { return key * 0x9E3779B97F4A7C15ull; }
 __device__ __forceinline__ uint32_t dpart(uint64_t key, uint32_t pbits) { return pbits ? (uint32_t)(dmix(key) >> (64u - pbits)) : 0u; }
@@ -752,7 +756,7 @@ template <class O> __device__ __forceinline__ void defer_merge(const BigPlan &P,
             if (tid < 64u) sh.outcnt[tid] = 0u;
             BSYNC();
             // Counts of 128 partitions ahead live in two registers (lane i: partition W + i, W + 64 + i); the bounds of a group come from
-            // them without a memory round trip: lane j of `inc` = records of the group's partitions 0..j.  The first four records of a
+            // them without a memory round trip: lane j of `inc` = records of the group's partitions 0..j.  The first six records of a
             // thread for the NEXT group, counted across its partitions, are requested while the table of the current group is scanned
             // and written back.
             uint32_t W = 0, cW = lane < Pn ? ptail[lane] : 0u, cW2 = 64u + lane < Pn ? ptail[64u + lane] : 0u;
@@ -768,33 +772,45 @@ template <class O> __device__ __forceinline__ void defer_merge(const BigPlan &P,
             };
             uint32_t p = 0, inc = 0, g = 0, tot = 0;
             bounds(0u, inc, g, tot);
-            // records x, x + nth, x + 2 nth, x + 3 nth of the group (p_, g_, inc_), x = b + tid: a record that lies behind the first j
-            // partitions of the group is found rcap - (records of the partition) further on for each of them
-            uint64_t f0 = 0, f1 = 0, f2 = 0, f3 = 0;
-            auto flat4 = [&](uint32_t p_, uint32_t g_, uint32_t inc_, uint32_t tot_, uint32_t b) {
-                const uint32_t x0 = b + tid, x1 = x0 + nth, x2 = x1 + nth, x3 = x2 + nth;
-                uint32_t a0 = x0, a1 = x1, a2 = x2, a3 = x3, prev = 0u;
+            // records x + k nth, k < NPF, of the group (p_, g_, inc_), x = b + tid: a record that lies behind the first j partitions of
+            // the group is found rcap - (records of the partition) further on for each of them.  NPF nth = 3072 >= the default lgrp:
+            // a group of the default plan is prefetched whole
+            constexpr uint32_t NPF = 6u;
+            uint64_t f[NPF] = {};
+            auto flatn = [&](uint32_t p_, uint32_t g_, uint32_t inc_, uint32_t tot_, uint32_t b) {
+                uint32_t x[NPF], a[NPF], prev = 0u;
+#pragma unroll
+                for (uint32_t k = 0; k < NPF; ++k) { x[k] = b + tid + k * nth; a[k] = x[k]; }
                 for (uint32_t j = 0; j + 1u < g_; ++j) {
                     const uint32_t s = (uint32_t)__builtin_amdgcn_readlane((int)inc_, (int)j), d = rcap - (s - prev);
                     prev = s;
-                    a0 += x0 >= s ? d : 0u; a1 += x1 >= s ? d : 0u; a2 += x2 >= s ? d : 0u; a3 += x3 >= s ? d : 0u;
+#pragma unroll
+                    for (uint32_t k = 0; k < NPF; ++k) a[k] += x[k] >= s ? d : 0u;
                 }
                 const uint64_t *sp = store + (uint64_t)p_ * rcap;
-                f0 = x0 < tot_ ? sp[a0] : 0ull; f1 = x1 < tot_ ? sp[a1] : 0ull; f2 = x2 < tot_ ? sp[a2] : 0ull; f3 = x3 < tot_ ? sp[a3] : 0ull;
+#pragma unroll
+                for (uint32_t k = 0; k < NPF; ++k) f[k] = x[k] < tot_ ? sp[a[k]] : 0ull;
             };
-            flat4(0u, g, inc, tot, 0u);
-#define PLO_PUT(v_) do { const int32_t d_ = (int32_t)((v_) & 0x7FFFull); if (d_) if (!lt_put(ltab, (v_) >> 16, ((v_) & 0x8000ull) ? d_ : -d_, pbits, lb)) { wg_max(&sh.errflag, (uint32_t)BERR_TABLE); wg_max(&sh.derr, 103u); } } while (0)
+            flatn(0u, g, inc, tot, 0u);
+            // the thread's NPF records go into the table, one behind the other
+            auto putn = [&](uint32_t lb_) {
+#pragma unroll
+                for (uint32_t k = 0; k < NPF; ++k) {
+                    const int32_t d_ = (int32_t)(f[k] & 0x7FFFull);
+                    if (d_) if (!lt_put(ltab, f[k] >> 16, (f[k] & 0x8000ull) ? d_ : -d_, pbits, lb_)) { wg_max(&sh.errflag, (uint32_t)BERR_TABLE); wg_max(&sh.derr, 103u); }
+                }
+            };
             unsigned long long tbl = wall_clock64();
             while (p < Pn) {
                 if (tot > (7u << (PLO_DLB - 3u))) { if (tid == 0) { wg_max(&sh.errflag, (uint32_t)BERR_TABLE); wg_max(&sh.derr, 102u); } break; }       // more than 7/8 of the table
                 uint32_t lb = 6u; while ((1u << lb) < 2u * tot + 64u && lb < PLO_DLB) ++lb;
                 unsigned long long tb0 = wall_clock64();
 #define PLO_BSTAMP(q_) do { if (tid == 0) { const unsigned long long t_ = wall_clock64(); sh.tmb[q_] += t_ - tb0; tb0 = t_; } } while (0)
-                if (tid == 0) { sh.tmb[3] += tb0 - tbl; ++sh.ngrp; if (tot > 4u * nth) sh.nloop += tot - 4u * nth; }
-                PLO_PUT(f0); PLO_PUT(f1); PLO_PUT(f2); PLO_PUT(f3);
-                for (uint32_t b = 4u * nth; b < tot; b += 4u * nth) {             // beyond the prefetch: lgrp above 4 nth, or one oversized partition
-                    flat4(p, g, inc, tot, b);
-                    PLO_PUT(f0); PLO_PUT(f1); PLO_PUT(f2); PLO_PUT(f3);
+                if (tid == 0) { sh.tmb[3] += tb0 - tbl; ++sh.ngrp; sh.lbmask |= 1u << lb; if (tot > NPF * nth) sh.nloop += tot - NPF * nth; }
+                putn(lb);
+                for (uint32_t b = NPF * nth; b < tot; b += NPF * nth) {           // beyond the prefetch: lgrp above NPF nth, or one oversized partition
+                    flatn(p, g, inc, tot, b);
+                    putn(lb);
                 }
                 // the next group: slide the window of counts, bounds, first records
                 const uint32_t pn = p + g;
@@ -803,15 +819,38 @@ template <class O> __device__ __forceinline__ void defer_merge(const BigPlan &P,
                 if (pn < Pn) bounds(pn, incn, gn, totn);
                 BSYNC();
                 PLO_BSTAMP(0);
-                if (pn < Pn) flat4(pn, gn, incn, totn, 0u); else { f0 = f1 = f2 = f3 = 0ull; }
-                // scan: a slot that held a key is emptied for the next group as it is read
-                for (uint32_t s = tid; s < (1u << lb); s += nth) {
+                if (pn < Pn) flatn(pn, gn, incn, totn, 0u);
+                else {
+#pragma unroll
+                    for (uint32_t k = 0; k < NPF; ++k) f[k] = 0ull;
+                }
+                // scan: the thread's slots tid + u PLO_BIG_THREADS (consecutive words per wave: no bank conflict; a compile-time stride:
+                // one address register, the rest is immediate offsets) are read up front, eight at a time; a slot that held a key of
+                // frequency below 2 (never chosen, never rises -- dropped) is emptied for the next group there, and a bit is kept for
+                // every live one.  The body runs once per set bit -- a group writes back 1.4 triples per thread from 16 slots -- reads
+                // the slot again and empties it.  A wave whose slots are all empty (a table smaller than the workgroup) runs no body.
+                const uint32_t nsl = 1u << lb;
+                constexpr uint32_t SB = 8u;
+                uint32_t live = 0u;
+#pragma unroll
+                for (uint32_t h = 0; h < PLO_DSLOTS; h += SB) {
+                    if (h * PLO_BIG_THREADS < nsl) {
+                        uint64_t w[SB];
+#pragma unroll
+                        for (uint32_t u = 0; u < SB; ++u) w[u] = ltab[(h + u) * PLO_BIG_THREADS + tid];     // (behind the group's 2^lb slots the table is empty: no test)
+#pragma unroll
+                        for (uint32_t u = 0; u < SB; ++u) {
+                            if (w[u] == PLO_LEMPTY) continue;
+                            if ((uint32_t)(w[u] & 0xFFFFull) >= PLO_DBIAS + 2u) live |= 1u << (h + u); else ltab[(h + u) * PLO_BIG_THREADS + tid] = PLO_LEMPTY;
+                        }
+                    }
+                }
+                while (live != 0u) {
+                    const uint32_t s = (uint32_t)__builtin_ctz(live) * PLO_BIG_THREADS + tid;
+                    live &= live - 1u;
                     const uint64_t v = ltab[s];
-                    if (v == PLO_LEMPTY) continue;
                     ltab[s] = PLO_LEMPTY;
-                    const uint32_t cb = (uint32_t)(v & 0xFFFFull);
-                    if (cb < PLO_DBIAS + 2u) continue;                       // frequency below 2: never chosen, never rises -- dropped
-                    const uint32_t c = cb - PLO_DBIAS; const uint64_t k = v >> 16;
+                    const uint32_t c = (uint32_t)(v & 0xFFFFull) - PLO_DBIAS; const uint64_t k = v >> 16;
                     if (c > maxf0) { wg_max(&sh.errflag, (uint32_t)BERR_FREQ); continue; }
                     wg_add(&hist[c], 1u);
                     const uint32_t j = dpart(k, pbits) - p;
@@ -824,7 +863,6 @@ template <class O> __device__ __forceinline__ void defer_merge(const BigPlan &P,
                 tbl = wall_clock64();
                 p = pn; inc = incn; g = gn; tot = totn;
             }
-#undef PLO_PUT
         }
         PLO_BIG_FENCE(); BSYNC();
         PLO_MSTAMP(2);
@@ -970,7 +1008,7 @@ template <int MODE, bool DEFER, bool IDK, class O> __device__ __forceinline__ ui
         for (int q = 0; q < 4; ++q) { sh.tb1[q] = sh.tb2[q] = 0; sh.nb[q] = 0; } sh.fb1 = sh.fb2 = sh.fl1 = sh.fl2 = 0; for (int q = 0; q < 16; ++q) sh.pw[q] = 0; for (int c_ = 0; c_ < 4; ++c_) for (int q = 0; q < 8; ++q) sh.tpc[c_][q] = 0;
 #endif
         sh.errflag = 0; sh.fullscans = 0; sh.rebuilds = 0; sh.steps = 0; sh.hlbad = 0; ncrptr[0] = 0; sh.nbisect = 0; sh.spilltot = 0; sh.listover = 0; sh.nwin = 0; sh.nsearched = 0;
-        sh.logn = 0; sh.hotn = 0; sh.hotbits = PW(hotbits_min); sh.derr = 0; for (int q = 0; q < 4; ++q) { sh.tmg[q] = 0; sh.tmb[q] = 0; } sh.ngrp = 0; sh.nloop = 0; sh.nforced = 0; sh.hotops = 0; sh.logtot_lo = 0; sh.logtot_hi = 0;
+        sh.logn = 0; sh.hotn = 0; sh.hotbits = PW(hotbits_min); sh.derr = 0; for (int q = 0; q < 4; ++q) { sh.tmg[q] = 0; sh.tmb[q] = 0; } sh.ngrp = 0; sh.nloop = 0; if constexpr (DEFER) sh.lbmask = 0; sh.nforced = 0; sh.hotops = 0; sh.logtot_lo = 0; sh.logtot_hi = 0;
     }
     PLO_BIG_FENCE(); BSYNC();
     if (tid == 0) sh.tld = wall_clock64() - tld0;
@@ -2289,6 +2327,7 @@ template <int MODE, bool DEFER, bool IDK = false, bool WIDE = false> __global__ 
                 J.stats[BS_LAST_MERGE_GROUPS] = sh.ngrp;
                 atomicAdd(&J.stats[BS_SUM_MERGE_GROUPS], sh.ngrp);
                 atomicAdd(&J.stats[BS_SUM_MERGE_LOOP], sh.nloop);
+                if constexpr (DEFER) atomicOr(&J.stats[BS_OR_MERGE_TABLES], sh.lbmask);
                 J.stats[BS_LAST_CSE_US] = (uint32_t)((tk1 - tk0) / 100ull);
                 J.stats[BS_LAST_PGEN_US] = (uint32_t)((tk2 - tk1) / 100ull);
                 J.stats[BS_LAST_LOAD_US] = (uint32_t)(sh.tld / 100ull);
