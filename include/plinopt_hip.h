@@ -516,6 +516,38 @@ int  plo_brent_check(plo_brent_plan_t *plan, uint64_t pair0, uint64_t pair1, plo
 int  plo_brent_plan_info(plo_brent_plan_t *plan, uint32_t out[8]);
 void plo_brent_plan_destroy(plo_brent_plan_t *plan);
 
+/* ---- The coefficient equations of a polynomial-multiplication triple: what the reference's PMchecker (src/PMchecker.cpp) samples
+ * at one random pair of polynomials, checked here one by one (bin/PMchecker).  L (r x na), R (r x nb), P (nc x r)
+ * as rational CSR claim to multiply a polynomial of degree na - 1 by one of degree nb - 1 into nc coefficients.  The pair
+ * (i, j) = i nb + j has the sums S[z] = sum_t L[t][i] R[t][j] P[z][t] for z < nc, 0 for z >= nc, and the defect polynomial
+ * sum_z S[z] X^z - X^(i+j).  Let Z = max(nc, na + nb - 1).
+ *   flen = 0 (no polynomial): w = Z equations per pair, equation e = (i nb + j) w + c asks S[c] == [c == i + j]; a P with too few
+ *     rows shows as violated equations at c = i + j >= nc.
+ *   flen >= 2: f of degree d = flen - 1, its coefficients fnum[c] / fden[c] (fden NULL: all 1), the constant term first; w = d, and
+ *     with rho[z] = X^z mod f equation e = (i nb + j) d + c asks sum_{z < nc} S[z] rho[z][c] == rho[i + j][c].  f need not be
+ *     irreducible.  When d >= Z nothing folds: the sums are compared with [c == i + j] directly, over the width d.
+ * Everything is modulo q, 2 <= q < 2^31, prime or not, taken as given (a proof over Q takes a few primes: bin/PMchecker).
+ * plo_polymul_check covers the pairs [pair0, pair1), that is the equations [pair0 w, pair1 w), in as many launches as the plan's
+ * pairs per launch ask for, and reports as plo_brent_check does: how many are violated, the smallest violated e (~0 when none),
+ * the residue found there and the residue expected; stats->candidates is the number of equations checked.  The result is exact
+ * and does not depend on scheduling.
+ * Refusals, each with its own text; the argument checks come before any device call, the missing plo_init (PLO_E_HIP) after them:
+ * PLO_E_ARG for a null pointer (fnum with flen > 0 included), for L.m != R.m or L.m != P.n, for q < 2 or q >= 2^31, for an unsorted
+ * row (or any other defect of a CSR), for flen = 1 (a constant), a leading coefficient 0 or a non-positive fden, for a denominator
+ * (of a matrix or of f) or a leading coefficient that is no unit modulo q, for an empty pair range or one beyond na nb.
+ * PLO_E_CAPACITY: na or nb above 16384, Z above 32768, r above 2^20, a matrix of 2^31 entries or more, a fold (d < Z) with d above
+ * PLO_POLYMUL_MAX_FOLD_DEGREE (the folded sums of a pair stay in LDS), or any d above 2^24.
+ * plo_polymul_plan_info: out[0] sums per wave in LDS (the chunk: min(nc, 2048) with a fold, min(w, 4096) without, or
+ * PLO_POLYMUL_CHUNK, a test knob; PLO_POLYMUL_PAIRS likewise lowers [3]), [1] chunks per pair, [2] waves per workgroup, [3] pairs
+ * per launch, [4] LDS bytes per workgroup, [5] na nb, [6] w, [7] 1 when the fold runs.  One device per call. */
+#define PLO_POLYMUL_MAX_FOLD_DEGREE 2048u
+typedef struct plo_polymul_plan plo_polymul_plan_t;
+int  plo_polymul_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P,
+                               const int64_t *fnum, const int64_t *fden, uint32_t flen, uint32_t q, plo_polymul_plan_t **plan);
+int  plo_polymul_check(plo_polymul_plan_t *plan, uint64_t pair0, uint64_t pair1, plo_brent_result_t *res, plo_stats_t *stats);
+int  plo_polymul_plan_info(plo_polymul_plan_t *plan, uint32_t out[8]);
+void plo_polymul_plan_destroy(plo_polymul_plan_t *plan);
+
 /* Pack / unpack the (cost, seed) word used by the grid reduction and by the
  * single 8-byte MIN all-reduce across ranks (the `#pragma omp critical`
  * best-so-far of include/plinopt_optimize.inl:1214-1237).  seed_off is the

@@ -30,6 +30,7 @@ EXPORTS = [
     "plo_orbit_plan_create_growth", "plo_orbit_growth_many", "plo_orbit_growth_search", "plo_orbit_growth_search_multi",
     "plo_dep_plan_create_q", "plo_dep_plan_destroy", "plo_dep_search",
     "plo_brent_plan_create_q", "plo_brent_plan_destroy", "plo_brent_plan_info", "plo_brent_check",
+    "plo_polymul_plan_create_q", "plo_polymul_plan_destroy", "plo_polymul_plan_info", "plo_polymul_check",
     "plo_pack_cost",
 ]
 
@@ -230,6 +231,13 @@ def lib():
             L.plo_brent_plan_destroy.restype = None
             L.plo_brent_plan_info.argtypes = [ctypes.c_void_p, u32p]
             L.plo_brent_check.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(BrentResult), ctypes.POINTER(Stats)]
+        if hasattr(L, "plo_polymul_check"):             # (an older build named by PLO_HIP_LIB, as above)
+            L.plo_polymul_plan_create_q.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                                    ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
+            L.plo_polymul_plan_destroy.argtypes = [ctypes.c_void_p]
+            L.plo_polymul_plan_destroy.restype = None
+            L.plo_polymul_plan_info.argtypes = [ctypes.c_void_p, u32p]
+            L.plo_polymul_check.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(BrentResult), ctypes.POINTER(Stats)]
         L.plo_multi_comm_inits.restype = ctypes.c_uint64
         L.plo_pack_cost.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32]
         L.plo_pack_cost.restype = ctypes.c_uint64

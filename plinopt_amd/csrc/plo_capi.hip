@@ -19,6 +19,7 @@
 #include "plo_orbit_growth.hip"
 #include "plo_dep.hip"
 #include "plo_brent.hip"
+#include "plo_polymul.hip"
 #include "../../include/plinopt_hip.h"
 
 #include <algorithm>
@@ -3421,6 +3422,175 @@ int plo_brent_check(plo_brent_plan_t *pl, uint64_t pair0, uint64_t pair1, plo_br
     if (rc == PLO_OK && res->violated) {
         const uint64_t z = res->first % Q.mn, pair = res->first / Q.mn, x = pair / Q.kn, y = pair % Q.kn;
         res->expected = (x % Q.k == y / Q.n && z == (x / Q.k) * Q.n + y % Q.n) ? 1u : 0u;
+    }
+    return call.done(rc);
+}
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------- polynomial-multiplication equations
+struct plo_polymul_plan {
+    plo::PolyMulPlan P{};
+    void *d_img = nullptr; unsigned long long *d_res = nullptr;      // d_res: the count of violated equations, then the packed minimum
+    uint32_t waves_per_wg = 4, lds_bytes = 0, pairs_per_launch = 0, na = 0, fold = 0;
+    uint64_t algo_bytes = 0;
+    std::vector<uint32_t> rho;                                       // the host's copy of the table (the expected value of the first violated equation)
+};
+
+namespace {
+#define PLO_POLYMUL_MAX_Z 32768u
+#define PLO_POLYMUL_MAX_CHUNK 4096u
+// the dynamic LDS any plan may ask for: 4 waves of 4096 sums, or of 2048 sums and PLO_POLYMUL_MAX_FOLD_DEGREE = 2048 folded ones
+#define PLO_POLYMUL_MAX_LDS (4u * 4u * PLO_POLYMUL_MAX_CHUNK)
+
+// X^z mod f for z < Z over Z/qZ, f monic of degree d given by its d low coefficients: Z rows of d residues
+std::vector<uint32_t> polymul_rho(const std::vector<uint32_t> &low, uint32_t Z, uint32_t q) {
+    const uint32_t d = (uint32_t)low.size();
+    std::vector<uint32_t> rho((size_t)Z * d, 0u);
+    for (uint32_t z = 0; z < Z && z < d; ++z) rho[(size_t)z * d + z] = 1u;
+    for (uint32_t z = d; z < Z; ++z) {                              // X rho[z - 1]: a shift, and the top coefficient times X^d = -low
+        const uint32_t *prev = rho.data() + (size_t)(z - 1u) * d; uint32_t *row = rho.data() + (size_t)z * d;
+        const uint64_t top = prev[d - 1u];
+        for (uint32_t c = 0; c < d; ++c) {
+            const uint64_t sub = top * low[c] % q, sh = c ? prev[c - 1u] : 0u;
+            row[c] = (uint32_t)((sh + q - sub) % q);
+        }
+    }
+    return rho;
+}
+} // namespace
+
+extern "C" {
+int plo_polymul_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P, const int64_t *fnum, const int64_t *fden, uint32_t flen, uint32_t q, plo_polymul_plan_t **plan)
+{
+    if (!L || !R || !P || !plan || (flen && !fnum)) return fail(PLO_E_ARG, "null argument");
+    if (L->m != R->m || L->m != P->n)
+        return fail(PLO_E_ARG, "inner dimensions " + std::to_string(L->m) + ", " + std::to_string(R->m) + ", " + std::to_string(P->n) + " of L, R and P differ");
+    if (q < 2u || q >= (1u << 31)) return fail(PLO_E_ARG, "modulus " + std::to_string(q) + " outside 2 .. 2^31 - 1");
+    for (const plo_qcsr_t *A : {L, R, P}) if (const char *d = qcsr_defect(A)) return fail(PLO_E_ARG, d);
+    if (flen == 1u) return fail(PLO_E_ARG, "a constant polynomial: the degree must be 1 at least");
+    if (flen && fnum[flen - 1u] == 0) return fail(PLO_E_ARG, "the leading coefficient of the polynomial is 0");
+    for (uint32_t c = 0; c < flen; ++c) if (fden && fden[c] <= 0) return fail(PLO_E_ARG, "a non-positive denominator in the polynomial");
+    const uint32_t r = L->m, na = L->n, nb = R->n, nc = P->m, d = flen ? flen - 1u : 0u;
+    const uint64_t Z64 = std::max<uint64_t>(nc, (uint64_t)na + nb - (na || nb ? 1u : 0u));
+    if (na > PLO_BRENT_MAX_DIM || nb > PLO_BRENT_MAX_DIM) return fail(PLO_E_CAPACITY, "more than 16384 columns in L or R");
+    if (Z64 > PLO_POLYMUL_MAX_Z) return fail(PLO_E_CAPACITY, "max(nc, na + nb - 1) above 32768");
+    if (r > PLO_BRENT_MAX_RANK) return fail(PLO_E_CAPACITY, "rank above 2^20");
+    for (const plo_qcsr_t *A : {L, R, P}) if (A->rowptr[A->m] >= (1u << 31)) return fail(PLO_E_CAPACITY, "a matrix of 2^31 entries or more");
+    const uint32_t Z = (uint32_t)Z64;
+    const bool fold = flen && d < Z;
+    if (fold && d > PLO_POLYMUL_MAX_FOLD_DEGREE) return fail(PLO_E_CAPACITY, "a fold modulo a polynomial of degree above " + std::to_string(PLO_POLYMUL_MAX_FOLD_DEGREE));
+    if (flen && d > (1u << 24)) return fail(PLO_E_CAPACITY, "a polynomial of degree above 2^24");
+    BrentCols cl, cr, cp;
+    for (const auto &pr : {std::make_pair(L, &cl), std::make_pair(R, &cr), std::make_pair(P, &cp)})
+        if (!brent_cols(pr.first, q, *pr.second)) return fail(PLO_E_ARG, "a denominator is no unit modulo " + std::to_string(q));
+    std::vector<uint32_t> low(d, 0u);                               // f made monic: its d low coefficients
+    if (flen) {
+        std::vector<uint32_t> fr(flen);
+        for (uint32_t c = 0; c < flen; ++c)
+            if (!residue_of(fnum[c], fden ? fden[c] : 1, q, fr[c])) return fail(PLO_E_ARG, "a denominator of the polynomial is no unit modulo " + std::to_string(q));
+        if (gcd64(fr[d], q) != 1) return fail(PLO_E_ARG, "the leading coefficient of the polynomial is no unit modulo " + std::to_string(q));
+        const uint64_t il = inv_mod(fr[d], q);
+        for (uint32_t c = 0; c < d; ++c) low[c] = (uint32_t)(fr[c] * il % q);
+    }
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
+
+    plo_polymul_plan *pl = new plo_polymul_plan();
+    plo::PolyMulPlan &Q = pl->P;
+    Q.nb = nb; Q.nc = nc; Q.w = flen ? d : Z; Q.d = fold ? d : 0u; Q.q = q; Q.mu = (~0ull) / q;
+    pl->na = na; pl->fold = fold ? 1u : 0u;
+    const uint32_t zend = fold ? nc : Q.w;                           // the z that the chunks walk
+    const uint32_t chunk_max = std::max(1u, std::min(zend, fold ? PLO_POLYMUL_MAX_CHUNK / 2u : PLO_POLYMUL_MAX_CHUNK));
+    Q.chunk = chunk_max;
+    if (const auto c = env_knob("PLO_POLYMUL_CHUNK")) Q.chunk = (uint32_t)std::min<long>(std::max<long>(*c, 1), chunk_max);   // test knob: several chunks on a small nc
+    Q.nchunks = (zend + Q.chunk - 1u) / Q.chunk;
+    pl->lds_bytes = round_up(4u * (Q.chunk + Q.d) * pl->waves_per_wg, 16);
+    // Pairs per launch, as for the Brent plan: per chunk at most min(wL[i], wR[j]) steps for a pair's t, besides the bisections
+    // and the clearing and comparing of the chunk; the fold adds ceil(d / 64) steps per row of rho that is no identity row
+    std::vector<uint32_t> wp(r);
+    for (uint32_t t = 0; t < r; ++t) wp[t] = 1u + (cp.ptr[t + 1u] - cp.ptr[t] + 63u) / 64u;
+    auto heaviest = [&](const BrentCols &C, uint32_t cols, uint64_t *longest) {
+        uint64_t best = 0; *longest = 0;
+        for (uint32_t j = 0; j < cols; ++j) {
+            uint64_t w = 0;
+            for (uint32_t e = C.ptr[j]; e < C.ptr[j + 1u]; ++e) w += wp[C.idx[e]];
+            best = std::max(best, w); *longest = std::max<uint64_t>(*longest, C.ptr[j + 1u] - C.ptr[j]);
+        }
+        return best;
+    };
+    uint64_t longl = 0, longr = 0;
+    const uint64_t wl = heaviest(cl, na, &longl), wr = heaviest(cr, nb, &longr);
+    const uint64_t fold_steps = fold ? (uint64_t)((d + 63u) / 64u) * ((nc > d ? nc - d : 0u) + 2u * Q.nchunks + 2u) : 0u;
+    const uint64_t per_pair = (uint64_t)Q.nchunks * (std::min(wl, wr) + (longl + 63u) / 64u * 24u + 2u * ((Q.chunk + 63u) / 64u) + 1u) + fold_steps + 1u;
+    uint64_t ppl = std::max<uint64_t>(1, PLO_BRENT_LAUNCH_STEPS / per_pair);
+    ppl = std::min<uint64_t>(ppl, 0xFFFFFFFFull / std::max(Q.w, 1u));                  // (pair - pair0) w + c stays below 2^32 in the packed minimum
+    if (const auto c = env_knob("PLO_POLYMUL_PAIRS")) ppl = (uint64_t)std::min<long>(std::max<long>(*c, 1), (long)ppl);   // test knob: several launches on a small input
+    pl->pairs_per_launch = (uint32_t)std::min<uint64_t>(ppl, std::max<uint64_t>(1, (uint64_t)na * nb));
+    if (fold) pl->rho = polymul_rho(low, Z, q);
+    pl->algo_bytes = 8ull * (cl.idx.size() + cr.idx.size() + cp.idx.size()) + 4ull * pl->rho.size();
+
+    // the image: nine arrays of 32-bit words and the table
+    const std::vector<uint32_t> *arr[10] = {&cl.ptr, &cl.idx, &cl.val, &cr.ptr, &cr.idx, &cr.val, &cp.ptr, &cp.idx, &cp.val, &pl->rho};
+    size_t off[10], words = 0;
+    for (int j = 0; j < 10; ++j) { off[j] = words; words += (arr[j]->size() + 3u) / 4u * 4u; }
+    std::vector<uint32_t> img(std::max<size_t>(words, 4), 0u);
+    for (int j = 0; j < 10; ++j) if (!arr[j]->empty()) memcpy(img.data() + off[j], arr[j]->data(), 4u * arr[j]->size());
+    if (hipMalloc(&pl->d_img, 4u * img.size()) != hipSuccess || hipMemcpy(pl->d_img, img.data(), 4u * img.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc((void **)&pl->d_res, 16) != hipSuccess ||
+        hipFuncSetAttribute((const void *)plo::polymul_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PLO_POLYMUL_MAX_LDS) != hipSuccess) {   // the largest any plan asks for: plans do not lower it under each other
+        plo_polymul_plan_destroy(pl); return fail(PLO_E_HIP, "device setup of the polynomial-multiplication plan failed");
+    }
+    const uint32_t *dv = (const uint32_t *)pl->d_img;
+    Q.lcp = dv + off[0]; Q.lt = dv + off[1]; Q.lv = dv + off[2];
+    Q.rcp = dv + off[3]; Q.rt = dv + off[4]; Q.rv = dv + off[5];
+    Q.prp = dv + off[6]; Q.pz = dv + off[7]; Q.pv = dv + off[8];
+    Q.rho = dv + off[9];
+    *plan = pl;
+    return PLO_OK;
+}
+
+void plo_polymul_plan_destroy(plo_polymul_plan_t *pl)
+{
+    if (pl) { dev_free(pl->d_img, pl->d_res); delete pl; }
+}
+
+int plo_polymul_plan_info(plo_polymul_plan_t *pl, uint32_t out[8])
+{
+    if (!pl || !out) return fail(PLO_E_ARG, "null argument");
+    out[0] = pl->P.chunk; out[1] = pl->P.nchunks; out[2] = pl->waves_per_wg; out[3] = pl->pairs_per_launch;
+    out[4] = pl->lds_bytes; out[5] = pl->na * pl->P.nb; out[6] = pl->P.w; out[7] = pl->fold;
+    return PLO_OK;
+}
+
+int plo_polymul_check(plo_polymul_plan_t *pl, uint64_t pair0, uint64_t pair1, plo_brent_result_t *res, plo_stats_t *stats)
+{
+    if (!pl || !res) return fail(PLO_E_ARG, "null argument");
+    const uint64_t npairs = (uint64_t)pl->na * pl->P.nb;
+    if (pair0 >= pair1 || pair1 > npairs) return fail(PLO_E_ARG, "pairs " + std::to_string(pair0) + " .. " + std::to_string(pair1) + ": an empty range or one beyond the " + std::to_string(npairs) + " pairs");
+    if (const int rc = require_device(NOINIT_PLAN)) return rc;
+    CallScope call(stats); plo_stats_t *st = call.st;
+    const plo::PolyMulPlan &Q = pl->P;
+    *res = plo_brent_result_t{0, ~0ull, 0, 0};
+    int rc = PLO_OK;
+    for (uint64_t p0 = pair0; rc == PLO_OK && p0 < pair1;) {
+        const uint64_t cnt = std::min<uint64_t>(pl->pairs_per_launch, pair1 - p0);
+        if (hipMemsetAsync(pl->d_res, 0, 8, g_stream) != hipSuccess || hipMemsetAsync(pl->d_res + 1, 0xFF, 8, g_stream) != hipSuccess) { rc = fail(PLO_E_HIP, "clearing the result words"); break; }
+        plo::PolyMulJob J{}; J.pair0 = p0; J.npairs = cnt; J.count = pl->d_res; J.first = pl->d_res + 1;
+        const uint64_t grid = (cnt + pl->waves_per_wg - 1u) / pl->waves_per_wg;
+        rc = timed_launch(pl, grid, cnt * Q.w, st, [&] {
+            hipLaunchKernelGGL(plo::polymul_kernel, dim3((uint32_t)grid), dim3(64 * pl->waves_per_wg), pl->lds_bytes, g_stream, pl->P, J);
+        });
+        unsigned long long w[2] = {0, 0};
+        if (rc == PLO_OK && hipMemcpy(w, pl->d_res, 16, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PLO_E_HIP, "copy back of the result words");
+        if (rc != PLO_OK) break;
+        if (w[0]) {
+            if (res->violated == 0) { res->first = p0 * Q.w + (w[1] >> 32); res->value = (uint32_t)w[1]; }   // launches go by increasing pair
+            res->violated += w[0];
+        }
+        p0 += cnt;
+    }
+    if (rc == PLO_OK && res->violated) {
+        const uint64_t c = res->first % Q.w, pair = res->first / Q.w, i = pair / Q.nb, j = pair % Q.nb;
+        res->expected = pl->fold ? pl->rho[(size_t)(i + j) * Q.d + c] : (c == i + j ? 1u : 0u);
     }
     return call.done(rc);
 }

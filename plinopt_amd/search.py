@@ -646,3 +646,45 @@ class BrentPlan:
         capi.check(capi.lib().plo_brent_check(self._h, pair0, self.npairs if pair1 is None else pair1, ctypes.byref(res), ctypes.byref(st)))
         self.last_stats = st.as_dict()
         return res.violated, (res.first if res.violated else None), res.value, res.expected
+
+
+class PolyMulPlan:
+    """Mirror of the exact polynomial-multiplication check of bin/PMchecker (plo_polymul_*): L (r x na), R (r x nb), P (nc x r),
+    each (rows, columns, rowptr, col, num[, den]), modulo q (2 <= q < 2^31, prime or not), and optionally the polynomial `f` as
+    its coefficients, constant term first, each an integer or a (numerator, denominator) pair.  `check(pair0, pair1)` covers
+    the pairs i nb + j of [pair0, pair1) (default: all) and returns (violated, first, value, expected): the number of violated
+    equations, the smallest one e = (i nb + j) w + c (None when there is none), the residue found there and the one it should
+    be; w is max(nc, na + nb - 1) without f and its degree with it.  `info()` is `plo_polymul_plan_info`."""
+
+    def __init__(self, L, R, P, q, f=None, device=None):
+        lib = capi.lib()
+        if device is not None:
+            capi.check(lib.plo_init(device))
+        self._h = None
+        self._csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
+        f = [c if isinstance(c, (tuple, list)) else (c, 1) for c in (f or [])]
+        fn = (ctypes.c_int64 * max(len(f), 1))(*[int(c[0]) for c in f])
+        fd = (ctypes.c_int64 * max(len(f), 1))(*[int(c[1]) for c in f])
+        h = ctypes.c_void_p()
+        capi.check(lib.plo_polymul_plan_create_q(*[ctypes.byref(c) for c, _ in self._csr], fn, fd, len(f), q, ctypes.byref(h)))
+        self._h = h
+        self.npairs = L[1] * R[1]
+        self.last_stats = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                capi.lib().plo_polymul_plan_destroy(self._h); self._h = None
+        except Exception:
+            pass
+
+    def info(self):
+        out = (ctypes.c_uint32 * 8)()
+        capi.check(capi.lib().plo_polymul_plan_info(self._h, out))
+        return dict(zip(("chunk", "chunks", "waves_per_wg", "pairs_per_launch", "lds_bytes", "npairs", "w", "fold"), out))
+
+    def check(self, pair0=0, pair1=None):
+        res, st = capi.BrentResult(), capi.Stats()
+        capi.check(capi.lib().plo_polymul_check(self._h, pair0, self.npairs if pair1 is None else pair1, ctypes.byref(res), ctypes.byref(st)))
+        self.last_stats = st.as_dict()
+        return res.violated, (res.first if res.violated else None), res.value, res.expected
