@@ -548,6 +548,47 @@ int  plo_polymul_check(plo_polymul_plan_t *plan, uint64_t pair0, uint64_t pair1,
 int  plo_polymul_plan_info(plo_polymul_plan_t *plan, uint32_t out[8]);
 void plo_polymul_plan_destroy(plo_polymul_plan_t *plan);
 
+/* ---- An in-place trilinear program of bin/trilplacer, certified: what the reference leaves to a Maple session (-DINPLACE_CHECKER,
+ * include/plinopt_inplace.inl:940-1067), checked here equation by equation (bin/TPchecker).  L (r x na), R (r x nb),
+ * P (nc0 x r) as rational CSR, and the program as flat records: family 0 a, 1 b, 2 c; PLO_TPROG_ADD x[dst] += v x[src] within one
+ * family; PLO_TPROG_SCA x[dst] *= v; PLO_TPROG_AXPY (family 2) c[dst] += v a[src] b[src2] with v = +-1 and part 0, or with
+ * PLO_TPROG_EXPANDED part 1 (low) or 2 (hig); v = num / den.  The state is a[na], b[nb], c[nc], nc = nc0, or nc0 + 1 with
+ * PLO_TPROG_EXPANDED; on unit inputs the program ends in a' = A a, b' = B b, c' = C c + S(a, b).  With the width w = nc (2 nc when
+ * expanded: the low components, then the hig ones), T[i][j][z] = sum_t L[t][i] R[t][j] P[z][t], or with PLO_TPROG_MATMUL the
+ * matrix-multiplication tensor of the (m, k, n) with na = m k, nb = k n, nc0 = m n (n = floor(sqrt(nb nc0 / na)); the entries of
+ * the matrices are then not read), the equations are numbered
+ *   e = (i nb + j) w + z          S[i][j][z] == T[i][j][z]; expanded: S_low[z] == T[z] (0 at z = nc0), S_hig[z] == T[z - 1] (0 at 0)
+ *   E0 + x na + i, E0 = na nb w   A[x][i] == [x == i];  then nb^2 numbers for B and nc^2 for C in the same way.
+ * Everything is modulo q, 2 <= q < 2^31, prime or not, taken as given (a proof over Q takes a few primes: bin/TPchecker).
+ * plo_tprog_check covers the bilinear equations of the pairs i nb + j in [pair0, pair1) and, when pair0 == 0, the three
+ * restoration blocks, and reports in a plo_brent_result_t (reused: the contract is the same): how many are violated, the
+ * smallest violated e (~0 when none), the residue found there and the residue expected; stats->candidates is the number of
+ * equations checked.  The result is exact and does not depend on scheduling.
+ * Refusals, each with its own text; the argument checks come before any device call, the missing plo_init (PLO_E_HIP) after them:
+ * PLO_E_ARG for a null pointer, L.m != R.m or L.m != P.n, q < 2 or q >= 2^31, a defect of a CSR, unknown flags or both at once, a
+ * shape that is no m k, k n, m n under PLO_TPROG_MATMUL, a record outside the list above (family, operation, part, an index out of
+ * range, an ADD across families, den <= 0), a denominator that is no unit modulo q, an empty pair range or one beyond na nb.
+ * PLO_E_CAPACITY: w, na or nb above PLO_TPROG_MAX_WORDS (a lane keeps that many state words in LDS), 2^24 records or more (the
+ * target's included: one per entry of P, two when expanded), r above 2^20, or a table of operands (AXPYs + r rows of na or nb
+ * words) of 2^28 words or more; all of them before anything of that size is allocated.
+ * plo_tprog_plan_info: out[0] PLO_TPROG_MAX_WORDS, [1] LDS words per wave of the bilinear kernel (64 w), [2] waves per workgroup
+ * there, [3] waves per launch (PLO_TPROG_WAVES, a test knob, lowers it), [4] records of the c stream, the appended target
+ * included, [5] na nb, [6] w, [7] AXPY rows (program and target).  PLO_TPROG_SKIP=0 (a measuring knob) makes the bilinear kernel walk
+ * the ADD and SCA records whose slot is still zero in every lane instead of passing them over.  One device per call. */
+#define PLO_TPROG_ADD  0u
+#define PLO_TPROG_SCA  1u
+#define PLO_TPROG_AXPY 2u
+#define PLO_TPROG_EXPANDED 1u
+#define PLO_TPROG_MATMUL   2u
+#define PLO_TPROG_MAX_WORDS 512u
+typedef struct { uint8_t family, op, part, reserved; uint32_t dst, src, src2; int64_t num, den; } plo_tprog_rec_t;
+typedef struct plo_tprog_plan plo_tprog_plan_t;
+int  plo_tprog_plan_create_q(const plo_qcsr_t *L, const plo_qcsr_t *R, const plo_qcsr_t *P,
+                             const plo_tprog_rec_t *recs, uint64_t nrec, uint32_t flags, uint32_t q, plo_tprog_plan_t **plan);
+int  plo_tprog_check(plo_tprog_plan_t *plan, uint64_t pair0, uint64_t pair1, plo_brent_result_t *res, plo_stats_t *stats);
+int  plo_tprog_plan_info(plo_tprog_plan_t *plan, uint32_t out[8]);
+void plo_tprog_plan_destroy(plo_tprog_plan_t *plan);
+
 /* Pack / unpack the (cost, seed) word used by the grid reduction and by the
  * single 8-byte MIN all-reduce across ranks (the `#pragma omp critical`
  * best-so-far of include/plinopt_optimize.inl:1214-1237).  seed_off is the

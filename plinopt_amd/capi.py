@@ -31,6 +31,7 @@ EXPORTS = [
     "plo_dep_plan_create_q", "plo_dep_plan_destroy", "plo_dep_search",
     "plo_brent_plan_create_q", "plo_brent_plan_destroy", "plo_brent_plan_info", "plo_brent_check",
     "plo_polymul_plan_create_q", "plo_polymul_plan_destroy", "plo_polymul_plan_info", "plo_polymul_check",
+    "plo_tprog_plan_create_q", "plo_tprog_plan_destroy", "plo_tprog_plan_info", "plo_tprog_check",
     "plo_pack_cost",
 ]
 
@@ -106,6 +107,12 @@ class DepHit(ctypes.Structure):
 class BrentResult(ctypes.Structure):
     """plo_brent_result_t of include/plinopt_hip.h"""
     _fields_ = [("violated", ctypes.c_uint64), ("first", ctypes.c_uint64), ("value", ctypes.c_uint32), ("expected", ctypes.c_uint32)]
+
+
+class TProgRec(ctypes.Structure):
+    """plo_tprog_rec_t of include/plinopt_hip.h"""
+    _fields_ = [("family", ctypes.c_uint8), ("op", ctypes.c_uint8), ("part", ctypes.c_uint8), ("reserved", ctypes.c_uint8),
+                ("dst", ctypes.c_uint32), ("src", ctypes.c_uint32), ("src2", ctypes.c_uint32), ("num", ctypes.c_int64), ("den", ctypes.c_int64)]
 
 
 class PloError(RuntimeError):
@@ -238,6 +245,13 @@ def lib():
             L.plo_polymul_plan_destroy.restype = None
             L.plo_polymul_plan_info.argtypes = [ctypes.c_void_p, u32p]
             L.plo_polymul_check.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(BrentResult), ctypes.POINTER(Stats)]
+        if hasattr(L, "plo_tprog_check"):               # (an older build named by PLO_HIP_LIB, as above)
+            L.plo_tprog_plan_create_q.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(TProgRec), ctypes.c_uint64,
+                                                  ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
+            L.plo_tprog_plan_destroy.argtypes = [ctypes.c_void_p]
+            L.plo_tprog_plan_destroy.restype = None
+            L.plo_tprog_plan_info.argtypes = [ctypes.c_void_p, u32p]
+            L.plo_tprog_check.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(BrentResult), ctypes.POINTER(Stats)]
         L.plo_multi_comm_inits.restype = ctypes.c_uint64
         L.plo_pack_cost.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32]
         L.plo_pack_cost.restype = ctypes.c_uint64

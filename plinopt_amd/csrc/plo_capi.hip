@@ -1,8 +1,10 @@
 // ===========================================================================
 // plo_capi.hip -- host side of libplinopt_hip.so: the C-ABI declared in
 // include/plinopt_hip.h, for all nine kernel families (CSE wave, CSE HBM, chained
-// CSE, kernel method, change of basis, trilplacer and inplacer, orbit, dependency),
-// each under its banner comment below; what they share comes first.
+// CSE, kernel method, change of basis, trilplacer and inplacer, orbit, dependency)
+// and the checkers, each under its banner comment below; what they share comes
+// first.  The in-place program check has its host code in plo_capi_tprog.hip,
+// included at the end.
 // There is NO CPU fallback in this file: without a HIP device every compute
 // entry point fails with PLO_E_HIP.
 // ===========================================================================
@@ -20,6 +22,7 @@
 #include "plo_dep.hip"
 #include "plo_brent.hip"
 #include "plo_polymul.hip"
+#include "plo_tprog.hip"
 #include "../../include/plinopt_hip.h"
 
 #include <algorithm>
@@ -32,6 +35,7 @@
 #include <functional>
 #include <array>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <optional>
 #include <string>
@@ -3595,3 +3599,6 @@ int plo_polymul_check(plo_polymul_plan_t *pl, uint64_t pair0, uint64_t pair1, pl
     return call.done(rc);
 }
 } // extern "C"
+
+// ---------------------------------------------------------------------------------------------- in-place trilinear programs
+#include "plo_capi_tprog.hip"

@@ -688,3 +688,48 @@ class PolyMulPlan:
         capi.check(capi.lib().plo_polymul_check(self._h, pair0, self.npairs if pair1 is None else pair1, ctypes.byref(res), ctypes.byref(st)))
         self.last_stats = st.as_dict()
         return res.violated, (res.first if res.violated else None), res.value, res.expected
+
+
+class TProgPlan:
+    """Mirror of the exact check of an in-place trilinear program of bin/TPchecker (plo_tprog_*): L (r x na), R (r x nb),
+    P (nc0 x r), each (rows, columns, rowptr, col, num[, den]), the program as records (family, op, part, dst, src, src2, num,
+    den) -- family 0 a, 1 b, 2 c; op 0 ADD, 1 SCA, 2 AXPY; part 0, or 1 low / 2 hig with `expanded` -- modulo q (2 <= q < 2^31,
+    prime or not).  `matmul`: the target is the matrix-multiplication tensor of the shape.  `check(pair0, pair1)` covers the
+    bilinear equations of the pairs i nb + j of [pair0, pair1) (default: all) and, from pair 0, the restoration blocks A, B, C
+    behind them; it returns (violated, first, value, expected) under the numbering of DESIGN.md 2.14 (first None when there
+    is none).  `info()` is `plo_tprog_plan_info`."""
+    EXPANDED, MATMUL = 1, 2
+
+    def __init__(self, L, R, P, records, q, expanded=False, matmul=False, device=None):
+        lib = capi.lib()
+        if device is not None:
+            capi.check(lib.plo_init(device))
+        self._h = None
+        self._csr = [_qcsr(*(tuple(A) + (None,) * (6 - len(A)))) for A in (L, R, P)]
+        recs = (capi.TProgRec * max(len(records), 1))()
+        for k, (fam, op, part, dst, src, src2, num, den) in enumerate(records):
+            recs[k] = capi.TProgRec(fam, op, part, 0, dst, src, src2, num, den)
+        h = ctypes.c_void_p()
+        flags = (self.EXPANDED if expanded else 0) | (self.MATMUL if matmul else 0)
+        capi.check(lib.plo_tprog_plan_create_q(*[ctypes.byref(c) for c, _ in self._csr], recs, len(records), flags, q, ctypes.byref(h)))
+        self._h = h
+        self.npairs = L[1] * R[1]
+        self.last_stats = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                capi.lib().plo_tprog_plan_destroy(self._h); self._h = None
+        except Exception:
+            pass
+
+    def info(self):
+        out = (ctypes.c_uint32 * 8)()
+        capi.check(capi.lib().plo_tprog_plan_info(self._h, out))
+        return dict(zip(("max_words", "lds_words_per_wave", "waves_per_wg", "waves_per_launch", "records", "npairs", "w", "rows"), out))
+
+    def check(self, pair0=0, pair1=None):
+        res, st = capi.BrentResult(), capi.Stats()
+        capi.check(capi.lib().plo_tprog_check(self._h, pair0, self.npairs if pair1 is None else pair1, ctypes.byref(res), ctypes.byref(st)))
+        self.last_stats = st.as_dict()
+        return res.violated, (res.first if res.violated else None), res.value, res.expected
