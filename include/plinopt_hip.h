@@ -315,6 +315,23 @@ int  plo_tril_plan_create_x(const plo_icsr_t *A, const plo_icsr_t *B, const plo_
  * a row of more than 64 entries, or an entry that vanishes modulo the prime. */
 typedef struct { uint32_t m, n; const uint32_t *rowptr; const uint32_t *col; const int64_t *num; const int64_t *den; } plo_qcsr_t;
 int  plo_tril_plan_create_q(const plo_qcsr_t *A, const plo_qcsr_t *B, const plo_qcsr_t *T, int expanded, plo_tril_plan_t **plan);
+/* ---- The restart search of the direct method over the RATIONALS, bit-exact with Optimizer() over Q seed by seed (bin/optimizer --gpu-q).
+ * A: rational CSR as above.  The plan is an ordinary plo_plan_t: plo_cse_search_plan, plo_cse_cost_many_plan (every cost mode) and
+ * plo_cse_plan_destroy take it; candidate `seed` is the candidate `bin/optimizer --replay --seed` prints without -q.
+ * How: every value a candidate can compare lies in the finite universe U = +-(V u R u {1}), V the distinct entries of A and
+ * R = { b/a : a, b in V } (RemOneCSE never makes a new value).  The plan keeps residues modulo a 31-bit prime that divides no
+ * numerator or denominator of U and keeps U's residues distinct -- 2147483629, else the next primes below it, 8 tried in all -- and the
+ * pair keys carry the RANK in U of a ratio, so their order is Q's.  A +-1 matrix runs the +-1 kernel at its speed.
+ * PLO_E_UNSUPPORTED, each with its own text and before any device call: more than 64 distinct values; an ordering of U that overflows
+ * 128 bits; no separating prime among the 8; a matrix beyond the LDS-resident kernels (the HBM-resident family has no search over Q yet:
+ * flags = PLO_PLAN_HBM is refused as well); plo_cse_enum_* on such a plan.  A candidate that meets a value outside U (none can, by the
+ * closure argument) makes the call return PLO_E_UNSUPPORTED, never a count.  PLO_E_ARG: null pointers, unknown flags, a defect of the CSR.
+ * Test knob PLO_CSE_Q_PRIME=<p>: the first prime tried is the largest one <= p. */
+int  plo_cse_plan_create_q(const plo_qcsr_t *A, uint32_t flags, plo_plan_t **plan);
+/* Host only (no device is touched): the prime, |V|, |U| and U ascending over Q as num[k]/den[k] (lowest terms, den > 0).  The counts are
+ * filled in whenever V and U could be formed; PLO_E_CAPACITY when cap < |U| or an element does not fit 64 bits; otherwise the refusals of
+ * plo_cse_plan_create_q that concern U (then *prime is 0). */
+int  plo_cse_q_universe(const plo_qcsr_t *A, uint32_t *prime, uint32_t *nvalues, uint32_t *nuniverse, int64_t *num, int64_t *den, uint32_t cap);
 void plo_tril_plan_destroy(plo_tril_plan_t *plan);
 /* ops6[6k..6k+5] = ADD,SCA,MUL of variant 0 then of variant 1 for candidate k (seeds[k], or seed0+k when seeds==NULL) */
 int  plo_tril_cost_many(plo_tril_plan_t *plan, const uint64_t *seeds, uint64_t seed0, uint64_t n, uint32_t *ops6, plo_stats_t *stats);

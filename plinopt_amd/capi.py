@@ -22,6 +22,7 @@ EXPORTS = [
     "plo_cse_cost_many_plan", "plo_cse_cost_many",
     "plo_cse_chain_create", "plo_cse_chain_destroy", "plo_cse_chain_search", "plo_cse_chain_cost_many", "plo_cse_chain_batch", "plo_cse_batch_search", "plo_kernel_search", "plo_kernel_search_orders", "plo_kernel_batch_search",
     "plo_cse_enum_cost_many_plan", "plo_cse_enum_search_plan",
+    "plo_cse_plan_create_q", "plo_cse_q_universe",
     "plo_cob_search", "plo_cob_search_range", "plo_cob_search_batch",
     "plo_tril_plan_create", "plo_tril_plan_create_x", "plo_tril_plan_create_q", "plo_tril_plan_destroy", "plo_tril_cost_many", "plo_tril_search",
     "plo_lin_plan_create_q", "plo_lin_plan_destroy", "plo_lin_cost_many", "plo_lin_search", "plo_lin_search_multi",
@@ -188,6 +189,9 @@ def lib():
                                            ctypes.POINTER(CobProblem), ctypes.POINTER(CobBest), ctypes.POINTER(Stats)]
         L.plo_cse_enum_cost_many_plan.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, u32p, u32p, u64p, ctypes.POINTER(Stats)]
         L.plo_cse_enum_search_plan.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(Best), u64p, ctypes.POINTER(Stats)]
+        if hasattr(L, "plo_cse_plan_create_q"):         # (an older build named by PLO_HIP_LIB, as above)
+            L.plo_cse_plan_create_q.argtypes = [ctypes.POINTER(QCSR), ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
+            L.plo_cse_q_universe.argtypes = [ctypes.POINTER(QCSR), u32p, u32p, u32p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_uint32]
         L.plo_tril_plan_create.argtypes = [ctypes.POINTER(ICSR), ctypes.POINTER(ICSR), ctypes.POINTER(ICSR), ctypes.POINTER(ctypes.c_void_p)]
         L.plo_tril_plan_create_x.argtypes = [ctypes.POINTER(ICSR), ctypes.POINTER(ICSR), ctypes.POINTER(ICSR), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
         L.plo_tril_plan_create_q.argtypes = [ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.POINTER(QCSR), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]

@@ -8,7 +8,9 @@
 // 1204-1238) runs on the GPU through the C-ABI of libplinopt_hip.so
 // (plo_cse_search); the winning seed is then replayed on the host to produce
 // the program text.  Over the rationals (no -q) the loop runs on the host, as
-// in the reference.  A failing GPU call is fatal: there is no silent fallback.
+// in the reference; with --gpu-q the restart loop of -D runs on the GPU through
+// the plan of plo_cse_plan_create_q, whose candidates are those of the host loop
+// over Q seed by seed.  A failing GPU call is fatal: there is no silent fallback.
 // ===========================================================================
 #include "plo_host.hpp"
 #include "plo_fast.hpp"
@@ -33,6 +35,7 @@ struct HipLib {
     PLO_SYM(chain_create, plo_cse_chain_create); PLO_SYM(chain_search, plo_cse_chain_search); PLO_SYM(chain_destroy, plo_cse_chain_destroy);
     PLO_SYM(plan_create, plo_cse_plan_create); PLO_SYM(plan_destroy, plo_cse_plan_destroy);
     PLO_SYM(enum_search, plo_cse_enum_search_plan);
+    PLO_SYM_OPT(plan_create_q, plo_cse_plan_create_q); PLO_SYM(search_plan, plo_cse_search_plan);   // --gpu-q
     PLO_SYM(chain_batch, plo_cse_chain_batch);
     PLO_SYM_OPT(kernel_search, plo_kernel_search);   // optional: -K with the decompositions on the device
     PLO_SYM_OPT(kernel_search_multi, plo_kernel_search_multi);   // optional: the same over N devices from this process
@@ -52,6 +55,7 @@ struct Options {
     uint64_t kernel_block = 1;     // --kernel-block: restarts per decomposition of -K (the reference draws one decomposition per restart, :1299-1340)
     bool recsub = false;           // --recsub: -E chooses the schedule as RecSub does (:950-959): additions, then ITS multiplication count (before ProgramGen)
     bool orders = false; uint64_t first = 0, count = 0;   // --orders first:count: -N over that range of order indices only (a walk of 12! split over processes and machines; a bounded run)
+    bool gpu_q = false;            // --gpu-q: over the rationals, the restart loop of -D on the device (exact: plo_cse_plan_create_q)
     bool on_gpu() const { return q != 0 && gpu > 0; }
 };
 template <class F> constexpr bool device_field = std::is_same<F, ZpField>::value;   // the field of the kernels: every use of the library is compiled for it alone
@@ -623,8 +627,31 @@ template <class F> int run(const F &f, const QMat &MQ, Options o)
             catch (const std::exception &e) { std::clog << "# -A skipped: " << e.what() << std::endl; }
         }
     }
+    if constexpr (std::is_same<F, QField>::value)
+        if (o.gpu_q && (o.kernel || o.lu || o.ab || o.exhaustive || o.allkernels)) std::clog << "# --gpu-q: -K, -G, -A, -E and -N stay on the host over Q" << std::endl;
     if (o.direct) {
         Best best = dshards.best; bool on_gpu = best.have;
+        if constexpr (std::is_same<F, QField>::value) if (o.gpu_q && o.loops > 0) {
+            // the same restarts on the device: its candidate `seed` is Optimizer() over Q of that seed, so the winner below is the host loop's
+            HipLib L;
+            if (!bring_up(L, "")) return 2;
+            const QCsr M = qcsr(MQ); const plo_qcsr_t A = M.view();
+            plo_plan_t *plan = nullptr; plo_best_t b{}; plo_stats_t st{};
+            int rc = PLO_E_UNSUPPORTED; std::string why;
+            if (!L.plan_create_q) why = "this build of the library has no search over Q";
+            else if (M.wide) why = "a coefficient does not fit 64-bit numerators and denominators";
+            else if ((rc = L.plan_create_q(&A, 0u, &plan)) == PLO_OK) { rc = L.search_plan(plan, o.seed0, o.loops, PLO_COST_SUM_THEN_ADD, &b, &st); if (rc != PLO_OK) why = L.last_error(); L.plan_destroy(plan); }
+            else why = L.last_error();
+            if (refusal(rc)) std::clog << "# -D on the GPU refused (" << why << "): host search" << std::endl;
+            else if (rc != PLO_OK) { fail(cat("GPU search failed (", rc, "): ", why)); return 2; }
+            else {
+                on_gpu = true; best.offer({b.adds, b.muls}, b.seed);
+                if (o.verbose > 0)
+                    std::clog << "# GPU (over Q): " << st.candidates << " candidates, kernel " << st.kernel_ms << " ms, "
+                              << (st.kernel_ms > 0 ? st.candidates / (st.kernel_ms * 1e-3) : 0.0) << " candidates/s" << std::endl;
+            }
+            L.shutdown();
+        }
         if constexpr (device_field<F>) if (o.on_gpu() && !best.have && !dshards.refused) {
             on_gpu = true;
             HipLib L;
@@ -656,10 +683,17 @@ template <class F> int run(const F &f, const QMat &MQ, Options o)
 #endif
             if (o.verbose > 0) std::clog << "# host search: " << o.loops << " candidates in " << dt << " s on " << nthr << " threads (index build included)" << std::endl;
         }
-        if (best.have && !replay_and_adopt('D', cat("replay of seed ", best.index), best, [&] {
+        auto adopt = [&] {
+            return !best.have || replay_and_adopt('D', cat("replay of seed ", best.index), best, [&] {
                 Ops ops; std::string t = replay_text(f, lM, best.index, ops, o.engine);
                 return found(t, ops, cat("\t[seed ", best.index, ']'));
-            }, nullptr, o.verbose, prog)) return 3;                                   // :1241-1245
+            }, nullptr, o.verbose, prog);                                             // :1241-1245
+        };
+        if (!adopt()) {
+            if (!(o.gpu_q && on_gpu)) return 3;
+            best = host_search(f, lM, o.seed0, o.loops, o.engine);                    // --gpu-q: the replay over Q disagrees with the device (said above, counted): the host's own search
+            if (!adopt()) return 3;
+        }
     }
     if (o.kernel && !o.kfi) {                                                         // :1450-1462
         try { kernel_method(f, lM, o, kshards, prog); }
@@ -733,10 +767,12 @@ int main(int argc, char **argv)
     for (int i = 1; i < argc; ++i) {
         std::string a(argv[i]);
         if (a == "-h") {
-            std::clog << "Usage: " << argv[0] << " [-h|-M|-P|-K|-D|-G|-E|-N|-A|-q #|-O #|--gpu #|--seed #|--orders #:#] [stdin|matrixfile.sms]\n"
+            std::clog << "Usage: " << argv[0] << " [-h|-M|-P|-K|-D|-G|-E|-N|-A|-q #|-O #|--gpu #|--gpu-q|--seed #|--orders #:#] [stdin|matrixfile.sms]\n"
                       << "  -D/-K/-G: direct/kernel/LU methods (default is all)\n"
                       << "  -F: kernel method with the identity added to its goals (inputs may join the row basis)\n"
-                      << "  -q #: search modulo (default is Rationals, on the host)\n"
+                      << "  -q #: search modulo (default is Rationals, on the host unless --gpu-q)\n"
+                      << "  --gpu-q: without -q, run the restart loop of -D on the MI355X, exactly as over Q (same winner and program as --gpu 0); matrices of\n"
+                      << "      at most 64 distinct values that fit the LDS-resident kernels, others are said and searched on the host; -K/-G/-A/-E/-N stay on the host\n"
                       << "  -O #: randomized search with that many loops (default " << o.loops << " loops)\n"
                       << "  --gpu #: 1 = run the restart loop on the MI355X (default with -q), 0 = host only, N >= 2 = the seeds of -D in N shards, one GPU each\n"
                       << "  --seed #: first candidate seed (default 0)\n"
@@ -768,6 +804,7 @@ int main(int argc, char **argv)
         else if (a == "--gpu" && i + 1 < argc) o.gpu = atoi(argv[++i]);
         else if (a == "--seed" && i + 1 < argc) o.seed0 = strtoull(argv[++i], nullptr, 10);
         else if (a == "--engine" && i + 1 < argc) { std::string e(argv[++i]); o.engine = e == "literal" ? 1 : e == "fast" ? 2 : 0; }
+        else if (a == "--gpu-q") o.gpu_q = true;
         else if (a == "--replay") replay_only = true;    // print the program of candidate --seed, no search
         else if (a == "--host-decomp") o.host_decomp = true;
         else if (a == "--fork-shards") o.fork_shards = true;
@@ -822,6 +859,7 @@ int main(int argc, char **argv)
             std::clog << "# " << ops.first << "\tadditions\n# " << ops.second << "\tmultiplications" << std::endl;
             return 0;
         }
+        if (q != 0 && o.gpu_q) { std::clog << "# --gpu-q is for the search over the rationals: ignored with -q" << std::endl; o.gpu_q = false; }
         if (q != 0) {
             if (q < 3 || q >= (1ull << 62)) { std::cerr << "# ERROR: modulus must be an odd prime below 2^62 in this build" << std::endl; return -1; }
             if (q < (1ull << 31)) { o.q = (uint32_t)q; return run(ZpField(o.q), MQ, o); }

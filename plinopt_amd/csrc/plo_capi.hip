@@ -4,7 +4,8 @@
 // CSE, kernel method, change of basis, trilplacer and inplacer, orbit, dependency)
 // and the checkers, each under its banner comment below; what they share comes
 // first.  The in-place program check has its host code in plo_capi_tprog.hip,
-// included at the end.
+// the plans of the CSE search over Q theirs in plo_capi_cseq.hip, both included
+// at the end.
 // There is NO CPU fallback in this file: without a HIP device every compute
 // entry point fails with PLO_E_HIP.
 // ===========================================================================
@@ -281,6 +282,11 @@ struct plo_plan {
     void *d_ws = nullptr; uint64_t ws_slices = 0;
     unsigned long long *d_next = nullptr; uint32_t *d_stats = nullptr;
     uint32_t big_lds = 0;
+    // exact search over Q (plo_cse_plan_create_q, plo_capi_cseq.hip): val holds the residues of the entries modulo p, qres the residues of the
+    // universe U in Q's order, and the pair keys carry a ratio's rank in U.  qunit: all entries are +-1; the plan then runs the +-1 kernel with
+    // p = 1 -- -1 is stored as p - 1 = 0, that kernel's product a == b ? 1 : p - 1 is an xnor, and 0 < 1 is Q's order of -1 and 1.
+    bool q = false, qunit = false;
+    std::vector<uint32_t> qres;
 };
 
 namespace {
@@ -329,6 +335,7 @@ int build_plan(plo_plan *pl, std::vector<uint8_t> *img_out = nullptr)
     uint32_t maxlen = 0; bool unit = true;
     for (uint32_t i = 0; i < m; ++i) maxlen = std::max(maxlen, rowptr[i + 1] - rowptr[i]);
     for (uint32_t k = 0; k < nnz; ++k) unit = unit && (val[k] == 1u % p || val[k] == p - 1);
+    if (pl->qunit) unit = true;
     if (maxlen > 64) return fail(PLO_E_CAPACITY, "row longer than 64 entries: not handled by the LDS-resident wave kernel");
     if (m == 0 || m > 31 * 64) return fail(PLO_E_CAPACITY, "row count outside [1,1984] for the wave kernel");
     const uint32_t mw = (m + 63) / 64;
@@ -337,19 +344,22 @@ int build_plan(plo_plan *pl, std::vector<uint8_t> *img_out = nullptr)
     uint32_t naive = 0;
     for (uint32_t i = 0; i < m; ++i) { uint32_t l = rowptr[i + 1] - rowptr[i]; if (l > 1) naive += l - 1; }
     const uint64_t NC = (uint64_t)n + naive / 2 + 2;
-    const uint32_t rb = ceil_log2(p), bb = ceil_log2((uint32_t)NC);     // residues < 2^rb, columns < 2^bb
+    const uint32_t rb = pl->qunit ? 1u : ceil_log2(p), bb = ceil_log2((uint32_t)NC);     // residues < 2^rb, columns < 2^bb (a plan over Q keeps the residues' width for ProgramGen's keys: a rank is narrower)
     if (NC >= 0xFFFFull || 2u * bb + rb > 51u)
         return fail(PLO_E_CAPACITY, "pair key (col,col,ratio) does not fit 51 bits for this matrix/modulus");
     if (2ull * nnz >= 65535ull) return fail(PLO_E_CAPACITY, "op-count may exceed 16 bits");
 
     std::vector<uint32_t> inv(nnz);
-    for (uint32_t k = 0; k < nnz; ++k) inv[k] = inv_mod(val[k], p);
+    for (uint32_t k = 0; k < nnz; ++k) inv[k] = pl->qunit ? val[k] : inv_mod(val[k], p);
+    std::map<uint32_t, uint32_t> qrank;                                  // over Q: rank in U of a residue
+    if (pl->q && !pl->qunit) for (uint32_t k = 0; k < pl->qres.size(); ++k) qrank[pl->qres[k]] = k;
     // initial pair table (listpairs, plinopt_optimize.inl:30-41; PairMap :220-225)
     std::map<uint64_t, uint32_t> pm; uint64_t pairs0 = 0;
     for (uint32_t i = 0; i < m; ++i)
         for (uint32_t x = rowptr[i]; x < rowptr[i + 1]; ++x)
             for (uint32_t y = x + 1; y < rowptr[i + 1]; ++y) {
-                uint32_t r = (uint32_t)((uint64_t)val[y] * inv[x] % p);
+                uint32_t r = pl->qunit ? (val[y] == val[x] ? 1u : 0u) : (uint32_t)((uint64_t)val[y] * inv[x] % p);
+                if (!qrank.empty()) r = qrank.at(r);                     // (U holds every ratio of two entries)
                 uint64_t key = ((uint64_t)col[x] << (bb + rb)) | ((uint64_t)col[y] << rb) | r;
                 pm[key]++; ++pairs0;
             }
@@ -393,16 +403,31 @@ int build_plan(plo_plan *pl, std::vector<uint8_t> *img_out = nullptr)
         tl[i] = (uint16_t)(rowptr[i + 1] - rowptr[i]); rs[i] = (uint16_t)rowptr[i];
         for (uint32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
             tm[(col[k] * 2u) * mw + (i >> 6)] |= 1ull << (i & 63);
-            if (val[k] == 1u % p || val[k] == p - 1) tm[(col[k] * 2u + 1u) * mw + (i >> 6)] |= 1ull << (i & 63);
+            if (unit || val[k] == 1u % p || val[k] == p - 1) tm[(col[k] * 2u + 1u) * mw + (i >> 6)] |= 1ull << (i & 63);
         }
     }
     rs[m] = (uint16_t)nnz;
+    if (!qrank.empty()) {                                                // the tables of plo::QTab behind the row starts
+        const uint32_t nu = (uint32_t)pl->qres.size(), qh = std::max(4u, ceil_log2(2u * nu));
+        const size_t at = img.size() / 8u;
+        img.resize(img.size() + 8u * (1u + ((size_t)1 << qh) + (nu + 1u) / 2u), 0);
+        uint64_t *q = (uint64_t *)img.data() + at;
+        q[0] = (uint64_t)qh | ((uint64_t)nu << 32);
+        for (size_t s = 0; s < ((size_t)1 << qh); ++s) q[1 + s] = ~0ull;
+        for (uint32_t k = 0; k < nu; ++k) {
+            uint32_t s = (pl->qres[k] * 0x9E3779B1u) >> (32u - qh);                                // == plo::q_rank
+            while (q[1 + s] != ~0ull) s = (s + 1u) & ((1u << qh) - 1u);
+            q[1 + s] = ((uint64_t)pl->qres[k] << 16) | k;
+        }
+        memcpy(q + 1 + ((size_t)1 << qh), pl->qres.data(), nu * sizeof(uint32_t));
+    }
 
     // waves per workgroup / LDS
     // waves (= candidates) per workgroup: the choice that puts most waves on a CU
-    if (P.rs_bytes + P.region_bytes > g_lds_max)
+    const size_t lds_max = g_lds_max ? g_lds_max : 160u * 1024u;        // (no device yet: the host-only pass of plo_cse_plan_create_q)
+    if (P.rs_bytes + P.region_bytes > lds_max)
         return fail(PLO_E_CAPACITY, "candidate state does not fit the 160 KiB LDS of one CU");
-    const uint32_t W = pick_waves([&](uint32_t w) { return P.rs_bytes + w * P.region_bytes; }, true, g_lds_max, &pl->lds_bytes);
+    const uint32_t W = pick_waves([&](uint32_t w) { return P.rs_bytes + w * P.region_bytes; }, true, lds_max, &pl->lds_bytes);
     pl->waves_per_wg = W;
 
     if (img_out) { *img_out = std::move(img); return PLO_OK; }
@@ -413,7 +438,7 @@ int build_plan(plo_plan *pl, std::vector<uint8_t> *img_out = nullptr)
     if (!pl->d_err) HIPCHK(hipMalloc((void **)&pl->d_err, sizeof(uint32_t)));
     if (!pl->d_best) HIPCHK(hipMalloc((void **)&pl->d_best, sizeof(unsigned long long)));
 
-    const void *fn = unit ? (const void *)plo::cse_wave_kernel<true> : (const void *)plo::cse_wave_kernel<false>;
+    const void *fn = unit ? (const void *)plo::cse_wave_kernel<true> : pl->q ? plo::cse_wave_q_kernel_fn() : (const void *)plo::cse_wave_kernel<false>;
     return occupancy_for(fn, W, pl->lds_bytes, &pl->blocks_per_cu);
 }
 
@@ -803,6 +828,7 @@ int launch(plo_plan *pl, plo::WaveJob J, plo_stats_t *st)
     J.err = pl->d_err;
     const int err = checked_launch(pl->d_err, st, LaunchShape{grid, pl->lds_bytes, W, pl->algo_bytes}, [&] {
         if (pl->P.unit) hipLaunchKernelGGL(plo::cse_wave_kernel<true>, dim3((uint32_t)grid), dim3(W * 64), pl->lds_bytes, g_stream, pl->P, J);
+        else if (pl->q) plo::cse_wave_q_launch((uint32_t)grid, W * 64, pl->lds_bytes, g_stream, pl->P, J);
         else hipLaunchKernelGGL(plo::cse_wave_kernel<false>, dim3((uint32_t)grid), dim3(W * 64), pl->lds_bytes, g_stream, pl->P, J);
     });
 #ifdef PLO_WAVE_PROFILE
@@ -821,6 +847,7 @@ int device_error(int err) {
     case plo::ERR_MULT:  return fail(PLO_E_INTERNAL, "device: multiplier list overflow");
     case plo::ERR_STEPS: return fail(PLO_E_INTERNAL, "device: more CSE steps than the column bound");
     case plo::ERR_PGEN:  return fail(PLO_E_UNSUPPORTED, "device: ProgramGen for non +-1 coefficients not available in this build");
+    case plo::ERR_QVAL:  return fail(PLO_E_UNSUPPORTED, "device: a candidate met a value outside the universe of the plan over Q");
     case plo::ERR_KDEC:  return fail(PLO_E_INTERNAL, "device: nullspace decomposition inconsistent with the rank found on the host");
     default:             return fail(PLO_E_INTERNAL, "device: pair table inconsistency");
     }
@@ -1129,6 +1156,7 @@ int plo_cse_enum_cost_many_plan(plo_plan_t *pl, uint64_t first, uint64_t n, uint
     if (!pl || !adds || !muls) return fail(PLO_E_ARG, "null argument");
     if (const int rc = require_device(NOINIT_CSE)) return rc;
     if (pl->big) return fail(PLO_E_UNSUPPORTED, "schedule enumeration is for matrices of the LDS-resident kernel (the tree of anything larger cannot be walked)");
+    if (pl->q) return fail(PLO_E_UNSUPPORTED, "schedule enumeration over Q is not built: plans of plo_cse_plan_create_q take the restart searches only");
     CallScope call(st); st = call.st;
     if (n == 0) return PLO_OK;                                                   // (`seconds` stays 0)
     if (n > 0xFFFFFFFFull) return fail(PLO_E_ARG, "at most 2^32-1 schedules per call");
@@ -1145,6 +1173,7 @@ int plo_cse_enum_search_plan(plo_plan_t *pl, uint64_t first, uint64_t count, int
     if (cost_mode != PLO_COST_SUM_THEN_ADD && cost_mode != PLO_COST_ADD_THEN_MUL && cost_mode != PLO_COST_RECSUB) return fail(PLO_E_ARG, "cost mode 0, 1 or 3");
     if (const int rc = require_device(NOINIT_CSE)) return rc;
     if (pl->big) return fail(PLO_E_UNSUPPORTED, "schedule enumeration is for matrices of the LDS-resident kernel (the tree of anything larger cannot be walked)");
+    if (pl->q) return fail(PLO_E_UNSUPPORTED, "schedule enumeration over Q is not built: plans of plo_cse_plan_create_q take the restart searches only");
     CallScope call(st); st = call.st;
     out->adds = out->muls = 0xFFFFFFFFu; out->seed = ~0ull; *maxprod = 0;
     DevBuf<unsigned long long> d_pm;
@@ -3602,3 +3631,4 @@ int plo_polymul_check(plo_polymul_plan_t *pl, uint64_t pair0, uint64_t pair1, pl
 
 // ---------------------------------------------------------------------------------------------- in-place trilinear programs
 #include "plo_capi_tprog.hip"
+#include "plo_capi_cseq.hip"

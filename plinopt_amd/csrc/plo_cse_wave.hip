@@ -17,7 +17,8 @@
 // L2-resident template at the start of every candidate):
 //   tab[cap]      u64  open-addressing pair table: key<<13 | count, key =
 //                      col_a<<(bb+rb) | col_b<<rb | ratio (<= 51 bits), so integer order of
-//                      keys == std::map order of the reference's (size_t,size_t,Element)
+//                      keys == std::map order of the reference's (size_t,size_t,Element); over Q (run_candidate<false, true>) the
+//                      ratio field holds the ratio's rank among the values a candidate can meet (QTab below), for the same reason
 //   masks[NC*2mw] u64  per column c: cmask (bit i: row i holds column c) then umask
 //                      (bit i: that entry is +-1); mw = ceil(m/64) words each
 //   val/inv[nnz]  u32  row entries (value, its modular inverse), rows packed at
@@ -55,7 +56,7 @@ struct WavePlan {
     uint32_t off_aff, off_ties, off_mult, region_bytes;                           // scratch part
     uint32_t rs_bytes;                                                            // shared rs[] image, multiple of 8
     uint64_t mu;                                                                  // floor(2^64/p)
-    const uint64_t *tmpl;   // tmpl_bytes of template followed by rs_bytes of rs[m+1] (u16)
+    const uint64_t *tmpl;   // tmpl_bytes of template followed by rs_bytes of rs[m+1] (u16); a plan over Q: followed by its tables (QTab)
 };
 
 struct WaveJob {
@@ -71,7 +72,7 @@ struct WaveJob {
     unsigned long long *prods;     // enumerate: that product per candidate (may be null)
 };
 
-enum { ERR_TABLE = 1, ERR_MULT = 2, ERR_STEPS = 3, ERR_PGEN = 4 };
+enum { ERR_TABLE = 1, ERR_MULT = 2, ERR_STEPS = 3, ERR_PGEN = 4, ERR_QVAL = 6 };   // (5 is the kernel method's ERR_KDEC); ERR_QVAL: a value outside U, the largest word so that atomicMax keeps it
 
 #define PLO_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
@@ -241,6 +242,35 @@ __device__ __forceinline__ uint32_t tab_find(const uint64_t *tab, uint64_t key, 
         if ((v >> PLO_VB) == key) return (uint32_t)(v & PLO_VMASK);
         s = (s + 1u) & (cap - 1u);
     }
+    return 0u;
+}
+
+// Exact search over Q (cse_wave_kernel<false, true>, plo_capi_cseq.hip).  U, sorted over Q, holds every value a candidate can compare
+// and the plan's prime keeps the residues of U apart, so residue arithmetic is exact; residues order Z_p, not Q, so the pair keys of this
+// mode carry a ratio's RANK in U in their ratio field, and integer order of the keys stays the reference's std::map order over Q.
+// The tables follow the row starts in the plan's image: one word (hash bits | |U| << 32), tab[1 << hbits] (open addressing, at most half
+// full: residue << 16 | rank, all ones = empty), res[|U|] (rank -> residue).  They stay in global memory -- 150 KB at 64 values,
+// 160 B to 38 KB for the fixtures, read by every wave of the grid and L2-resident (what that costs).
+// ProgramGen needs none of this: it compares classes {v, -v}, for which min(e, p - e) is as good a name as |v|, and tests +-1.  Q's SIGN
+// enters its counts nowhere: Triangle records the signed pivot in `multiples` (:464) and the output rows ask for |v| (:585), but after
+// FactorOutColumns a class occurs once in a column and Triangle takes the entry it records out of it, so no row can ask for that key.
+struct QTab { const uint64_t *tab; const uint32_t *res; uint32_t hbits; };
+__device__ __forceinline__ QTab q_tables(const WavePlan &P) {
+    const uint64_t *q = P.tmpl + ((P.tmpl_bytes + P.rs_bytes) >> 3);
+    const uint32_t hbits = (uint32_t)q[0];
+    return QTab{q + 1, (const uint32_t *)(q + 1 + (1ull << hbits)), hbits};
+}
+// rank of a residue; one that is not in U: *miss, rank 0
+__device__ __forceinline__ uint32_t q_rank(const QTab &Q, uint32_t res, bool *miss) {
+    const uint32_t qcap = 1u << Q.hbits;
+    uint32_t s = (res * 0x9E3779B1u) >> (32u - Q.hbits);
+    for (uint32_t pr = 0; pr < qcap; ++pr) {
+        const uint64_t v = Q.tab[s];
+        if ((uint32_t)(v >> 16) == res && v != ~0ull) return (uint32_t)(v & 0xFFFFull);
+        if (v == ~0ull) break;
+        s = (s + 1u) & (qcap - 1u);
+    }
+    *miss = true;
     return 0u;
 }
 
@@ -448,7 +478,7 @@ __device__ uint64_t program_gen_general(const WavePlan &P, uint8_t *reg, const u
 struct PickState { uint32_t rng; uint32_t enumerate; uint64_t rem, prod; uint32_t recsub_muls; };   // recsub_muls: RecSub's multiplication count of the schedule (:950-951), set by run_candidate
 
 // One candidate.  Returns packed (adds<<32 | muls); sets *errw on failure.
-template <bool UNIT>
+template <bool UNIT, bool QR = false>
 __device__ uint64_t run_candidate(const WavePlan &P, uint8_t *reg, const uint16_t *rs, PickState &ps,
                                   uint32_t lane, uint32_t *errw)
 {
@@ -467,6 +497,10 @@ __device__ uint64_t run_candidate(const WavePlan &P, uint8_t *reg, const uint16_
     const uint32_t p = P.p, NC = P.NC, cap = P.cap, hbits = P.hbits, mw = P.mw, ms = 2u * P.mw;
     const uint32_t rb = P.rb, bb = P.bb, abs_ = P.rb + P.bb;
 #define PLO_KEY(a_, b_, r_) (((uint64_t)(a_) << abs_) | ((uint64_t)(b_) << rb) | (uint64_t)(r_))   // masks interleaved: {cmask[mw],umask[mw]} per column
+    // QR: a key made from a ratio's residue gets the ratio's rank in U in its place, one look-up per key
+#define PLO_QK(k_) (QR ? (((k_) >> rb) << rb) | q_rank(QT, (uint32_t)((k_) & ((1ull << rb) - 1ull)), &qmiss) : (k_))
+    const QTab QT = QR ? q_tables(P) : QTab{nullptr, nullptr, 0u};
+    bool qmiss = false;
     const uint64_t mu = P.mu;
     const uint32_t LPR = 1u << P.lpr_log2, G = 64u >> P.lpr_log2;
     const uint32_t g = lane >> P.lpr_log2, t = lane & (LPR - 1u), gbase = g << P.lpr_log2;
@@ -531,7 +565,8 @@ __device__ uint64_t run_candidate(const WavePlan &P, uint8_t *reg, const uint16_
         WP_T(2);
         ++nbadd;                                                            // :292
         // ---- RemOneCSE :60-194
-        const uint32_t r = (uint32_t)(key & ((1ull << rb) - 1ull)), b = (uint32_t)(key >> rb) & ((1u << bb) - 1u), a = (uint32_t)(key >> abs_);
+        const uint32_t rk_ = (uint32_t)(key & ((1ull << rb) - 1ull));
+        const uint32_t r = QR ? uni32(QT.res[rk_]) : rk_, b = (uint32_t)(key >> rb) & ((1u << bb) - 1u), a = (uint32_t)(key >> abs_);
         uint32_t c0 = 0, c1 = 0;
         for (uint32_t w = 0; w < mw; ++w) { c0 += (uint32_t)__popcll(umask[a * ms + w]); c1 += (uint32_t)__popcll(umask[b * ms + w]); }
         const bool swap = uni32(c0) < uni32(c1);                                          // :79-88
@@ -558,8 +593,8 @@ __device__ uint64_t run_candidate(const WavePlan &P, uint8_t *reg, const uint16_
             const bool aff = act && ma && mb && vb == fmul<UNIT>(r, va, p, mu);
             if (aff && have && lane != lb) {
                 const bool isa = lane == la;
-                const uint64_t k1 = isa ? key : (c < a ? PLO_KEY(c, a, fmul<UNIT>(va, iv, p, mu)) : PLO_KEY(a, c, fmul<UNIT>(v, ia, p, mu)));
-                const uint64_t k2 = c < b ? PLO_KEY(c, b, fmul<UNIT>(vb, iv, p, mu)) : PLO_KEY(b, c, fmul<UNIT>(v, ib, p, mu));
+                const uint64_t k1 = isa ? key : PLO_QK(c < a ? PLO_KEY(c, a, fmul<UNIT>(va, iv, p, mu)) : PLO_KEY(a, c, fmul<UNIT>(v, ia, p, mu)));
+                const uint64_t k2 = PLO_QK(c < b ? PLO_KEY(c, b, fmul<UNIT>(vb, iv, p, mu)) : PLO_KEY(b, c, fmul<UNIT>(v, ib, p, mu)));
                 bad |= !tab_dec2(tab, k1, k2, cap, hbits, !isa);
                 if (isa) {
                     atomicOr((unsigned long long *)&affw[0], 1ull << (uint32_t)myrow);
@@ -573,7 +608,7 @@ __device__ uint64_t run_candidate(const WavePlan &P, uint8_t *reg, const uint16_
                 const uint32_t q0 = first ? la : lb, q1 = first ? lb : la;
                 const uint32_t coeff = first ? va : vb, icoeff = first ? ia : ib;
                 if (lane != q0 && lane != q1) {
-                    bad |= !tab_inc(tab, PLO_KEY(c, lm, fmul<UNIT>(coeff, iv, p, mu)), cap, hbits);
+                    bad |= !tab_inc(tab, PLO_QK(PLO_KEY(c, lm, fmul<UNIT>(coeff, iv, p, mu))), cap, hbits);
                     const uint32_t np = base + t - (lane > q0 ? 1u : 0u) - (lane > q1 ? 1u : 0u);
                     col[np] = (uint16_t)c; val[np] = v; if (!UNIT) inv[np] = iv;
                 } else if (lane == q0) {
@@ -608,8 +643,8 @@ __device__ uint64_t run_candidate(const WavePlan &P, uint8_t *reg, const uint16_
                     if (aff && have && lane != lb) {
                         // one probe loop for every lane: the entry of a retires the chosen triple itself, the others their pairs with a and with b
                         const bool isa = lane == la;
-                        const uint64_t k1 = isa ? key : (c < a ? PLO_KEY(c, a, fmul<UNIT>(va, iv, p, mu)) : PLO_KEY(a, c, fmul<UNIT>(v, ia, p, mu)));
-                        const uint64_t k2 = c < b ? PLO_KEY(c, b, fmul<UNIT>(vb, iv, p, mu)) : PLO_KEY(b, c, fmul<UNIT>(v, ib, p, mu));
+                        const uint64_t k1 = isa ? key : PLO_QK(c < a ? PLO_KEY(c, a, fmul<UNIT>(va, iv, p, mu)) : PLO_KEY(a, c, fmul<UNIT>(v, ia, p, mu)));
+                        const uint64_t k2 = PLO_QK(c < b ? PLO_KEY(c, b, fmul<UNIT>(vb, iv, p, mu)) : PLO_KEY(b, c, fmul<UNIT>(v, ib, p, mu)));
                         bad |= !tab_dec2(tab, k1, k2, cap, hbits, !isa);
                         if (isa) {
                             atomicOr((unsigned long long *)&affw[(uint32_t)myrow >> 6], 1ull << ((uint32_t)myrow & 63u));
@@ -642,7 +677,7 @@ __device__ uint64_t run_candidate(const WavePlan &P, uint8_t *reg, const uint16_
                     const uint32_t coeff = bcast(v, q0), icoeff = bcast(iv, q0);
                     if (have) {
                         if (lane != q0 && lane != q1) {
-                            bad |= !tab_inc(tab, PLO_KEY(c, lm, fmul<UNIT>(coeff, iv, p, mu)), cap, hbits);
+                            bad |= !tab_inc(tab, PLO_QK(PLO_KEY(c, lm, fmul<UNIT>(coeff, iv, p, mu))), cap, hbits);
                             const uint32_t np = base + t - (lane > q0 ? 1u : 0u) - (lane > q1 ? 1u : 0u);
                             col[np] = (uint16_t)c; val[np] = v; if (!UNIT) inv[np] = iv;
                         } else if (lane == q0) {
@@ -663,6 +698,7 @@ __device__ uint64_t run_candidate(const WavePlan &P, uint8_t *reg, const uint16_
             umask[l0 * ms + lane] &= ~af; umask[l1 * ms + lane] &= ~af;
             cmask[lm * ms + lane] = af;   umask[lm * ms + lane] = uaf;
         }
+        if (QR && __ballot(qmiss)) { if (lane == 0) atomicMax(errw, (uint32_t)ERR_QVAL); break; }
         if (__ballot(bad)) { if (lane == 0) atomicMax(errw, (uint32_t)ERR_TABLE); break; }
         // ---- multiplier reuse :153-169 (counts only)
         if (!UNIT) {
@@ -719,7 +755,7 @@ __device__ __forceinline__ uint32_t cost_key32(uint32_t a, uint32_t mu_, uint32_
     }
 }
 
-template <bool UNIT>
+template <bool UNIT, bool QR = false>
 __global__ __launch_bounds__(256, UNIT ? PLO_WAVE_OCC_UNIT : PLO_WAVE_OCC_GEN) void cse_wave_kernel(WavePlan P, WaveJob J)
 {
     extern __shared__ uint64_t lds64[];
@@ -737,7 +773,7 @@ __global__ __launch_bounds__(256, UNIT ? PLO_WAVE_OCC_UNIT : PLO_WAVE_OCC_GEN) v
         PLO_WAVE_SYNC();
         const uint64_t seed = J.seeds ? J.seeds[c] : J.seed0 + c;
         PickState ps{1u + (uint32_t)(splitmix64(seed) % 2147483646ull), J.enumerate, seed, 1ull, 0u};
-        const uint64_t res = run_candidate<UNIT>(P, reg, rs, ps, lane, J.err);
+        const uint64_t res = run_candidate<UNIT, QR>(P, reg, rs, ps, lane, J.err);
 #ifdef PLO_WAVE_PROFILE
         if (lane == 0) atomicAdd(&g_wprof[9], 1ull);
 #endif
@@ -764,6 +800,12 @@ __global__ __launch_bounds__(256, UNIT ? PLO_WAVE_OCC_UNIT : PLO_WAVE_OCC_GEN) v
     }
 }
 
+// The instantiation over Q, cse_wave_kernel<false, true>, lives in a translation unit of its own (plo_cse_wave_q.hip): one more caller of
+// program_gen_general in this one changes what the inliner does with the chain kernels below.  That unit takes the code above only.
+const void *cse_wave_q_kernel_fn();
+void cse_wave_q_launch(uint32_t grid, uint32_t block, uint32_t lds_bytes, hipStream_t stream, const WavePlan &P, const WaveJob &J);
+
+#ifndef PLO_CSE_WAVE_Q_UNIT
 // Two matrices per candidate, one random stream: the restart loop of LUOptimiser (reference
 // include/plinopt_optimize.inl:1056-1100) runs Optimizer() on a copy of U and then on a copy of L and adds
 // the two op-counts (:1068-1079); the thread's generator simply keeps running from one call to the next.
@@ -863,5 +905,7 @@ __global__ __launch_bounds__(256) void cse_chain_batch_kernel(const WavePlan *pl
         }
     }
 }
+
+#endif // PLO_CSE_WAVE_Q_UNIT
 
 } // namespace plo

@@ -88,6 +88,41 @@ class CSEPlan:
         return (b.adds, b.muls, b.seed), mp.value
 
 
+def cse_q_universe(m, n, rowptr, col, num, den=None):
+    """Host only (plo_cse_q_universe): (prime, |V|, U) of a rational matrix, U ascending over Q as (num, den) pairs -- every value a
+    candidate of the exact search over Q can compare, and the prime that keeps their residues apart."""
+    L = capi.lib()
+    A, keep = _qcsr(m, n, rowptr, col, num, den)
+    prime, nv, nu = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    rc = L.plo_cse_q_universe(ctypes.byref(A), ctypes.byref(prime), ctypes.byref(nv), ctypes.byref(nu), None, None, 0)
+    if rc != capi.PLO_E_CAPACITY or nu.value == 0:
+        capi.check(rc)
+    un, ud = (ctypes.c_int64 * nu.value)(), (ctypes.c_int64 * nu.value)()
+    capi.check(L.plo_cse_q_universe(ctypes.byref(A), ctypes.byref(prime), ctypes.byref(nv), ctypes.byref(nu), un, ud, nu.value))
+    del keep
+    return prime.value, nv.value, list(zip(un, ud))
+
+
+class CSEPlanQ(CSEPlan):
+    """A matrix over the RATIONALS prepared for the restart search that is bit-exact with Optimizer() over Q
+    (plo_cse_plan_create_q): entries num[k]/den[k] (den None: integers).  cost_many and search are CSEPlan's; the schedule
+    enumeration is refused on such a plan."""
+
+    def __init__(self, m, n, rowptr, col, num, den=None, device=None):
+        L = capi.lib()
+        if device is not None:
+            capi.check(L.plo_init(int(device)))
+        self.m, self.n, self.p = m, n, 0
+        self.nnz = len(col)
+        A, self._keep = _qcsr(m, n, rowptr, col, num, den)
+        h = ctypes.c_void_p()
+        capi.check(L.plo_cse_plan_create_q(ctypes.byref(A), 0, ctypes.byref(h)))
+        self._h = h
+        self.is_hbm = False
+        self.last_stats = None
+        self.prime = cse_q_universe(m, n, rowptr, col, num, den)[0]      # the prime the plan took (the same host code chooses it)
+
+
 def cse_search_multi(m, n, rowptr, col, val, p, seed0, nseeds, devices, cost_mode=capi.COST_SUM_THEN_ADD):
     """One process, several devices (plo_cse_search_multi): the restart range in len(devices) contiguous shards, one host thread and
     one device each; (adds, muls, seed) of the minimum under (cmpOpCount key, seed) and the aggregated stats."""
