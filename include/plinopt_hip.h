@@ -106,6 +106,15 @@ int plo_cse_plan_hbm_counters(const plo_plan_t *plan, uint32_t out[8]);
  * (the length of the shorter row list of a step's two columns, summed over steps: reference include/plinopt_optimize.inl:92-94 walks
  * every row). */
 int plo_cse_plan_hbm_counters_ex(const plo_plan_t *plan, uint32_t *out, uint32_t n);
+/* Host only (nothing is launched): what the plan of the HBM-resident family chose for its matrix and modulus.  out[0] kernel mode
+ * (2 ratio identifiers: at most 32 distinct coefficients; 1 value table in LDS: at most 512; 0 value table in global memory), [1] 1 when
+ * the pair keys hold the ratio's identifier instead of its residue, [2] 1 for deferred updates (0: the eager pair table), [3] 1 for the
+ * kernels with 64-bit workspace offsets, [4] bits of the modulus, [5] bits of a key's ratio field, [6] bits of a key's column fields,
+ * [7] bound on the columns (created ones included), [8] distinct coefficients, [9] 1 when an LDS aggregation entry carries the ratio and
+ * its inverse, [10] count bits of that entry, [11] k for a Mersenne modulus 2^k - 1 (shift-and-add reduction), else 0 (Barrett),
+ * [12] 1 when the table of inverses of every residue exists (moduli up to 2^20), [13] log2 of the LDS aggregation table's entries,
+ * [14] log2 of the deferred store's partitions, [15] log2 of the table region's slots.  PLO_E_ARG for a plan of the wave kernel. */
+int plo_cse_plan_hbm_info(const plo_plan_t *plan, uint32_t out[16]);
 /* Host only (no device is touched): the workspace slice the HBM-resident family lays out for one candidate of a matrix with `rows` rows,
  * `nnz` entries, at most `ncmax` columns (created ones included) and an eager pair table of 2^table_bits slots (10..30).
  * out[0] = bytes of the front region (every array but the table, which comes last: the kernels address the front region with 32-bit

@@ -17,7 +17,7 @@ PLAN_HBM = 1
 # every symbol include/plinopt_hip.h declares
 EXPORTS = [
     "plo_init", "plo_shutdown", "plo_last_error", "plo_device_count",
-    "plo_cse_plan_create", "plo_cse_plan_create_ex", "plo_cse_plan_is_hbm", "plo_cse_plan_hbm_counters", "plo_cse_plan_hbm_counters_ex", "plo_cse_hbm_workspace_layout", "plo_cse_plan_destroy",
+    "plo_cse_plan_create", "plo_cse_plan_create_ex", "plo_cse_plan_is_hbm", "plo_cse_plan_hbm_counters", "plo_cse_plan_hbm_counters_ex", "plo_cse_plan_hbm_info", "plo_cse_hbm_workspace_layout", "plo_cse_plan_destroy",
     "plo_cse_search_plan", "plo_cse_search", "plo_cse_search_multi", "plo_multi_comm_inits", "plo_kernel_search_multi", "plo_tril_search_multi",
     "plo_cse_cost_many_plan", "plo_cse_cost_many",
     "plo_cse_chain_create", "plo_cse_chain_destroy", "plo_cse_chain_search", "plo_cse_chain_cost_many", "plo_cse_chain_batch", "plo_cse_batch_search", "plo_kernel_search", "plo_kernel_search_orders", "plo_kernel_batch_search",
@@ -147,6 +147,8 @@ def lib():
         L.plo_cse_plan_is_hbm.argtypes = [ctypes.c_void_p]
         L.plo_cse_plan_hbm_counters.argtypes = [ctypes.c_void_p, u32p]
         L.plo_cse_plan_hbm_counters_ex.argtypes = [ctypes.c_void_p, u32p, ctypes.c_uint32]
+        if hasattr(L, "plo_cse_plan_hbm_info"):
+            L.plo_cse_plan_hbm_info.argtypes = [ctypes.c_void_p, u32p]
         if hasattr(L, "plo_cse_hbm_workspace_layout"):      # (PLO_HIP_LIB may name an older build of the library: the A/B runs)
             L.plo_cse_hbm_workspace_layout.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u64p]
         L.plo_cse_plan_destroy.argtypes = [ctypes.c_void_p]

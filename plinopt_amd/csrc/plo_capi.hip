@@ -606,7 +606,9 @@ int build_big_plan(plo_plan *pl)
         const uint32_t bbres = rb <= 44u ? (48u - rb) / 2u : 0u;            // column bits beside a residue
         const bool fits = rb <= 30u && bbres >= 2u && n + 2ull <= (1ull << bbres) && std::min<uint64_t>(NC, 32768) <= (1ull << bbres);
         if ((!fits || K.idkeys) && ratio_ids && rb <= 31u) { idk = true; kb = std::max(1u, ceil_log2((uint32_t)rv.size())); }   // (PLO_BIG_IDKEYS: test knob, identifiers although residues would fit)
-        else if (rb > 30 || bbres < 2u) return fail(PLO_E_CAPACITY, "modulus too large for the 48-bit pair key (and more than 32 distinct coefficients: no ratio identifiers)");
+        // (!fits below 15 column bits: the modulus, not the kernel's 32768 columns, is what leaves no room -- the bound NC on the created columns
+        // counts, as it does for the identifiers above; clamping it to 2^bbres instead would only move the refusal into the launch)
+        else if (rb > 30 || bbres < 2u || (bbres < 15u && !fits)) return fail(PLO_E_CAPACITY, "modulus too large for the 48-bit pair key (and more than 32 distinct coefficients: no ratio identifiers)");
     }
     const uint32_t bbmax = std::min(15u, (48u - kb) / 2u);
     if (n + 2ull > (1ull << bbmax) || n + 2ull > 32768ull) return fail(PLO_E_CAPACITY, "too many columns for the HBM-resident kernel (48-bit pair key / 32768 columns)");
@@ -1082,6 +1084,18 @@ int plo_cse_plan_hbm_counters_ex(const plo_plan_t *pl, uint32_t *out, uint32_t n
     o[8] = hs[plo::BS_SUM_EXTRA_WINDOWS]; o[9] = hs[plo::BS_SUM_ROWS_SEARCHED];
     o[10] = hs[plo::BS_SUM_FORCED_MERGES]; o[11] = hs[plo::BS_SUM_MERGE_GROUPS]; o[12] = hs[plo::BS_SUM_MERGE_LOOP];         // the merge: forced by log / hot pressure, groups summed, records loaded behind the prefetch
     for (uint32_t k = 0; k < n; ++k) out[k] = o[k];
+    return PLO_OK;
+}
+
+// host only, nothing is launched: the choices build_big_plan made for this plan
+int plo_cse_plan_hbm_info(const plo_plan_t *pl, uint32_t out[16])
+{
+    if (!pl || !out) return fail(PLO_E_ARG, "null argument");
+    if (!pl->big) return fail(PLO_E_ARG, "the plan information belongs to the HBM-resident kernel family");
+    const plo::BigPlan &B = pl->B;
+    const uint32_t o[16] = {B.mode, B.idk, B.defer, B.wide, B.rb, B.kb, B.bb, B.NCmax, B.nv, B.agg_dual, B.agg_cb, B.mers,
+                            B.invtab ? 1u : 0u, B.aggbits, B.defer ? B.pbits : 0u, B.hbits};
+    for (int k = 0; k < 16; ++k) out[k] = o[k];
     return PLO_OK;
 }
 

@@ -45,6 +45,14 @@ class CSEPlan:
         return dict(zip(("steps", "full_scans", "level_rebuilds", "bisections", "spilled_pairs", "list_overflows", "candidates", "eager_refits", "extra_sweep_windows", "rows_searched",
                          "forced_merges", "merge_groups", "merge_loop_records"), out[:13]))
 
+    HBM_INFO = ("mode", "idk", "defer", "wide", "rb", "kb", "bb", "NCmax", "nv", "agg_dual", "agg_cb", "mers", "invtab", "aggbits", "pbits", "hbits")
+
+    def hbm_info(self):
+        """What the plan of the HBM-resident family chose (plo_cse_plan_hbm_info: host only, nothing is launched)."""
+        out = (ctypes.c_uint32 * 16)()
+        capi.check(capi.lib().plo_cse_plan_hbm_info(self._h, out))
+        return dict(zip(self.HBM_INFO, out[:16]))
+
     def cost_many(self, seeds=None, seed0=0, n=0):
         """(adds[], muls[]) of candidates `seeds` (or seed0..seed0+n-1): Optimizer() per seed."""
         L = capi.lib()

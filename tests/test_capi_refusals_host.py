@@ -88,6 +88,9 @@ def calls(L):
     add("plan_create_ex: null matrix", "plo_cse_plan_create_ex", None, u32(7), u32(1), ref(h))
     add("plan_create_ex: even modulus", "plo_cse_plan_create_ex", ref(A), u32(6), u32(1), ref(h))
     add("plan_is_hbm: null", "plo_cse_plan_is_hbm", None)
+    add("hbm_info: null", "plo_cse_plan_hbm_info", None, words)
+    add("hbm_info: null out", "plo_cse_plan_hbm_info", fake, None)
+    add("hbm_info: no HBM plan", "plo_cse_plan_hbm_info", fake, words)
     add("hbm_counters: null", "plo_cse_plan_hbm_counters", None, words)
     add("hbm_counters_ex: null", "plo_cse_plan_hbm_counters_ex", None, words, u32(8))
     add("hbm_counters_ex: n = 14", "plo_cse_plan_hbm_counters_ex", fake, words, u32(14))

@@ -135,7 +135,11 @@ def _hbm_cases():
         rng = random.Random(7100 + s)
         m, n = rng.randint(20, 90), rng.randint(16, 64)
         dens = rng.choice([0.15, 0.25, 0.4])
-        nv = rng.choice([0, 1, 3, 40, 600])                    # kernel modes 2 (ratio identifiers), 1 (value table in LDS) and 0 (in global memory)
+        # nv <= 3: kernel mode 2 (ratio identifiers).  The nv = 40 and 600 matrices take the value-table modes, but with independent random
+        # residues their pair triples hardly repeat: on the oracle, at the three seeds this test uses, the eleven nv = 40 cases save 0 to 29
+        # additions of 110 to 911 and the four nv = 600 cases 0 or 1 of 454 to 1103; one matrix alone (525 values)
+        # passes 512 values and so reaches mode 0, for one step.  The coverage of modes 1 and 0 is tests/test_gpu_hbm_modes.py.
+        nv = rng.choice([0, 1, 3, 40, 600])
         vals = [1, P - 1] + [rng.randint(2, P - 2) for _ in range(nv)]
         rows = [{j: rng.choice(vals) for j in range(n) if rng.random() < dens} for _ in range(m)]
         rows = [r if r else {0: 1} for r in rows]
